@@ -1,7 +1,10 @@
 """Benchmark of the MI355X-native GraspNeRF volumetric hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+`--dump-outputs DIR` writes what the last timed step computed on rank 0 (the volume and the coarse / fine render outputs) as
+DIR/<name>.npy in float32, so that two builds run with the same arguments (same seeded inputs) can be compared output for output.
 
 One STEP = one forward pass of the hot path over a batch of B synthetic scenes per GPU with all inputs already resident in
 HBM: feature-map repack (gnr_prepare) + TSDF volume (sample_volume, 40^3) + ray rendering (512 rays, 40 coarse + 40 fine
@@ -704,6 +707,27 @@ class StubPath:
         return {'k_chain.volume': (steps, 0.5 * self.ms * steps), 'k_chain.render': (2 * steps, 0.3 * self.ms * steps)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs, first_scene):
+    """--dump-outputs: the arrays the last timed step returned (sample_volume's volume, render's coarse and fine dicts; leading dim =
+    scene) -> path/volume.npy, path/coarse_<key>.npy, path/fine_<key>.npy in float32 (the 0 / 1 ray masks as 0.0 / 1.0), plus
+    path/scene_index.npy = the global scene ids of the rows.  At most DUMP_MAX_BYTES in all: a larger batch keeps a fixed seeded
+    sample of its scenes, the same rows in every array."""
+    vol, co, fi = outputs
+    arrays = {'volume': vol, **{f'coarse_{k}': v for k, v in co.items()}, **{f'fine_{k}': v for k, v in fi.items()}}
+    B = vol.shape[0]
+    per_scene = sum(v[0].numel() * 4 for v in arrays.values()) + 8
+    keep = min(B, DUMP_MAX_BYTES // per_scene)
+    rows = np.arange(B) if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    sel = torch.from_numpy(rows).to(vol.device)
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), v.index_select(0, sel).float().cpu().numpy())
+    np.save(os.path.join(path, 'scene_index.npy'), (first_scene + rows).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -724,7 +748,13 @@ def main():
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'], help='nccl = RCCL (the product); gloo only with --stub-step-ms')
     ap.add_argument('--stub-step-ms', type=float, default=0.0, help='> 0: no GPU, a step is a sleep of this length (control-flow test of the N > 1 branches)')
     ap.add_argument('--stub-parity-fail', action='store_true', help='with --stub-step-ms: rank 0 fails its parity gate (every rank must exit 3)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last of them computed on rank 0 as DIR/<name>.npy '
+                                                          '(float32, at most 64 MB: a larger batch keeps a fixed seeded sample of its scenes)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.stub_step_ms > 0:
+        ap.error('--dump-outputs needs the GPU path (a --stub-step-ms step computes nothing)')
     # host threads: the node shows 256 hardware threads, the container's cgroup grants 16 of them; torch's default 128-thread pool
     # exhausts that quota on one small CPU op and the kernel throttles the whole process for the rest of the 100 ms period
     # (graspnerf_amd/hostenv.py): every rank takes its share
@@ -823,11 +853,15 @@ def main():
     if rank == 0 and not stub:
         _lib.timing_begin(only='k_chain.volume')      # HIP events around the dominant kernel's launches, on its launch stream
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()                                          # kept for --dump-outputs
     sync()
     dt_local = time.perf_counter() - t0
     dt = max_over_ranks(dt_local, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, lo)
+    del last
     table = {}
     full = {}
     if rank == 0:

@@ -5,7 +5,8 @@ Runs only in the build container (the reference cannot travel to the GPU box).  
   tests/golden/golden_cfg1.npz     V=3, 16^3, 96x128: reference outputs (+ sha256 of inputs)
   tests/golden/golden_cfg2.npz     V=6, 40^3, 288x512, 512 rays: reference outputs
 Inputs are NOT stored: tests regenerate them from graspnerf_amd.synth.make_scene(seed) and
-check the recorded SHA-256.
+check the recorded SHA-256.  The exception is
+  tests/golden/golden_ref_ops.npz  the reference's row functions: seeded random inputs AND outputs (--ref-ops-only)
 
 Weights: `torch.manual_seed(0)` construction of the reference NeuralRayRenderer, then every
 hot-path bias / LayerNorm parameter gets + 0.1*N(0,1) (the reference zero-initialises most
@@ -596,10 +597,109 @@ def run_post():
     np.savez_compressed(ROOT + '/tests/golden/golden_post.npz', **out)
 
 
+def run_ref_ops(weights):
+    """The reference's own row functions (render_ops.py, dist_decoder.py, ibrnet.py, aggregate_net.py, neus.py) on seeded
+    random inputs -> tests/golden/golden_ref_ops.npz: inputs and outputs of every case of tests/test_oracle_vs_reference_ops.py,
+    so that the CPU oracle is checked row by row against them without the reference."""
+    from graspnerf_amd.synth import random_scene
+    import network.render_ops as rops
+    import network.dist_decoder as dd
+    import network.ibrnet as ib
+    import network.aggregate_net as an
+    import network.neus as neus
+    g = {}
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    put = lambda key, v: g.__setitem__(key, np.asarray(v.detach().numpy() if torch.is_tensor(v) else v))
+    for seed in range(8):                                            # P1-P3: projection, directions, in-image mask
+        rng = np.random.default_rng(seed)
+        ref, que, m = random_scene(int(rng.integers(0, 10 ** 6)))
+        N = 257
+        pts = (rng.uniform(-0.3, 0.3, (N, 3)) + [0, 0, 0.1]).astype(np.float32)
+        info = {'poses': t(ref['poses']), 'Ks': t(ref['Ks']), 'imgs': t(ref['imgs'])}
+        rfn = ref['poses'].shape[0]
+        uv_r, valid_r, z_r = rops.project_points_coords(t(pts), info['poses'], info['Ks'])
+        _, _, _, mk = rops.project_points_ref_views(info, t(pts))
+        for k, v in (('poses', ref['poses']), ('Ks', ref['Ks']), ('hw', np.int64([m['H'], m['W']])), ('pts', pts),
+                     ('uv', uv_r.reshape(rfn, N, 2)), ('z', z_r.reshape(rfn, N)),
+                     ('dir', rops.project_points_directions(info['poses'], t(pts)).reshape(rfn, N, 3)), ('mask', mk.reshape(rfn, N).bool())):
+            put(f'P.{seed}.{k}', v)
+    for seed in range(8):                                            # I1: bilinear feature interpolation
+        rng = np.random.default_rng(100 + seed)
+        V, C = int(rng.integers(1, 5)), int(rng.integers(1, 9))
+        h, w = int(rng.integers(8, 40)), int(rng.integers(8, 40))
+        same = seed % 2 == 0                                         # full-res map (align_corners True) or another resolution
+        fh, fw = (h, w) if same else (int(rng.integers(3, 20)), int(rng.integers(3, 20)))
+        feat = rng.standard_normal((V, C, fh, fw)).astype(np.float32)
+        uv = np.stack([rng.uniform(-2, w + 1, (V, 99)), rng.uniform(-2, h + 1, (V, 99))], -1).astype(np.float32)
+        for k, v in (('feat', feat), ('uv', uv), ('hw', np.int64([h, w])),
+                     ('out', rops.interpolate_feature_map(t(feat), t(uv), torch.ones(V, 99), h, w))):
+            put(f'I.{seed}.{k}', v)
+    for seed in range(6):                                            # S1-S3, C0, F1: depth sampling, hit prob, resampling, intervals
+        rng = np.random.default_rng(200 + seed)
+        rn, dn, fdn = int(rng.integers(1, 30)), int(rng.integers(3, 48)), int(rng.integers(3, 48))
+        dr = torch.tensor([[rng.uniform(0.1, 0.3), rng.uniform(0.6, 1.2)]], dtype=torch.float32)
+        d_ref, _ = rops.sample_depth(dr, torch.zeros(1, rn, 2), dn, False)
+        alpha = rng.random((1, rn, dn)).astype(np.float32)
+        hp = (rng.random((1, rn, dn)).astype(np.float32) ** 3)
+        torch.manual_seed(seed)
+        fd_det = rops.sample_fine_depth(d_ref, t(hp), dr, fdn, False)
+        torch.manual_seed(seed + 50)
+        fd_rnd = rops.sample_fine_depth(d_ref, t(hp), dr, fdn, True)
+        torch.manual_seed(seed + 50)
+        u = torch.rand(1, rn, fdn)[0]                                # the draw sample_fine_depth made above
+        inv = rops.depth2inv_dists(d_ref, dr)
+        near, far = dd.get_near_far_points(torch.ones(1, 1, rn, dn), inv[None], torch.tensor([[1.0, 2.0]]), True)
+        for k, v in (('shape', np.int64([rn, dn, fdn])), ('dr', dr[0]), ('alpha', alpha[0]), ('hp', hp[0]), ('u', u),
+                     ('depth', d_ref[0]), ('hit', rops.alpha_values2hit_prob(t(alpha))[0]), ('fine_det', fd_det[0]),
+                     ('fine_rand', fd_rnd[0]), ('near', near[0, 0].reshape(-1)), ('far', far[0, 0].reshape(-1))):
+            put(f'S.{seed}.{k}', v)
+    for seed in range(6):                                            # D1-D3: mixture-logistics visibility decoder
+        rng = np.random.default_rng(300 + seed)
+        V, N = int(rng.integers(1, 5)), 77
+        dec = dd.MixtureLogisticsDistDecoder({'use_vis': False})
+        dec.load_state_dict({k[len('dist_decoder.'):]: t(v) for k, v in weights.items() if k.startswith('dist_decoder.')})
+        f = (0.7 * rng.standard_normal((V, 1, N, 1, 32))).astype(np.float32)
+        z = rng.uniform(0.05, 1.0, (V, 1, N, 1)).astype(np.float32)
+        dr = np.stack([rng.uniform(0.1, 0.3, V), rng.uniform(0.6, 1.2, V)], 1).astype(np.float32)
+        with torch.no_grad():
+            prj_mean, prj_var, prj_vis, prj_aw = dec(t(f))
+            _, vis_r, hit_r = dec.compute_prob(t(z), torch.empty(1, 0), prj_mean, prj_var, prj_vis, prj_aw, True, t(dr))
+        for k, v in (('f', f.reshape(V, N, 32)), ('z', z.reshape(V, N)), ('dr', dr), ('hit', hit_r.reshape(V, N)), ('vis', vis_r.reshape(V, N))):
+            put(f'D.{seed}.{k}', v)
+    embed_fn, dim = neus.get_embedder(3, 3)
+    put('A.embed_dim', np.int64(dim))
+    for seed in range(4):                                            # A2: weighted mean / variance, A3: positional embedding
+        rng = np.random.default_rng(400 + seed)
+        x = rng.standard_normal((5, 9, 4, 7)).astype(np.float32)
+        w = rng.random((5, 9, 4, 1)).astype(np.float32)
+        mr, vr = ib.fused_mean_variance(t(x), t(w))
+        p = rng.uniform(-0.5, 0.5, (33, 3)).astype(np.float32)
+        for k, v in (('x', x), ('w', w), ('mean', mr.reshape(45, 7)), ('var', vr.reshape(45, 7)), ('p', p), ('embed', embed_fn(t(p)))):
+            put(f'A.{seed}.{k}', v)
+    for n in (16, 40):                                               # A3: the sinusoid table of the ray transformer
+        put(f'A.pos{n}', ib.IBRNetWithNeuRayNeus(32, n_samples=n).pos_encoding[0].cpu())
+    rng = np.random.default_rng(7)                                   # N1: NeuS alpha from sdf, gradient and view direction
+    rn, dn = 11, 13
+    net = an.NeusAggregationNet({'sample_num': dn, 'init_s': 0.3, 'fix_s': 0})
+    sdf = rng.uniform(-0.3, 0.3, (rn, dn)).astype(np.float32)
+    grad = rng.standard_normal((1, rn, dn, 3)).astype(np.float32)
+    qdir = rng.standard_normal((rn, 3)).astype(np.float32)
+    qdir = qdir / np.linalg.norm(qdir, axis=1, keepdims=True)
+    depth = np.sort(rng.uniform(0.2, 0.8, (rn, dn)).astype(np.float32), -1)
+    with torch.no_grad():
+        ar = net._get_alpha_from_sdf(t(sdf), t(grad), t(qdir)[None, :, None].expand(1, rn, dn, 3), rops.depth2dists(t(depth)[None]))
+    for k, v in (('sdf', sdf), ('grad', grad[0]), ('qdir', qdir), ('depth', depth), ('alpha', ar[0])):
+        put(f'N.{k}', v)
+    np.savez_compressed(ROOT + '/tests/golden/golden_ref_ops.npz', **g)
+    print('ref ops golden:', len(g), 'arrays,', sum(v.nbytes for v in g.values()), 'bytes')
+
+
 def main():
     renderer = import_reference()
     if '--post-only' in sys.argv:
         return run_post()
+    if '--ref-ops-only' in sys.argv:
+        return run_ref_ops(dict(np.load(ROOT + '/tests/golden/weights_seed0.npz')))
     if '--train-step-only' in sys.argv:
         if '--vis' in sys.argv:
             return run_train_step(renderer, 1, 13, 99, 7, 'golden_train_step_vis.npz', use_vis=True)
@@ -657,6 +757,7 @@ def main():
     run_train_step(renderer, 3, 11, 77, 9, 'golden_train_step_b.npz')
     run_train_step(renderer, 1, 13, 99, 7, 'golden_train_step_vis.npz', use_vis=True)
     run_train_step(renderer, 2, 17, 55, 3, 'golden_train_step_all.npz', use_all=True)
+    run_ref_ops(weights)
 
 
 if __name__ == '__main__':
