@@ -1,6 +1,6 @@
 """Benchmark of the MI355X-native GraspNeRF volumetric hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--dump-outputs DIR` writes what the last timed step computed on rank 0 (the volume and the coarse / fine render outputs) as
@@ -11,15 +11,20 @@ HBM: feature-map repack (gnr_prepare) + TSDF volume (sample_volume, 40^3) + ray 
 samples, ground-truth pixel colours), 6 views of 288x512 (BASELINE.json configs[2]; configs[3] = the same on 8 GPUs).
 Scenes are independent, so N GPUs shard scenes with no data-path collective (weak scaling: B scenes per GPU).
 
-Before any timing is accepted rank 0 runs a PARITY GATE: scene 0 of its batch is the scene tests/golden/golden_cfg2.npz pins
-(outputs of the imported reference), and the batched launch must reproduce it.
+A plain run does only what the headline needs: set-up, one first step, the warm-up, the timed steps (HIP events around the
+dominant kernel's launches inside them give `roofline`), --dump-outputs, and the line.  Everything else runs with `--full` only:
+the parity gate, the per-kernel table, the stand-alone / render-launch / counter figures of `roofline` and the recorded float64
+arbiter (null in a plain line), and the legs below (absent from it).
+
+With `--full`, before any timing is accepted rank 0 runs a PARITY GATE: scene 0 of its batch is the scene
+tests/golden/golden_cfg2.npz pins (outputs of the imported reference), and the batched launch must reproduce it.
 
 `--dist-backend gloo --stub-step-ms T` runs the SAME control flow without a GPU (the step is a sleep): the N > 1 branches --
 RCCL rank count, barrier + MAX-over-ranks, per-rank gather, parity-gate failure propagation, the train leg's all-reduce
 record -- are executed under gloo by tests/test_bench_dist.py, so the first multi-GPU lease does not debug them.
 
-After the forward leg the same process measures, outside the headline's timed region and reported as sub-records of the ONE
-JSON line rank 0 prints:  `train_step` = BASELINE.json configs[4] (8 full-size scenes per GPU: backbones + volumetric path +
+With `--full`, after the forward leg the same process measures, outside the headline's timed region and reported as sub-records
+of the ONE JSON line rank 0 prints:  `train_step` = BASELINE.json configs[4] (8 full-size scenes per GPU: backbones + volumetric path +
 grasp head + losses, backward, one flat gradient all-reduce over RCCL, Adam);  `with_backbones` = images -> volume + render +
 grasps (N = 1 only);  `cpu_baseline` = the oracle on the host cores (N = 1 only).  See DESIGN.md §6.
 """
@@ -434,7 +439,7 @@ def f32_mfma_build_leg(value):
     for k in [k for k in env if k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'GROUP_RANK', 'ROLE_RANK', 'LOCAL_WORLD_SIZE') or k.startswith(('TORCHELASTIC', 'MASTER_'))]:
         env.pop(k)                                          # the child is a plain single-process run, also under torch.distributed.run
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '60', '--warmup', '10', '--no-train', '--no-backbones',
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--steps', '60', '--warmup', '10', '--full', '--no-train', '--no-backbones',
                             '--no-cpu-baseline', '--no-f32-build', '--no-live-pmc'], env=env, capture_output=True, text=True, timeout=300)
         d = json.loads(r.stdout.strip().splitlines()[-1])
     except Exception as e:                                  # noqa: BLE001  (a failed companion run must not lose the product's line)
@@ -734,11 +739,15 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=32, help='scenes per GPU per step')
+    ap.add_argument('--full', action='store_true', help='also run what the headline does not need: the parity gate, the per-kernel table, the '
+                                                        'stand-alone and counter figures of roofline, and the legs behind the timed steps '
+                                                        '(train_step, with_backbones, f32_mfma_build, cpu_baseline); the --no-* options '
+                                                        'below select among them')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-train', action='store_true', help='skip the configs[4] train-step sub-record')
     ap.add_argument('--no-backbones', action='store_true', help='skip the images -> grasps figure')
     ap.add_argument('--no-live-pmc', action='store_true', help='skip the two rocprofv3 --pmc child passes that measure roofline.traffic in this run (N = 1)')
-    ap.add_argument('--extras-budget-s', type=float, default=300.0, help='wall-clock budget of the OPTIONAL legs behind the timed steps (live PMC child passes, the 2-CPU train child, images -> grasps, the fp32-MFMA companion build): a leg that would start beyond it is skipped and the line says so; the timed forward steps, the train_step record and cpu_baseline always run')
+    ap.add_argument('--extras-budget-s', type=float, default=300.0, help='wall-clock budget of the OPTIONAL legs behind the timed steps (live PMC child passes, the 2-CPU train child, images -> grasps, the fp32-MFMA companion build): a leg that would start beyond it is skipped and the line says so; with --full the train_step record and cpu_baseline always run')
     ap.add_argument('--no-f32-build', action='store_true', help='skip timing the fp32-MFMA companion build next to the product')
     ap.add_argument('--train-scenes', type=int, default=8)
     ap.add_argument('--no-train-2cpu', action='store_true', help='skip the train step of a child process pinned to 2 CPUs (the host budget of one rank of an 8-rank node)')
@@ -747,7 +756,7 @@ def main():
     ap.add_argument('--train-warmup', type=int, default=24, help='the caching allocators and MIOpen (solvers compiled on their first uses) settle over ~20 steps: profiles/r03_d, r03_f show stalled steps up to the 13th')
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'], help='nccl = RCCL (the product); gloo only with --stub-step-ms')
     ap.add_argument('--stub-step-ms', type=float, default=0.0, help='> 0: no GPU, a step is a sleep of this length (control-flow test of the N > 1 branches)')
-    ap.add_argument('--stub-parity-fail', action='store_true', help='with --stub-step-ms: rank 0 fails its parity gate (every rank must exit 3)')
+    ap.add_argument('--stub-parity-fail', action='store_true', help='with --stub-step-ms --full: rank 0 fails its parity gate (every rank must exit 3)')
     ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last of them computed on rank 0 as DIR/<name>.npy '
                                                           '(float32, at most 64 MB: a larger batch keeps a fixed seeded sample of its scenes)')
     args = ap.parse_args()
@@ -819,14 +828,14 @@ def main():
         rccl_ranks = int(one.item())
         assert rccl_ranks == dist.get_world_size()
 
-    # ---- parity gate in front of the warm-up and the timed region (rank 0 holds scene 0 = the scene the reference golden pins).  It
-    # stands BEFORE the warm-up steps since round 6: the gate compares on the host for a few hundred milliseconds while the GPU idles
-    # and drops its clocks, and a timed region that started right behind it ran its first ~20 steps 2.5 % slow (20 timed steps:
-    # 6.47 ms per step with 5 or 50 warm-up steps alike, 200 timed steps: 6.32) -- the warm-up exists to absorb exactly that.
+    # ---- parity gate (--full) in front of the warm-up and the timed region (rank 0 holds scene 0 = the scene the reference golden
+    # pins).  It stands BEFORE the warm-up steps since round 6: the gate compares on the host for a few hundred milliseconds while the
+    # GPU idles and drops its clocks, and a timed region that started right behind it ran its first ~20 steps 2.5 % slow (20 timed
+    # steps: 6.47 ms per step with 5 or 50 warm-up steps alike, 200 timed steps: 6.32) -- the warm-up exists to absorb exactly that.
     step()                                                 # (first use: allocations, attribute calls)
     parity = None
     range_flags = None
-    if rank == 0 and B >= 1:
+    if args.full and rank == 0 and B >= 1:
         try:
             if stub:
                 if args.stub_parity_fail:
@@ -842,7 +851,7 @@ def main():
                 del vol, co, fi, inds
         except SystemExit as e:                            # no timing is accepted: tell the other ranks, then stop
             print(e, file=sys.stderr, flush=True)
-    ok = max_over_ranks(0.0 if (rank != 0 or parity is not None) else 1.0, dev) == 0.0
+    ok = not args.full or max_over_ranks(0.0 if (rank != 0 or parity is not None) else 1.0, dev) == 0.0
     if not ok:
         if dist is not None:
             dist.destroy_process_group()
@@ -866,16 +875,17 @@ def main():
     full = {}
     if rank == 0:
         if stub:
-            table, full = hp.table(args.steps), hp.table(5)
+            table, full = hp.table(args.steps), (hp.table(5) if args.full else {})
         else:
             table = _lib.timing_end()
-            # per-kernel table: a few further steps with every launch bracketed (outside the timed region: 14 event pairs per
-            # step cost ~2 % of it)
-            _lib.timing_begin()
-            for _ in range(5):
-                step()
-            torch.cuda.synchronize()
-            full = _lib.timing_end()
+            if args.full:
+                # per-kernel table: a few further steps with every launch bracketed (outside the timed region: 14 event pairs per
+                # step cost ~2 % of it)
+                _lib.timing_begin()
+                for _ in range(5):
+                    step()
+                torch.cuda.synchronize()
+                full = _lib.timing_end()
     per_rank = None
     if dist is not None:
         mine = torch.tensor([B * args.steps / dt_local], device=dev)
@@ -885,24 +895,35 @@ def main():
 
     out = None
     if rank == 0:
-        # dominant kernel: average of the HIP-event pairs recorded around each of its launches INSIDE the timed region; a
-        # stand-alone re-timing is reported next to it
+        # dominant kernel: average of the HIP-event pairs recorded around each of its launches INSIDE the timed region; with --full
+        # a stand-alone re-timing is reported next to it
         n_vol, t_vol = table['k_chain.volume']
-        n_ren, t_ren = full['k_chain.render']
         ms = t_vol / n_vol
-        ms_ren = t_ren / n_ren
-        ms_alone = args.stub_step_ms * 0.5 if stub else hp.time_chain_kernel(bref, res, iters=10)
+        ms_alone = None
+        if args.full:
+            ms_alone = args.stub_step_ms * 0.5 if stub else hp.time_chain_kernel(bref, res, iters=10)
         fl_alg = chain_flops(B * res ** 3, c['V'], render=False)
         fl_exe = executed_mfma_flops(B * res ** 3, False)
-        fl_ren = executed_mfma_flops(B * rn * dn, True)
-        fl_ren_alg = chain_flops(B * rn * dn, c['V'], render=True)
         achieved = fl_exe / (ms * 1e-3) / 1e12
         _EXTRAS['budget'] = args.extras_budget_s
-        if world == 1 and not args.no_live_pmc and not stub and extras_left('live_pmc'):
+        if args.full and world == 1 and not args.no_live_pmc and not stub and extras_left('live_pmc'):
             live_pmc()                                   # counters of THIS run when the box has the profiler (else the recorded, sha-stamped ones)
-        traffic, counters, valu = (None, None, None) if stub else recorded_pmc(B)
+        traffic, counters, valu = recorded_pmc(B) if args.full and not stub else (None, None, None)
         if counters is not None:
             counters['live'] = _LIVE_PMC['info']
+        render_launch = None
+        if full:
+            n_ren, t_ren = full['k_chain.render']
+            ms_ren = t_ren / n_ren
+            fl_ren = executed_mfma_flops(B * rn * dn, True)
+            fl_ren_alg = chain_flops(B * rn * dn, c['V'], render=True)
+            render_launch = {'kernel': 'k_chain<6,true> on the ray points (2 launches per step)', 'ms_per_launch': round(ms_ren, 4),
+                             'achieved': round(fl_ren_alg / (ms_ren * 1e-3) / 1e12, 2),
+                             'frac': round(fl_ren_alg / (ms_ren * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS, 4), 'flops_per_launch': fl_ren_alg,
+                             'flops_per_point': 2 * (c['V'] * MAC_VIEW_RAY + MAC_POINT_CHAIN), 'points_per_launch': B * rn * dn,
+                             'frac_executed': round(fl_ren / (ms_ren * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS, 4), 'flops_per_launch_executed': fl_ren,
+                             'traffic': ((counters or {}).get('other_kernels', {}).get('k_chain<6, true, false, false, true>') or {}).get('traffic'),
+                             'l2_hit_rate': ((counters or {}).get('other_kernels', {}).get('k_chain<6, true, false, false, true>') or {}).get('l2_hit_rate')}
         out = {
             'metric': METRIC, 'value': round(world * B * args.steps / dt, 3), 'unit': 'scenes/s', 'n_gpus': world,
             'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
@@ -912,7 +933,7 @@ def main():
                           'DESIGN.md 4.1b; as close to a float64 evaluation as the fp32 CPU oracle, tests/test_range_guard.py); operands beyond the '
                           'fp16 range make the launch fall back to the fp32-input MFMA (range_flags); f32_mfma_build is the same step with '
                           'every product on fp32 instructions',
-            'fp64_arbiter_at_benched_shape': None if stub else recorded_arbiter(),
+            'fp64_arbiter_at_benched_shape': recorded_arbiter() if args.full and not stub else None,
             'parity_checked': parity is not None, 'parity': parity, 'range_flags': range_flags,
             'host_threads': {'torch_intra_op': host_threads, 'cpu_budget': cpu_budget(), 'cpus_visible': os.cpu_count()},
             'config': {'workload': f'{B} scenes/GPU/step, 6 views 288x512 (feature maps 72x128x32 x2), 40^3 TSDF volume + '
@@ -934,7 +955,7 @@ def main():
                          'achieved_executed': round(achieved, 2), 'frac_executed': round(achieved / PEAK_F16_MFMA_TFLOPS, 4),
                          'flops_per_launch_executed': fl_exe,
                          'kernel': 'k_chain<6,false> on the volume points', 'ms_per_launch': round(ms, 4),
-                         'launches_timed': n_vol, 'ms_per_launch_standalone': round(ms_alone, 4),
+                         'launches_timed': n_vol, 'ms_per_launch_standalone': None if ms_alone is None else round(ms_alone, 4),
                          'note': 'frac = achieved / peak with achieved = flops_per_launch / ms_per_launch (algorithmic fp32 FLOPs, SURVEY 8d); '
                                  'frac_executed = flops_per_launch_executed / ms_per_launch / peak (696 v_mfma_f32_16x16x32_f16 + 114 '
                                  'v_mfma_f32_16x16x4_f32 per 16-point tile; counters.mfma_per_launch / (points_per_launch / 16) = 810 agrees).  '
@@ -945,14 +966,8 @@ def main():
                          'algorithmic_fp32_equiv': {'tflops': round(fl_alg / (ms * 1e-3) / 1e12, 2), 'flops_per_launch': fl_alg,
                                                     'note': 'un-hoisted fp32 FLOPs 2*(6*27736+6528) per point (SURVEY.md 8d); the fp32-instruction peak of '
                                                             'the part is 157.3 TFLOP/s (f32_mfma_build.frac_of_fp32_mfma_peak is measured against it)'},
-                         'render_launch': {'kernel': 'k_chain<6,true> on the ray points (2 launches per step)', 'ms_per_launch': round(ms_ren, 4),
-                                           'achieved': round(fl_ren_alg / (ms_ren * 1e-3) / 1e12, 2),
-                                           'frac': round(fl_ren_alg / (ms_ren * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS, 4), 'flops_per_launch': fl_ren_alg,
-                                           'flops_per_point': 2 * (c['V'] * MAC_VIEW_RAY + MAC_POINT_CHAIN), 'points_per_launch': B * rn * dn,
-                                           'frac_executed': round(fl_ren / (ms_ren * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS, 4), 'flops_per_launch_executed': fl_ren,
-                                           'traffic': ((counters or {}).get('other_kernels', {}).get('k_chain<6, true, false, false, true>') or {}).get('traffic'),
-                                           'l2_hit_rate': ((counters or {}).get('other_kernels', {}).get('k_chain<6, true, false, false, true>') or {}).get('l2_hit_rate')}},
-            'kernels_ms_per_step': {k: round(v[1] / 5, 4) for k, v in sorted(full.items(), key=lambda kv: -kv[1][1])},
+                         'render_launch': render_launch},
+            'kernels_ms_per_step': {k: round(v[1] / 5, 4) for k, v in sorted(full.items(), key=lambda kv: -kv[1][1])} if full else None,
         }
         # SURVEY.md §8d extras: the whole step against the HBM roof (26.0 MB compulsory bytes per scene, TSDF + render) and the
         # recorded counters of the dominant kernel
@@ -962,15 +977,15 @@ def main():
                                          'traffic_GBps_dominant_kernel': None if traffic is None else round(traffic / (ms * 1e-3) / 1e9, 1)}
         out['roofline']['counters'] = counters
     step_ms = dt / args.steps * 1e3
-    if not args.no_train:
+    if args.full and not args.no_train:
         rec = train_leg_stub(args, world, rank, dev, dist, sync) if stub else train_leg(args, world, rank, dev, dist, sync)
         if rank == 0:
             out['train_step'] = rec
-    if rank == 0 and world == 1 and not args.no_backbones and not stub and extras_left('with_backbones'):
+    if args.full and rank == 0 and world == 1 and not args.no_backbones and not stub and extras_left('with_backbones'):
         out['with_backbones'] = backbone_leg(hp, bref, bque, dev, B, step_ms)
-    if rank == 0 and world == 1 and not args.no_f32_build and not stub and extras_left('f32_mfma_build'):
+    if args.full and rank == 0 and world == 1 and not args.no_f32_build and not stub and extras_left('f32_mfma_build'):
         out['f32_mfma_build'] = f32_mfma_build_leg(out['value'])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:    # the CPU leg is reported at N=1 only (the other ranks would wait)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:    # the CPU leg is reported at N=1 only (the other ranks would wait)
         out['cpu_baseline'] = cpu_baseline(wnp)
     if rank == 0:
         out['optional_legs_skipped_for_time'] = _EXTRAS['skipped']

@@ -29,7 +29,7 @@ def _run(world, extra, timeout=240):
 
 
 def test_two_ranks_print_one_line_with_the_multi_rank_records():
-    r = _run(2, [])
+    r = _run(2, ['--full'])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]                       # rank 0 only
@@ -49,10 +49,27 @@ def test_two_ranks_print_one_line_with_the_multi_rank_records():
 
 
 def test_a_failed_parity_gate_on_rank_0_stops_every_rank_before_timing():
-    r = _run(2, ['--stub-parity-fail'])
+    r = _run(2, ['--full', '--stub-parity-fail'])
     assert r.returncode != 0
     assert 'parity gate FAILED' in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith('{')]      # no bench line
+
+
+def test_a_plain_run_prints_the_headline_without_the_full_records():
+    """Without --full: no parity gate, no per-kernel table or stand-alone re-timing, no legs behind the timed steps; the headline
+    and the roofline of the timed region's own HIP events are there."""
+    r = _run(2, [])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['metric'] and d['unit'] == 'scenes/s' and d['higher_is_better'] is True and d['dtype'] == 'f32' and d['steps'] == 4
+    assert abs(d['value'] - 64 / (d['ms_per_step'] * 1e-3)) < 1e-3 * d['value']
+    assert d['rccl_ranks'] == 2 and len(d['per_rank_scenes_per_s']) == 2
+    assert d['roofline']['frac'] <= 1.0 and d['roofline']['launches_timed'] == 4
+    assert not d['parity_checked'] and d['parity'] is None and d['kernels_ms_per_step'] is None
+    assert d['roofline']['ms_per_launch_standalone'] is None and d['roofline']['render_launch'] is None
+    assert not {'train_step', 'cpu_baseline', 'with_backbones', 'f32_mfma_build'} & set(d)
 
 
 def test_gpus_flag_must_match_the_launch():
