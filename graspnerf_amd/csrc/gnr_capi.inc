@@ -35,6 +35,7 @@ struct Workspace {
     float* feat64; float* viewp; unsigned* range_flag;             // persistent between gnr_prepare and the forwards
     float* desc; float* rec; float* depth_c; float* depth_f; float* depth_m; float* gerr_part; unsigned char* vmask_pts;   // per call
     int* ray_perm;                                                  // per call: Morton order of the rays (k_ray_order)
+    int* sample_perm; unsigned char* sample_keys;                   // per render pass: view-mask order of the samples (k_points_rays, k_sample_order); used up to MAX_SORT_SAMPLES
     size_t total;
 };
 
@@ -57,6 +58,10 @@ static Workspace carve(const GnrScene* s, size_t P, size_t rn, void* base) {
     w.gerr_part = (float*)take((size_t)s->B * (rn > 0 ? rn : 1) * sizeof(float));
     w.vmask_pts = (unsigned char*)take((size_t)s->B * P);
     w.ray_perm = (int*)take((size_t)s->B * (rn > 0 ? rn : 1) * sizeof(int));
+    // ray samples only (rn == 0: volume points, never ordered).  Reserved for every P, also above MAX_SORT_SAMPLES where no pass uses it: the
+    // total grows with P, so a workspace sized for P serves every call of the same rn with fewer points
+    w.sample_perm = rn > 0 ? (int*)take((size_t)s->B * P * sizeof(int)) : nullptr;
+    w.sample_keys = rn > 0 ? (unsigned char*)take((size_t)s->B * P) : nullptr;
     w.total = off;
     return w;
 }
@@ -588,23 +593,45 @@ static int order_rays(const GnrScene* s, const GnrRays* q, Workspace& w, hipStre
     return GNR_OK;
 }
 
+// View-mask order of a render pass's samples (csrc/gnr_sample_order.h) behind its k_points_rays: -> w.sample_perm, or null = natural order:
+//   GNR_OPT_SAMPLE_ORDER_NATURAL;  more than MAX_SORT_SAMPLES samples per scene;  a launch of fewer than SAMPLE_ORDER_MIN_TILES_PER_SLOT tiles
+//   per wavefront slot of the device.  Measured at 512 rays x 40 (0.625 B tiles per slot; profiles/sample_order_ab.json): the two chain launches
+//   of a step gain 0.00 / 0.04 / 0.04 / 0.07 / 0.22 ms at B = 1 / 2 / 4 / 8 / 32, the two sorts cost 0.09 ms at every B (one workgroup per
+//   scene, 43 us a launch): the step loses 0.05 ms at B = 4, 0.02 at B = 8 and wins 0.10 at B = 32; break-even near B = 12 = 7.5 tiles per slot.
+constexpr int SAMPLE_ORDER_MIN_TILES_PER_SLOT = 8;
+static bool sample_order_wanted(const GnrScene* s, const Workspace& w, int P) {
+    if (opt(s, GNR_OPT_SAMPLE_ORDER_NATURAL) || !w.sample_perm || !w.sample_keys || P > MAX_SORT_SAMPLES) return false;
+    const long ntiles = (long)s->B * ((P + 15) / 16), slots = (long)num_cus() * (GNR_CHAIN_THREADS / 64);
+    return ntiles >= SAMPLE_ORDER_MIN_TILES_PER_SLOT * slots;
+}
+static int launch_sample_order(const unsigned char* keys, int* perm, int B, int P, int nkeys, hipStream_t st) {
+    { KScope ks("k_sample_order@render_pass", st); hipLaunchKernelGGL(k_sample_order, dim3(B), dim3(1024), 0, st, keys, perm, P, nkeys); }
+    GNR_HIP(hipGetLastError());
+    return GNR_OK;
+}
 // gt_also / skip_gt: the ground-truth colours of the rays are the same in both passes of gnr_render_rays_fwd: the coarse pass's launch writes
 // the fine pass's array too (gt_also), the fine pass skips its own (skip_gt)
 static int render_pass(const GnrScene* s, const GnrRays* q, const float* depth, int dn, const float* wl, GnrRenderOut* out,
                        Workspace& w, hipStream_t st, float* fine_depth, int* fine_inds, int fdn, const float* fine_u = nullptr,
-                       const int* perm = nullptr, int range_slot = RS_COARSE, float* gt_also = nullptr, bool skip_gt = false, bool gen_depth = false) {
+                       const int* perm = nullptr, int range_slot = RS_COARSE, float* gt_also = nullptr, bool skip_gt = false, bool gen_depth = false,
+                       const int* sample_perm_in = nullptr) {      // sample_perm_in: gnr_debug_render_by_depth_perm (a caller-given order instead of the pass's own)
     if (!out || !out->colors_nr) return fail(GNR_ERR_ARG, "GnrRenderOut.colors_nr is required");
     const int B = s->B, rn = q->rn;
     const int P = rn * dn;
+    const bool ordered = !sample_perm_in && sample_order_wanted(s, w, P);      // the pass's own view-mask order: keys from k_points_rays, then the sort
     { KScope ks("k_points_rays@render_pass", st); hipLaunchKernelGGL(k_points_rays, dim3((B * P + 255) / 256), dim3(256), 0, st, q->coords, q->que_pose, q->que_K,
-                       q->que_depth_range, depth, w.desc, rn, dn, B, perm, gen_depth ? const_cast<float*>(depth) : nullptr); }    // gen_depth: the coarse pass's depths are generated here, into `depth`
+                       q->que_depth_range, depth, w.desc, rn, dn, B, perm, gen_depth ? const_cast<float*>(depth) : nullptr,     // gen_depth: the coarse pass's depths are generated here, into `depth`
+                       ordered ? w.sample_keys : nullptr, w.viewp, s->V, s->H, s->W); }
     GNR_HIP(hipGetLastError());
+    if (ordered)
+        if (int rc = launch_sample_order(w.sample_keys, w.sample_perm, B, P, 1 << s->V, st)) return rc;
     ChainArgs a{wl, w.feat64, s->imgs, w.viewp, w.desc, w.rec, out->colors_nr, out->view_mask, nullptr,
                 B, P, s->H, s->W, s->fh, s->fw, 0};
     a.range_flag = w.range_flag;
     a.range_launch = w.range_flag ? w.range_flag + range_slot : nullptr;      // watch word of this pass (RS_COARSE: coarse / by-depth, RS_FINE)
     a.tile_ctr = (w.range_flag && !opt(s, GNR_OPT_STATIC_TILES)) ? w.range_flag + RS_WORDS : nullptr;
     a.ray_perm = perm; a.perm_rn = rn; a.perm_dn = dn;
+    a.sample_perm = ordered ? w.sample_perm : sample_perm_in;
     if (int rc = launch_chain<true>(s, a, st)) return rc;
     RayArgs r;
     memset(&r, 0, sizeof(r));
@@ -654,6 +681,53 @@ extern "C" int gnr_render_by_depth_fwd(const GnrScene* s, const GnrRays* q, cons
     const int* perm = nullptr;
     if (int rc = order_rays(s, q, w, (hipStream_t)stream, &perm)) return rc;
     return render_pass(s, q, depth, dn, wl, out, w, (hipStream_t)stream, nullptr, nullptr, 0, nullptr, perm);
+}
+
+// Test tooling: gnr_render_by_depth_fwd with a caller-given order of every scene's samples (sample_perm [B][rn*dn] int32 on the device, each
+// row a permutation of 0 .. rn*dn-1) in place of the pass's own: the outputs do not depend on it.
+extern "C" int gnr_debug_render_by_depth_perm(const GnrScene* s, const GnrRays* q, const float* depth, int dn, const float* wl,
+                                              GnrRenderOut* out, const int* sample_perm, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_scene(s)) return rc;
+    if (int rc = check_rays(q, true)) return rc;
+    if (!depth || !wl || !ws || !sample_perm) return fail(GNR_ERR_ARG, "gnr_debug_render_by_depth_perm: null pointer");
+    if (dn < 3 || dn > MAX_DN_FWD) return fail(GNR_ERR_SHAPE, "dn must be in 3..128");
+    if (int rc = check_points(s, (size_t)q->rn * dn)) return rc;
+    Workspace w = carve(s, (size_t)q->rn * dn, q->rn, ws);
+    if (ws_bytes < w.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
+    const int* perm = nullptr;
+    if (int rc = order_rays(s, q, w, (hipStream_t)stream, &perm)) return rc;
+    return render_pass(s, q, depth, dn, wl, out, w, (hipStream_t)stream, nullptr, nullptr, 0, nullptr, perm, RS_COARSE, nullptr, false, false, sample_perm);
+}
+
+// Test tooling: the device sort alone -- keys [B][P] bytes on the device -> perm [B][P] int32 (what a render pass builds from its own keys;
+// no threshold).  gnr_sample_order_host: the same permutation of one scene on the host (csrc/gnr_sample_order.h; no device work).
+// gnr_sample_order_offsets: byte offsets of the keys [B][P] and the permutation [B][P] of the LAST render pass inside a workspace that was
+// carved for P = rn * dn_max samples per scene (gnr_workspace_bytes' arguments); GNR_ERR_SHAPE when such a workspace has neither.
+extern "C" int gnr_debug_sample_order(const unsigned char* keys, int B, int P, int* perm, void* stream) {
+    if (!keys || !perm) return fail(GNR_ERR_ARG, "gnr_debug_sample_order: null pointer");
+    if (B < 1 || P < 1 || P > MAX_SORT_SAMPLES) return fail(GNR_ERR_SHAPE, "gnr_debug_sample_order: 1 <= P <= 2^18 samples per scene");
+    return launch_sample_order(keys, perm, B, P, 256, (hipStream_t)stream);
+}
+extern "C" int gnr_sample_order_host(const unsigned char* keys, int P, int* perm_out) {
+    if (!keys || !perm_out) return fail(GNR_ERR_ARG, "gnr_sample_order_host: null pointer");
+    if (P < 1) return fail(GNR_ERR_SHAPE, "gnr_sample_order_host: P must be positive");
+    int start[256], hist[256] = {0};
+    for (int i = 0; i < P; ++i) ++hist[keys[i]];
+    for (int k = 0; k < 256; ++k) {
+        start[k] = 0;
+        for (int k2 = 0; k2 < 256; ++k2) if (sorder::key_before(k2, k)) start[k] += hist[k2];
+    }
+    for (int i = 0; i < P; ++i) perm_out[sorder::slot_of(start[keys[i]]++, P)] = i;
+    return GNR_OK;
+}
+extern "C" int gnr_sample_order_offsets(const GnrScene* s, int rn, int dn_max, size_t* keys_off, size_t* perm_off) {
+    if (!s || !keys_off || !perm_off) return fail(GNR_ERR_ARG, "gnr_sample_order_offsets: null pointer");
+    if (rn < 1 || dn_max < 1) return fail(GNR_ERR_SHAPE, "gnr_sample_order_offsets: rn, dn_max must be positive");
+    char* const base = (char*)4096;
+    Workspace w = carve(s, (size_t)rn * dn_max, rn, base);
+    if ((size_t)rn * dn_max > (size_t)MAX_SORT_SAMPLES) return fail(GNR_ERR_SHAPE, "gnr_sample_order_offsets: more samples per scene than the sort handles");
+    *keys_off = (size_t)((char*)w.sample_keys - base); *perm_off = (size_t)((char*)w.sample_perm - base);
+    return GNR_OK;
 }
 
 extern "C" int gnr_render_rays_fwd(const GnrScene* s, const GnrRays* q, const float* wc, const float* wf, GnrRenderOut* coarse,

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "gnr_layout.h"
+#include "gnr_sample_order.h"
 
 // GNR_ABLATE: timing-only diagnostic builds of k_chain (tools/ab_chain.py; results are WRONG, never shipped): bit 0 no rotation of
 // the per-view state, bit 1 projection / tap arithmetic of view 0 reused for every view, bit 2 no residual half (m = 0),
@@ -531,12 +532,18 @@ __global__ __launch_bounds__(256) void k_ray_order(const float* __restrict__ coo
     for (int i = threadIdx.x; i < rn; i += 256) perm[(size_t)b * rn + i] = (int)(key[i] & 0xFFFu);
 }
 
+// key of a point for the sample order of the inference render passes (csrc/gnr_sample_order.h): bit v set iff the point lies inside view v
+// (project_view's mask, the input of k_chain's skip ballot); defined behind project_view
+DEV unsigned view_mask_key(const float* __restrict__ viewp_b, const float (&p)[3], int V, int H, int W);
+
 // ref: render_ops.py:4-39 (rays, unnormalised directions), :41-52 + dist_decoder.py:34-38 (intervals)
 // perm (nullable): descriptor slot (b, s, k) holds sample k of ray perm[b][s] (k_ray_order); coords / depth are in the caller's order
+// keys (nullable; then viewp [B*V][VIEWP_FLOATS], V, H, W): keys[b][slot * dn + k] = view_mask_key of the point
 __global__ void k_points_rays(const float* __restrict__ coords, const float* __restrict__ que_pose,
                               const float* __restrict__ que_K, const float* __restrict__ que_dr,
                               const float* __restrict__ depth, float* __restrict__ desc, int rn, int dn, int B,
-                              const int* __restrict__ perm = nullptr, float* __restrict__ depth_gen = nullptr) {
+                              const int* __restrict__ perm = nullptr, float* __restrict__ depth_gen = nullptr,
+                              unsigned char* __restrict__ keys = nullptr, const float* __restrict__ viewp = nullptr, int V = 0, int H = 0, int W = 0) {
     // depth_gen: the coarse pass -- the depths are k_coarse_depth's (same arithmetic), computed here and written to depth_gen; `depth` is not read
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * rn * dn) return;
@@ -570,12 +577,15 @@ __global__ void k_points_rays(const float* __restrict__ coords, const float* __r
     auto inv = [&](int j) { return __fdiv_rn(__fsub_rn(__fdiv_rn(-1.f, z(j)), near), __fsub_rn(far, near)); };
     auto half = [&](int j) { return (j == dn - 1) ? 0.5e6f : __fmul_rn(__fsub_rn(inv(j + 1), inv(j)), 0.5f); };
     float* d = desc + (size_t)i * DESC_FLOATS;
+    float pw[3];
     for (int c = 0; c < 3; ++c) {
-        d[c] = tr[c] + dir[c] * zk;
+        pw[c] = tr[c] + dir[c] * zk;
+        d[c] = pw[c];
         d[3 + c] = -dir[c] / nrm;
     }
     d[6] = half(k == 0 ? 0 : k - 1);
     d[7] = half(k);
+    if (keys) keys[i] = (unsigned char)view_mask_key(viewp + (size_t)b * V * VIEWP_FLOATS, pw, V, H, W);
 }
 
 // sample points and query directions of a render pass as plain tensors (the inputs of the training pass's backward kernels):
@@ -618,6 +628,9 @@ struct ChainArgs {
     // inference render passes: the points are laid out in the Morton order of their rays (k_ray_order); the user-visible
     // per-point outputs (colours, view masks) go to the caller's ray order: point (slot s, sample k) -> ray_perm[b][s] * dn + k
     const int* ray_perm; int perm_rn, perm_dn;
+    // inference render passes: slot n of scene b processes point sample_perm[b][n] (k_sample_order: a scene's samples grouped by view mask, so
+    // that whole tiles skip their masked views); null = natural order.  Everything a point reads and writes follows the point, not the slot.
+    const int* sample_perm;
     // dynamic tile hand-out (null: static round-robin).  [x] = next tile of XCD x's chunk, [8] = wavefronts of the launch that are through:
     // zero before the first launch (gnr_prepare), set back to zero by the last wavefront of every launch
     unsigned* tile_ctr;
@@ -753,6 +766,83 @@ constexpr int SW = 20;     // per-view state width: X[9] E[8] gate m rgb  /  H2[
 // rows of the two queues
 constexpr int rows_a(int V) { return GNR_TWO_QUEUES ? (V + 1) / 2 : V; }
 constexpr int rows_b(int V) { return GNR_TWO_QUEUES ? V / 2 : 0; }
+
+// ---- sample order of the inference render passes (csrc/gnr_sample_order.h) ----
+// (project_view<false>: FULL only adds the point-to-camera direction terms dd[]; u, v, z and the mask m are the same statements in both
+// instantiations, so the key is bit for bit the m of the project_view<true> / project_coop that k_chain ballots on)
+DEV unsigned view_mask_key(const float* __restrict__ viewp_b, const float (&p)[3], int V, int H, int W) {
+    const float qd[3] = {0.f, 0.f, 0.f};
+    unsigned k = 0;
+    for (int v = 0; v < V; ++v) {
+        ViewGeom vg;
+        project_view<false>(viewp_b + v * VIEWP_FLOATS, p, qd, H, W, vg);
+        k |= (vg.m != 0.f ? 1u : 0u) << v;
+    }
+    return k;
+}
+// perm[b][sorder::slot_of(position of sample i in the stable key sort)] = i.  One workgroup of 16 wavefronts per scene: wavefront w owns the
+// contiguous segment w of the samples; per-(wavefront, key) counts -> exclusive offsets (groups in sorder::key_before order, then wavefront
+// order), then every wavefront walks its segment 64 samples at a time and ranks the lanes of equal key by lane id.  Integer counts and fixed
+// ownership only: the same keys give the same permutation.  The keys of SO_DEPTH steps are loaded together (a step's rank depends on the step
+// before it, and with one load per step the launch took 52 us, all of it load latency).  nkeys: every key is below it (1 << V; 256 = any byte).
+constexpr int MAX_SORT_SAMPLES = 1 << 18;       // per scene; above it the passes keep the natural order (one workgroup per scene: the sort's time grows with P)
+constexpr int SO_DEPTH = 16;
+__global__ __launch_bounds__(1024) void k_sample_order(const unsigned char* __restrict__ keys, int* __restrict__ perm, int P, int nkeys) {
+    __shared__ int hist[256];
+    __shared__ int wbase[16][256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned char* kb = keys + (size_t)blockIdx.x * P;
+    int* pb = perm + (size_t)blockIdx.x * P;
+    for (int i = tid; i < 16 * 256; i += 1024) (&wbase[0][0])[i] = 0;
+    __syncthreads();
+    const int seg = ((P + 16 * 64 - 1) / (16 * 64)) * 64;
+    const int s0 = min(P, wave * seg), s1 = min(P, s0 + seg);
+    for (int i0 = s0; i0 < s1; i0 += 64 * SO_DEPTH) {
+        int kk[SO_DEPTH];
+#pragma unroll
+        for (int u = 0; u < SO_DEPTH; ++u) { const int i = i0 + u * 64 + lane; kk[u] = i < s1 ? (int)kb[i] : -1; }
+#pragma unroll
+        for (int u = 0; u < SO_DEPTH; ++u) if (kk[u] >= 0) atomicAdd(&wbase[wave][kk[u]], 1);
+    }
+    __syncthreads();
+    if (tid < nkeys) {
+        int t = 0;
+        for (int w = 0; w < 16; ++w) t += wbase[w][tid];
+        hist[tid] = t;
+    }
+    __syncthreads();
+    if (tid < nkeys) {
+        int run = 0;
+        for (int k2 = 0; k2 < nkeys; ++k2) if (sorder::key_before(k2, tid)) run += hist[k2];
+        for (int w = 0; w < 16; ++w) { const int c = wbase[w][tid]; wbase[w][tid] = run; run += c; }
+    }
+    __syncthreads();
+    volatile int* base = wbase[wave];
+    for (int i0 = s0; i0 < s1; i0 += 64 * SO_DEPTH) {
+        int kk[SO_DEPTH];
+#pragma unroll
+        for (int u = 0; u < SO_DEPTH; ++u) { const int i = i0 + u * 64 + lane; kk[u] = i < s1 ? (int)kb[i] : -1; }
+#pragma unroll
+        for (int u = 0; u < SO_DEPTH; ++u) {
+            if (i0 + u * 64 >= s1) break;                      // wave-uniform
+            const int k = kk[u];
+            const bool ok = k >= 0;
+            unsigned long long same = __ballot(ok);            // -> the lanes of this step that hold the same key
+#pragma unroll
+            for (int bit = 0; bit < 8; ++bit) {
+                const bool on = (k >> bit) & 1;
+                const unsigned long long bb = __ballot(on);
+                same &= on ? bb : ~bb;
+            }
+            const int rank = __popcll(same & ((1ull << lane) - 1ull));
+            const int pos = ok ? base[k] + rank : 0;
+            __builtin_amdgcn_wave_barrier();
+            if (ok && rank == 0) base[k] = pos + __popcll(same);
+            __builtin_amdgcn_wave_barrier();
+            if (ok) pb[sorder::slot_of(pos, P)] = i0 + u * 64 + lane;
+        }
+    }
+}
 
 #ifndef GNR_DYN_TILES
 #define GNR_DYN_TILES 1         // k_chain takes its tiles from a per-XCD counter (ChainArgs::tile_ctr); 0: static round-robin shares; 2: a wavefront whose XCD's chunk is
@@ -926,7 +1016,11 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             ts_ = ((BX * bx + wi / GY) * gpr + GY * by + wi % GY) * tpg + tin;
         }
     };
-    auto point_of = [&](int b_, int ts_) -> size_t { const int nr = ts_ * 16 + r; return (size_t)b_ * a.P + (nr < a.P ? nr : a.P - 1); };
+    auto point_of = [&](int b_, int ts_) -> size_t {
+        int nr = min(ts_ * 16 + r, a.P - 1);
+        if (RENDER && !SAVE && a.sample_perm) nr = min(max(a.sample_perm[(size_t)b_ * a.P + nr], 0), a.P - 1);
+        return (size_t)b_ * a.P + nr;
+    };
     int tile = dyn ? resolve(grab()) : xcd * chunk + lblk * waves_per_block + wave;
     constexpr bool DPF = GNR_DESC_PREFETCH != 0 && !SAVE;      // the next tile's point descriptors are fetched behind the second view loop
     f4 d0n = {0.f, 0.f, 0.f, 0.f}, d1n = d0n;
@@ -942,7 +1036,10 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
         locate(tile, b, ts);
         const int n_raw = ts * 16 + r;
         const bool row_ok = n_raw < a.P;
-        const int n = row_ok ? n_raw : a.P - 1;
+        int n = row_ok ? n_raw : a.P - 1;                  // (the clamp is on the slot)
+        if constexpr (RENDER && !SAVE) {
+            if (a.sample_perm) n = min(max(a.sample_perm[(size_t)b * a.P + n], 0), a.P - 1);      // slot -> point; a permutation holds 0 .. P-1 (the clamp keeps a bad one inside the scene)
+        }
         const size_t pt = (size_t)b * a.P + n;
         size_t opt = pt;                                   // where the point's user-visible outputs go (caller's ray order)
         if (RENDER && !SAVE && a.ray_perm) {

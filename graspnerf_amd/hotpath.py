@@ -61,7 +61,8 @@ class HotPath:
 
     def set_option(self, name, on=True):
         """Switch one of the per-call options (_lib.OPTIONS: fp32_chain, feature_grad_fixed, view1_one_wavefront, view2_one_wavefront,
-        ray_order_morton, poison_partials, direct_scatter, geo_dual_fp32, test_lose_partner, static_tiles) for the calls of THIS HotPath; -> previous."""
+        ray_order_morton, poison_partials, direct_scatter, geo_dual_fp32, test_lose_partner, static_tiles, split_launch,
+        sample_order_natural) for the calls of THIS HotPath; -> previous."""
         bit = _lib.OPTIONS[name]
         prev = bool(self.options & bit)
         self.options = (self.options | bit) if on else (self.options & ~bit)
@@ -231,7 +232,7 @@ class HotPath:
             o['ray_mask'] = o['ray_mask'].view(torch.bool)       # the kernels write 0 / 1 bytes: a view, not a conversion kernel
         return (co, fi, inds) if debug else (co, fi)
 
-    def render_by_depth(self, ref, que, depth, level='coarse', cfg=None, debug=False, prepared=None):
+    def render_by_depth(self, ref, que, depth, level='coarse', cfg=None, debug=False, prepared=None, _sample_perm=None):
         cfg = cfg or {}
         depth = _f32(depth, self.device)
         B, rn, dn = depth.shape
@@ -239,11 +240,41 @@ class HotPath:
         rays, rkeep = self._rays(que, dn, dn, cfg, scene.H, scene.W)
         o_s, o = self._alloc_out(B, rn, dn, 'imgs' in que, debug, rays.ray_batch_num)
         w = self.wc if level == 'coarse' else self.wf
-        _lib.check(self.L.gnr_render_by_depth_fwd(self._sc(scene), C.byref(rays), depth.data_ptr(), dn, w.data_ptr(),
-                                                  C.byref(o_s), ws.data_ptr(), ws.numel(), self._stream()),
-                   'gnr_render_by_depth_fwd')
+        if _sample_perm is not None:                     # debug_render_by_depth_perm
+            sp = _sample_perm.to(device=self.device, dtype=torch.int32).contiguous()
+            assert sp.shape == (B, rn * dn)
+            _lib.check(self.L.gnr_debug_render_by_depth_perm(self._sc(scene), C.byref(rays), depth.data_ptr(), dn, w.data_ptr(), C.byref(o_s),
+                                                             sp.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                       'gnr_debug_render_by_depth_perm')
+        else:
+            _lib.check(self.L.gnr_render_by_depth_fwd(self._sc(scene), C.byref(rays), depth.data_ptr(), dn, w.data_ptr(),
+                                                      C.byref(o_s), ws.data_ptr(), ws.numel(), self._stream()),
+                       'gnr_render_by_depth_fwd')
         o['ray_mask'] = o['ray_mask'].view(torch.bool)       # the kernels write 0 / 1 bytes: a view, not a conversion kernel
         return o
+
+    def debug_render_by_depth_perm(self, ref, que, depth, sample_perm, level='coarse', cfg=None, debug=False, prepared=None):
+        """Test tooling: render_by_depth with a caller-given order in which the chain kernel visits a scene's samples -- sample_perm
+        [B, rn*dn] int32, every row a permutation (gnr_debug_render_by_depth_perm, include/gnr.h "sample order"); the outputs do not
+        depend on it."""
+        return self.render_by_depth(ref, que, depth, level, cfg, debug, prepared, _sample_perm=sample_perm)
+
+    def sample_order_state(self, rn, dn_max, P, prepared=None):
+        """(keys [B, P] uint8, perm [B, P] int32): device views of what the LAST render pass (P samples per scene) left in a workspace
+        prepared for (rn, dn_max) -- meaningful only if that pass ordered its samples (include/gnr.h "sample order")."""
+        scene, keep, ws = prepared or self._prepared
+        ko, po = C.c_size_t(0), C.c_size_t(0)
+        _lib.check(self.L.gnr_sample_order_offsets(self._sc(scene), rn, dn_max, C.byref(ko), C.byref(po)), 'gnr_sample_order_offsets')
+        B = scene.B
+        return ws[ko.value:ko.value + B * P].view(B, P), ws[po.value:po.value + 4 * B * P].view(torch.int32).view(B, P)
+
+    def debug_sample_order(self, keys):
+        """The device sort alone: keys [B, P] uint8 -> perm [B, P] int32 (gnr_debug_sample_order)."""
+        keys = keys.to(device=self.device, dtype=torch.uint8).contiguous()
+        B, P = keys.shape
+        perm = torch.empty(B, P, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.gnr_debug_sample_order(keys.data_ptr(), B, P, perm.data_ptr(), self._stream()), 'gnr_debug_sample_order')
+        return perm
 
     def merge_depths(self, a, b):
         """sort(cat([a, b], -1), -1) of two per-ray ascending depth lists [..., na], [..., nb] on the device (gnr_merge_depths;

@@ -76,6 +76,8 @@ typedef struct GnrScene {
  *   GNR_OPT_SPLIT_LAUNCH        (experiment) gnr_sample_volume_fwd runs the two halves of the batch as two launch sequences on two streams (the
  *                               caller's and a library-owned one, joined before the call returns its stream), so that each half's
  *                               launches fill the other's tails; bit-identical outputs
+ *   GNR_OPT_SAMPLE_ORDER_NATURAL  the inference render passes keep the natural (ray, sample) order of their points instead of the view-mask order
+ *                               (see "sample order" below; bit-identical outputs: tests, A/B measurements)
  *   GNR_OPT_TEST_LOSE_PARTNER   (tests) the partner wavefronts of k_view1_bwd_pw / k_view2_bwd_pw return at once: the compute wavefronts'
  *                               bounded waits give up, the call's gradients are garbage and bit 4 of gnr_range_status says so */
 #define GNR_OPT_FP32_CHAIN 0x001u
@@ -89,7 +91,8 @@ typedef struct GnrScene {
 #define GNR_OPT_TEST_LOSE_PARTNER 0x100u
 #define GNR_OPT_STATIC_TILES 0x200u
 #define GNR_OPT_SPLIT_LAUNCH 0x400u
-#define GNR_OPT_ALL 0x7ffu
+#define GNR_OPT_SAMPLE_ORDER_NATURAL 0x800u
+#define GNR_OPT_ALL 0xfffu
 
 /* Query rays of B scenes.  Replaces the `que_imgs_info` dict (imgs_info.py:126-135). */
 typedef struct GnrRays {
@@ -233,6 +236,30 @@ int gnr_render_rays_fwd(const GnrScene* scene, const GnrRays* rays, const float*
                         const float* packed_fine, GnrRenderOut* coarse, GnrRenderOut* fine,
                         const float* fine_depth_in, int* fine_inds_out, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* Sample order of the inference render passes (gnr_render_by_depth_fwd, both passes of gnr_render_rays_fwd).  The chain kernel works on
+ * tiles of 16 points and skips a view for a tile when all 16 points project outside it.  Before its chain launch a pass therefore computes
+ * one key byte per sample (bit v = the sample lies inside view v) and a per-scene permutation that groups the samples by key (more views
+ * first; the sorted 16-sample groups dealt round-robin into 8 stripes of the scene's tiles: csrc/gnr_sample_order.h), and slot n of scene b
+ * processes point perm[b][n].  A point's results do not depend on its tile, so every output is bit-identical to the natural order's, and
+ * every array of the ABI keeps the caller's layout.  The workspace holds 5 bytes per ray sample for it (reserved for every sample count,
+ * so that gnr_workspace_bytes grows with rn * dn_max).
+ * A pass keeps the natural order when
+ *   - GNR_OPT_SAMPLE_ORDER_NATURAL is set;
+ *   - a scene has more than 2^18 samples in the pass (one workgroup sorts a scene);
+ *   - the chain launch has fewer than 8 tiles per wavefront slot of the device (B * ceil(rn*dn/16) < 8 * 8 * CUs = 16 384 on MI355X; at
+ *     512 rays x 40 samples: fewer than 13 scenes).  A launch of a tile or two per slot lasts as long as its longest tiles in any order
+ *     (B = 1: no gain at all), and the sort costs 43 us per pass at any B: measured at B = 1, 2, 4, 8, 32 the step loses 0.05 ms at
+ *     B = 4, 0.02 ms at B = 8 and wins 0.10 ms at B = 32, break-even near 7.5 tiles per slot (profiles/sample_order_ab.json).
+ * Test tooling: gnr_debug_render_by_depth_perm = gnr_render_by_depth_fwd with a caller-given sample_perm [B][rn*dn] (int32, device; every
+ * row a permutation of 0 .. rn*dn-1; entries are clamped into the scene); gnr_debug_sample_order = the device sort alone, keys [B][P] ->
+ * perm [B][P] (P <= 2^18); gnr_sample_order_host = the same permutation of one scene computed on the host (no device work);
+ * gnr_sample_order_offsets = byte offsets of the last pass's keys / permutation in a workspace carved for (rn, dn_max). */
+int gnr_debug_render_by_depth_perm(const GnrScene* scene, const GnrRays* rays, const float* depth, int dn, const float* level_weights,
+                                   GnrRenderOut* out, const int* sample_perm, void* workspace, size_t workspace_bytes, void* stream);
+int gnr_debug_sample_order(const unsigned char* keys, int B, int P, int* perm, void* stream);
+int gnr_sample_order_host(const unsigned char* keys_host, int P, int* perm_out_host);
+int gnr_sample_order_offsets(const GnrScene* scene, int rn, int dn_max, size_t* keys_offset, size_t* perm_offset);
 
 /* fine_depth_use_all under training (renderer.py:145-146: the fine pass renders torch.sort(torch.cat([coarse depths, resampled depths])))
  * -- depth_a [nrays,na], depth_b [nrays,nb], each ascending per ray -> out [nrays,na+nb] ascending (na + nb <= 128).  The inference
