@@ -13,6 +13,8 @@ import torch
 
 from .renderer import GraspNeRF
 from .grasp_post import GraspSelector, grasps_from_selection
+from .ingest import axis_tables
+from .planner_session import PlannerSession
 
 
 def load_model(cfg, checkpoint=None, device='cuda:0', depth_coords_rng='device'):
@@ -51,9 +53,19 @@ def core(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8),
 
 
 def plan(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497)),
-         seed=None, selector=None, tsdf_thres_high=0.0, tsdf_thres_low=-0.85, voxel_size=0.3 / 40, return_volumes=False):
+         seed=None, selector=None, tsdf_thres_high=0.0, tsdf_thres_low=-0.85, voxel_size=0.3 / 40, return_volumes=False,
+         session=None):
     """`GraspNeRFPlanner.__call__` from arrays (main.py:185-209): forward, process + select on the device, seeded
-    permutation, voxel -> metric.  -> (grasps dict of numpy arrays: pos, quat, width, score, index; forward seconds)."""
+    permutation, voxel -> metric.  -> (grasps dict of numpy arrays: pos, quat, width, score, index; forward seconds).
+    session: a PlannerSession of this net -- `images` are then the raw uint8 frames [V,h,w,c] and the whole plan is one replay
+    of the session's captured graph (the thresholds and the voxel size are the session's: they must agree with the arguments)."""
+    if session is not None:
+        sp = session.selector_params
+        if session.net is not net or selector is not None or (sp['tsdf_thres_high'], sp['tsdf_thres_low'], session.voxel_size) != \
+                (tsdf_thres_high, tsdf_thres_low, voxel_size):
+            raise ValueError('plan(session=...): the session was built for another net, thresholds or voxel size '
+                             '(its GraspSelector is its own: pass no selector)')
+        return session.plan(images, extrinsics, intrinsics, depth_range, bbox3d, seed=seed, return_volumes=return_volumes)
     dev = next(net.parameters()).device
     V, _, h, w = images.shape
     t = lambda a: torch.as_tensor(np.array(a, np.float32), device=dev)
@@ -95,20 +107,8 @@ def resize_bilinear_u8(img, wh):
     if (dw, dh) == (sw, sh):
         return img.copy()
 
-    def axis(dn, sn):
-        f = (np.arange(dn, dtype=np.float64) + 0.5) * (sn / dn) - 0.5
-        i0 = np.floor(f).astype(np.int64)
-        w = (f - i0).astype(np.float32)
-        lo = i0 < 0
-        i0[lo], w[lo] = 0, 0.0
-        hi = i0 >= sn - 1
-        i0[hi], w[hi] = sn - 1, 0.0
-        i1 = np.minimum(i0 + 1, sn - 1)
-        c1 = np.clip(np.rint(w.astype(np.float64) * 2048), -32768, 32767).astype(np.int64)      # saturate_cast<short>(w * 2^11)
-        c0 = np.clip(np.rint((1.0 - w.astype(np.float64)) * 2048), -32768, 32767).astype(np.int64)
-        return i0, i1, c0, c1
-    x0, x1, a0, a1 = axis(dw, sw)
-    y0, y1, b0, b1 = axis(dh, sh)
+    x0, x1, a0, a1 = axis_tables(dw, sw)
+    y0, y1, b0, b1 = axis_tables(dh, sh)
     src = img.astype(np.int64)
     rows = src[:, x0] * a0[None, :, None] + src[:, x1] * a1[None, :, None]                       # horizontal pass: int, scale 2^11
     s0, s1 = rows[y0], rows[y1]
@@ -165,9 +165,12 @@ class GraspNeRFPlanner:
     cfg: the reference's yaml as a dict;  checkpoint: `model_best.pth` path or state dict ({'network_state_dict': ...});
     renderer_root_dir: holds camera_pose.npy (main.py:174);  rgb_dir: the directory of the rendered `%04d.png` images
     (main.py:168);  database_name: as in the reference's args, e.g. 'vgn_syn/test/packed/packed_170-220/032cd891d9be4a16be5ea4be9f7eca2b/w_0.8'
-    (the trailing `<background>_<size>` sets the down-sampling, main.py:96-103)."""
+    (the trailing `<background>_<size>` sets the down-sampling, main.py:96-103);  graphed: plan through a PlannerSession --
+    the decoded PNGs go to the device as uint8 and the resize, the forward and the selection replay as one captured graph
+    (built at the first call from its frame size and view count, rebuilt when either changes)."""
 
-    def __init__(self, cfg, checkpoint, renderer_root_dir, rgb_dir, database_name='vgn_syn/test/x/x/x/w_0.8', seed=0, device='cuda:0'):
+    def __init__(self, cfg, checkpoint, renderer_root_dir, rgb_dir, database_name='vgn_syn/test/x/x/x/w_0.8', seed=0, device='cuda:0',
+                 graphed=False):
         tp, _split, _stype, _ssplit, _sid, background_size = database_name.split('/')                 # main.py:96
         self.tp, self.down_sample = tp, float(background_size.split('_')[1])
         self.img_wh = (np.array(SRC_WH[tp]) * self.down_sample).astype(int)                            # main.py:103
@@ -183,9 +186,12 @@ class GraspNeRFPlanner:
         self.net = load_model(cfg, ckpt, device)                                                       # main.py:150-157
         self.step = int(ckpt.get('step', 0)) if isinstance(ckpt, dict) else 0                          # main.py:155
         self.selector = GraspSelector(next(self.net.parameters()).device)
+        self.graphed, self.session = bool(graphed), None
 
     def get_image(self, img_id, round_idx=0):                                                          # main.py:167-172
         img = read_rgb_png(os.path.join(self.rgb_dir, '%04d.png' % img_id))
+        if getattr(self, 'graphed', False):
+            return img                                                                                 # the session resizes on the device
         return resize_bilinear_u8(img, self.img_wh).astype(np.float32)
 
     def get_pose(self, img_id):                                                                        # main.py:174-177
@@ -201,14 +207,24 @@ class GraspNeRFPlanner:
             raise NotImplementedError('depth-map based ranges need the simulator\'s depth renderings (main.py:185-187)')
         return np.array([0.2, 0.8])
 
+    def _session_for(self, frames):
+        key = (len(frames), frames[0].shape[:2])
+        if self.session is None or (self.session.n_views, self.session.src_hw) != key:
+            self.session = PlannerSession(self.net, key[0], key[1], self.img_wh, max_grasps=self.selector.max_grasps,
+                                          voxel_size=self.voxel_size, tsdf_thres_high=self.tsdf_thres_high,
+                                          tsdf_thres_low=self.tsdf_thres_low)
+        return self.session
+
     def __call__(self, test_view_id, round_idx=0, n_grasp=0, gt_tsdf=None):                            # main.py:189-209
-        images = np.stack([self.get_image(i, round_idx) for i in test_view_id], 0)
-        images = (images.astype(np.float32) / 255).transpose([0, 3, 1, 2])                             # color_map_forward
+        images = [self.get_image(i, round_idx) for i in test_view_id]
+        session = self._session_for(images) if self.graphed else None
+        if session is None:
+            images = (np.stack(images, 0).astype(np.float32) / 255).transpose([0, 3, 1, 2])            # color_map_forward
         extrinsics = np.stack([self.get_pose(i) for i in test_view_id], 0)
         intrinsics = np.stack([self.get_K(i) for i in test_view_id], 0)
         depth_range = np.asarray([self.get_depth_range(i, round_idx, fixed=True) for i in test_view_id], dtype=np.float32)
         g, toc = plan(self.net, images, extrinsics, intrinsics, depth_range, self.bbox3d, seed=self.seed + round_idx + n_grasp,
-                      selector=self.selector, tsdf_thres_high=self.tsdf_thres_high, tsdf_thres_low=self.tsdf_thres_low,
-                      voxel_size=self.voxel_size)
+                      selector=None if session else self.selector, tsdf_thres_high=self.tsdf_thres_high,
+                      tsdf_thres_low=self.tsdf_thres_low, voxel_size=self.voxel_size, session=session)
         grasps = [Grasp(q, t, w) for q, t, w in zip(g['quat'], g['pos'], g['width'])]
         return grasps, g['score'], toc

@@ -1,0 +1,193 @@
+"""The planner's operating point -- one scene per call (ref: src/nr/main.py:188-209) -- as ONE captured hipGraph from raw
+uint8 frames to the selected grasps: device ingest (csrc/gnr_ingest.hip) -> image_encoder / init_net / vis_encoder ->
+gnr_prepare -> sample_volume -> HIP grasp head -> process + select (csrc/gnr_post.hip).  The graph holds what the planner
+consumes and nothing else: no depth-mean head (renderer.py:732 runs it on every eval forward, the planner drops it), no
+render pass, no valid-ratio read-back.  A plan is two pinned host->device copies, one graph replay and one read-back.
+
+Limits: one scene per plan, a fixed view count, frame size and selector parameters per session (forward_scenes is the batched
+route); the model's parameters may change between plans (the graph is captured again when they did)."""
+import inspect
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from .grasp_post import GraspSelector, grasps_from_selection
+from .ingest import DeviceIngest
+
+_SELECTOR_DEFAULTS = {k: p.default for k, p in inspect.signature(GraspSelector.__call__).parameters.items()
+                      if p.default is not inspect.Parameter.empty}
+_SEG = 64                                                    # floats: every camera block starts on a 256-byte boundary
+
+
+class PlannerSession:
+    """PlannerSession(net, n_views, src_hw, img_wh, max_grasps=2048, **selector_params)
+
+    net: GraspNeRF on a ROCm GPU (planner.load_model);  src_hw = (h, w) of the uint8 frames;  img_wh = (W, H) of the network
+    input (multiples of 32, main.py:226);  selector_params: keyword arguments of GraspSelector.__call__ (the reference planner
+    passes tsdf_thres_high=0.0, tsdf_thres_low=-0.85, main.py:93-94,199);  channels: 3, or 4 for RGBA frames (alpha ignored);
+    deterministic: the convolutions of the 2D backbones are recorded with MIOpen's deterministic solvers, so the same frames and
+    cameras give the same bits on every replay (its default solvers for some of the strided layers sum in arrival order: an
+    eager forward differs from itself by ~1e-5); False records whatever MIOpen picks."""
+
+    def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
+                 **selector_params):
+        cfg = net.nr_net.cfg
+        if cfg.get('warn_low_valid_ratio', False):
+            raise ValueError("graph capture cannot read the valid ratio back on every call: unset cfg['warn_low_valid_ratio']")
+        if not cfg.get('sample_volume', False):
+            raise ValueError("the planner needs cfg['sample_volume'] = True")
+        unknown = sorted(set(selector_params) - set(_SELECTOR_DEFAULTS))
+        if unknown:
+            raise TypeError(f'unknown selector parameters {unknown}; GraspSelector takes {sorted(_SELECTOR_DEFAULTS)}')
+        dev = next(net.parameters()).device
+        if dev.type != 'cuda':
+            raise _lib.GnrError('PlannerSession needs the model on a ROCm GPU; there is no CPU fallback')
+        W, H = int(img_wh[0]), int(img_wh[1])
+        if H % 32 or W % 32 or channels not in (3, 4):
+            raise ValueError('img_wh must be multiples of 32 (main.py:226) and channels 3 or 4')
+        self.net, self.device = net, dev
+        self.n_views, self.src_hw, self.img_wh, self.channels = int(n_views), (int(src_hw[0]), int(src_hw[1])), (W, H), int(channels)
+        self.max_grasps, self.voxel_size, self.warmup = int(max_grasps), float(voxel_size), int(warmup)
+        self.deterministic = bool(deterministic)
+        self.selector_params = {**_SELECTOR_DEFAULTS, **selector_params}
+        self.ingest = DeviceIngest(dev)
+        self.selector = GraspSelector(dev, max_grasps=self.max_grasps)
+        V, M = self.n_views, self.max_grasps
+        # static inputs of the graph and their pinned staging twins: the frames, and one float block for the cameras
+        self._d_frames = torch.zeros(V, *self.src_hw, self.channels, dtype=torch.uint8, device=dev)
+        self._h_frames = torch.zeros(V, *self.src_hw, self.channels, dtype=torch.uint8, pin_memory=True)
+        sizes = (('poses', (V, 3, 4)), ('Ks', (V, 3, 3)), ('depth_range', (V, 2)), ('bbox3d', (2, 3)))
+        offs, n = {}, 0
+        for k, shp in sizes:
+            offs[k] = (n, shp)
+            n += -(-int(np.prod(shp)) // _SEG) * _SEG
+        self._h_cam = torch.zeros(n, dtype=torch.float32, pin_memory=True)
+        self._d_cam = torch.zeros(n, dtype=torch.float32, device=dev)
+        view = lambda buf: {k: buf[o:o + int(np.prod(shp))].view(shp) for k, (o, shp) in offs.items()}
+        self._h = {k: v.numpy() for k, v in view(self._h_cam).items()}
+        self._h_frames_np = self._h_frames.numpy()
+        self._d = view(self._d_cam)
+        self.images = torch.zeros(V, 3, H, W, dtype=torch.float32, device=dev)       # the ingested frames of the last plan
+        # the selection, packed for one read-back: count | index [M,3] | score [M] | quat [M,4] | width [M], 4-byte words
+        self._d_out = torch.zeros(1 + 9 * M, dtype=torch.int32, device=dev)
+        self._h_out = torch.zeros(1 + 9 * M, dtype=torch.int32, pin_memory=True)
+        self.selection = None
+        self.captures = 0
+        self._set_example_cameras()
+        self._capture()
+
+    # ---- capture -----------------------------------------------------------------------------------------------
+    def _set_example_cameras(self):
+        """Well-formed cameras for the warm-up runs (a zero intrinsic matrix would divide by zero in the projections)."""
+        from .synth import ring_cameras
+        W, H = self.img_wh
+        self._h['poses'][:] = ring_cameras(self.n_views).astype(np.float32)[:, :3, :]
+        self._h['Ks'][:] = np.float32([[0.7 * W, 0, 0.5 * W], [0, 0.7 * W, 0.5 * H], [0, 0, 1]])
+        self._h['depth_range'][:] = np.float32([0.2, 0.8])
+        self._h['bbox3d'][:] = np.float32([[-0.15, -0.15, -0.0503], [0.15, 0.15, 0.2497]])
+        self._d_cam.copy_(self._h_cam)
+
+    def _forward(self):
+        nr = self.net.nr_net
+        imgs = self.ingest(self._d_frames, self.img_wh, out=self.images)
+        ref = {'imgs': imgs, **self._d}
+        ref['img_feats'] = nr.image_encoder(imgs)
+        ref['ray_feats'] = nr.vis_encoder(nr.init_net(ref, None, False), ref['img_feats'])
+        prep = nr._prepare(ref, 0)
+        vol = nr.sample_volume(ref, _prep=prep)
+        q, r, w = self.net.grasp_head(vol)
+        sel = self.selector(vol, q, r, w, **self.selector_params)
+        M, o = self.max_grasps, self._d_out
+        o[0:1].copy_(sel['count'])
+        o[1:1 + 3 * M].copy_(sel['index'].reshape(-1))
+        for k, a, b in (('score', 1 + 3 * M, 1 + 4 * M), ('quat', 1 + 4 * M, 1 + 8 * M), ('width', 1 + 8 * M, 1 + 9 * M)):
+            o[a:b].copy_(sel[k].reshape(-1).view(torch.int32))
+        return {'volume': vol, 'qual': q, 'rot': r, 'width': w, 'sel_qual': sel['qual']}
+
+    def _state(self):
+        """What the captured graph depends on besides its static inputs: the parameter versions and addresses (the packed
+        copies of the hot path and of the grasp head are re-uploaded when they move -- outside a capture) and the addresses
+        of the workspaces those two keep (another caller's larger shape re-allocates them)."""
+        nr, head = self.net.nr_net, self.net._head
+        hot = nr._hot
+        ptr = lambda t: None if t is None else t.data_ptr()
+        return (tuple((p._version, p.data_ptr()) for p in self._params), hot, head,
+                None if hot is None else (ptr(hot._ws), ptr(hot.wc), hot.options), None if head is None else (ptr(head._ws), ptr(head.w)))
+
+    def _capture(self):
+        self._params = list(self.net.parameters())
+        self.graph = self._out = None                        # the previous capture's pool goes back first
+        was = torch.backends.cudnn.deterministic             # read when a convolution picks its solver: warm-up and capture
+        torch.backends.cudnn.deterministic = was or self.deterministic
+        try:
+            s = torch.cuda.Stream(self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(s), torch.no_grad():
+                for _ in range(max(self.warmup, 1)):         # builds HotPath / GraspHead / the workspaces, re-packs moved weights
+                    self._forward()
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with torch.no_grad(), torch.cuda.graph(g):
+                out = self._forward()
+        finally:
+            torch.backends.cudnn.deterministic = was
+        self.graph, self._out, self._captured = g, out, self._state()
+        self.captures += 1
+
+    # ---- one plan ----------------------------------------------------------------------------------------------
+    def _stage_frames(self, frames):
+        if torch.is_tensor(frames) and frames.is_cuda:       # frames that are on the device already: no staging
+            if frames.dtype != torch.uint8 or tuple(frames.shape) != tuple(self._d_frames.shape):
+                raise ValueError(f'frames must be uint8 {tuple(self._d_frames.shape)}, got {frames.dtype} {tuple(frames.shape)}')
+            self._d_frames.copy_(frames, non_blocking=True)
+            return
+        if isinstance(frames, (list, tuple)):
+            if len(frames) != self.n_views:
+                raise ValueError(f'this session takes {self.n_views} frames, got {len(frames)}')
+            frames = [np.asarray(f) for f in frames]
+        else:
+            frames = np.asarray(frames)
+            frames = frames[None] if frames.ndim == 3 else frames
+        want = self._h_frames_np.shape
+        for f in frames:
+            if f.dtype != np.uint8 or f.shape != want[1:]:
+                raise ValueError(f'this session takes {want[0]} uint8 frames {want[1:]}, got {f.dtype} {f.shape}')
+        if len(frames) != want[0]:
+            raise ValueError(f'this session takes {want[0]} frames, got {len(frames)}')
+        for dst, f in zip(self._h_frames_np, frames):
+            np.copyto(dst, f)
+        self._d_frames.copy_(self._h_frames, non_blocking=True)
+
+    def plan(self, frames_u8, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497)),
+             seed=None, return_volumes=False):
+        """planner.plan() from raw frames: frames_u8 [V,h,w,c] uint8 (array, list of arrays, or a device tensor);
+        extrinsics [V,3|4,4] world->camera; intrinsics [V,3,3] of the RESIZED images; depth_range [2] or [V,2].
+        -> (grasps dict: pos, quat, width, score, index (+ volumes); seconds from before the first copy to after the read-back)."""
+        if self._state() != self._captured:
+            self._capture()
+        V = self.n_views
+        ext, K = np.asarray(extrinsics, np.float32), np.asarray(intrinsics, np.float32)
+        if ext.shape[0] != V or K.shape != (V, 3, 3):
+            raise ValueError(f'this session takes {V} views, got extrinsics {ext.shape} and intrinsics {K.shape}')
+        st = torch.cuda.current_stream(self.device)
+        t0 = time.time()
+        self._stage_frames(frames_u8)
+        self._h['poses'][:] = ext[:, :3, :]
+        self._h['Ks'][:] = K
+        self._h['depth_range'][:] = np.asarray(depth_range, np.float32)      # [2] broadcasts over the views
+        self._h['bbox3d'][:] = np.asarray(bbox3d, np.float32)
+        self._d_cam.copy_(self._h_cam, non_blocking=True)
+        self.graph.replay()
+        self._h_out.copy_(self._d_out, non_blocking=True)
+        st.synchronize()
+        dt = time.time() - t0
+        M, h = self.max_grasps, self._h_out.clone()          # the staging buffer is rewritten by the next plan
+        f = lambda a, b, *shp: h[a:b].view(torch.float32).view(1, M, *shp)
+        self.selection = {'count': h[0:1], 'index': h[1:1 + 3 * M].view(1, M, 3), 'score': f(1 + 3 * M, 1 + 4 * M),
+                          'quat': f(1 + 4 * M, 1 + 8 * M, 4), 'width': f(1 + 8 * M, 1 + 9 * M)}
+        grasps = grasps_from_selection(self.selection, 0, self.voxel_size, seed)
+        if return_volumes:
+            grasps['volumes'] = tuple(self._out[k].cpu().numpy() for k in ('volume', 'qual', 'rot', 'width', 'sel_qual'))
+        return grasps, dt

@@ -352,6 +352,25 @@ int gnr_reflect_pad2d(const float* x, float* y, long long planes, int H, int W, 
 int gnr_reflect_pad2d_bwd(const float* dy, float* dx, long long planes, int H, int W, int pad, void* stream);
 int gnr_upsample2x_bilinear(const float* x, float* y, long long planes, int H, int W, void* stream);
 
+/* ---- image ingest on the device (csrc/gnr_ingest.hip) -----------------------------------------------------------
+ * The planner's image preparation (src/nr/main.py:167-172, 191-192: skimage imread(...)[:, :, :3] -> cv2.resize(img, wh),
+ * INTER_LINEAR -> / 255 -> HWC to CHW) for n uint8 frames in ONE launch: out = float [n,3,dst_h,dst_w] in [0,1], bit-identical
+ * to planner.resize_bilinear_u8(img, wh).astype(float32) / 255 transposed (OpenCV's fixed point: 11-bit coefficients,
+ * (.. + 2) >> 2 in the vertical pass; the kernel is integer arithmetic plus a 256-entry table of float(i) / 255).
+ * gnr_ingest_tables_host (host only, no device work) fills an opaque blob of gnr_ingest_tables_bytes(dst_h, dst_w) bytes with
+ * the per-axis source indices and coefficients (float64 positions, no fused multiply-add) and that table; the caller uploads it
+ * once per (src, dst) size and passes the device copy as tables_dev.
+ * frames: DEVICE uint8, `channels` = 3 or 4 interleaved (a 4th channel is ignored), row y of frame f at
+ * frames + f * frame_pitch + y * row_pitch (pitches in bytes).  Stream-ordered, no allocation, no host synchronisation.
+ * GNR_ERR_ARG: null pointer, channels not 3 / 4, a pitch shorter than the row / frame it strides;  GNR_ERR_SHAPE: n < 1, a
+ * dimension outside 1..16384, more than 2^31 - 1 groups of four output pixels;  text in gnr_ingest_last_error(). */
+#define GNR_INGEST_MAX_DIM 16384
+size_t gnr_ingest_tables_bytes(int dst_h, int dst_w);
+int gnr_ingest_tables_host(int src_h, int src_w, int dst_h, int dst_w, void* tables_host);
+int gnr_ingest_u8(const unsigned char* frames, int n, int src_h, int src_w, int channels, size_t row_pitch, size_t frame_pitch,
+                  const void* tables_dev, float* out, int dst_h, int dst_w, void* stream);
+const char* gnr_ingest_last_error(void);
+
 /* ---- backward twins ------------------------------------------------------------------------
  * Parameter gradients are DETERMINISTIC: the kernels use no float atomics on them.  Points / rays are assigned to
  * wavefronts statically, every wavefront stores its partial sums into its own slot of a partial buffer inside the
