@@ -3,6 +3,7 @@
 #include <string.h>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/gnr.h"
 
@@ -21,7 +22,7 @@ static int fail(int code, const char* what, hipError_t e = hipSuccess) {
 
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: one bit per device id and kernel
+// hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: one bit per device id and kernel (launch())
 static bool attr_needed(std::atomic<unsigned long long>& done) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return true;
@@ -109,11 +110,10 @@ static int num_cus() {
 // depth-mean / geometry-GEMM kernels up to two workgroups per CU.
 static size_t chain_part_floats() { return (size_t)4 * num_cus() * GP_STRIDE; }
 static size_t tail_part_floats(int waves_per_block) { return (size_t)2 * num_cus() * waves_per_block * tp::STRIDE; }
-
+// grid of the backward's chain stages: four tiles (wavefronts) per workgroup, at most one workgroup per CU
+static int chain_blocks(int ntiles) { return (ntiles + 3) / 4 < num_cus() ? (ntiles + 3) / 4 : num_cus(); }
 
 struct GradRange { int lo, hi, dlo; };
-static int launch_grad_reduce(const float* part, int nslots, int stride, float* dst, const GradRange* rg, int nranges,
-                              hipStream_t st, const char* label);
 
 // ---- optional in-situ timing of the library's kernels (bench.py: roofline.achieved, train-step split) -------------
 // Between gnr_timing_begin() and gnr_timing_end() every kernel launch of this library is bracketed by a pair of HIP
@@ -129,8 +129,8 @@ struct KTiming {
 static KTiming g_kt;
 struct KScope {
     hipStream_t st; int idx = -1;
-    KScope(const char* label, hipStream_t s) : st(s) {
-        if (!g_kt.on.load() || (g_kt.only[0] && !strstr(label, g_kt.only))) return;
+    KScope(const char* label, hipStream_t s) : st(s) {            // label == nullptr: a launch that is never bracketed
+        if (!label || !g_kt.on.load() || (g_kt.only[0] && !strstr(label, g_kt.only))) return;
         hipEvent_t e0, e1;
         if (hipEventCreate(&e0) != hipSuccess) return;
         if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return; }
@@ -143,6 +143,36 @@ struct KScope {
     ~KScope() { if (idx >= 0) hipEventRecord(g_kt.rec[idx].e1, st); }
 };
 
+// Every kernel launch of this file: the timing bracket around the launch alone, then the launch's own error check.  A kernel that takes
+// more dynamic LDS than a launch gets by default names its maximum as MAX_LDS -- the most any launch of it asks for, not this launch's
+// bytes -- and has hipFuncAttributeMaxDynamicSharedMemorySize raised to it on the first launch per device (one static per kernel).
+// A kernel passed as a template argument has lost its default arguments: the call sites spell them out.
+template <auto Kernel, size_t MAX_LDS = 0, typename... Args>
+static int launch(const char* label, hipStream_t st, dim3 grid, dim3 block, size_t lds_bytes, Args... args) {
+    if constexpr (MAX_LDS != 0) {
+        static std::atomic<unsigned long long> attr_done{0};
+        if (attr_needed(attr_done)) GNR_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MAX_LDS));
+    }
+    { KScope ks(label, st); hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...); }
+    GNR_HIP(hipGetLastError());
+    return GNR_OK;
+}
+
+// The kernels with a view loop are templates on the view count: f(std::integral_constant<int, V>) for the scene's V (check_scene: 2..8)
+template <typename F>
+static int with_views(int V, F&& f) {
+    switch (V) {
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 5: return f(std::integral_constant<int, 5>());
+        case 6: return f(std::integral_constant<int, 6>());
+        case 7: return f(std::integral_constant<int, 7>());
+        case 8: return f(std::integral_constant<int, 8>());
+        default: return fail(GNR_ERR_SHAPE, "unsupported view count");
+    }
+}
+
 static int launch_grad_reduce(const float* part, int nslots, int stride, float* dst, const GradRange* rg, int nranges,
                               hipStream_t st, const char* label) {
     GradReduceArgs a;
@@ -151,9 +181,7 @@ static int launch_grad_reduce(const float* part, int nslots, int stride, float* 
     int total = 0;
     for (int k = 0; k < nranges; ++k) { a.lo[k] = rg[k].lo; a.hi[k] = rg[k].hi; a.dlo[k] = rg[k].dlo; total += rg[k].hi - rg[k].lo; }
     if (total <= 0 || nslots <= 0) return GNR_OK;
-    { KScope ks(label, st); hipLaunchKernelGGL(k_grad_reduce, dim3((total + 63) / 64), dim3(256), 0, st, a); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    return launch<k_grad_reduce>(label, st, dim3((total + 63) / 64), dim3(256), 0, a);
 }
 
 // partials of a per-ray tail kernel (layout tp::) -> dtail (layout tl::, overwritten)
@@ -161,9 +189,7 @@ static int launch_tail_reduce(const float* part, int nslots, const float* wpk, f
     GNR_HIP(hipMemsetAsync(dtail, 0, tl::TOTAL * sizeof(float), st));
     const GradRange rg[1] = {{tp::W, tp::W + 1024, tl::WQ}};
     if (int rc = launch_grad_reduce(part, nslots, tp::STRIDE, dtail, rg, 1, st, "k_grad_reduce@tail")) return rc;
-    { KScope ks("k_tail_finish", st); hipLaunchKernelGGL(k_tail_finish, dim3(16), dim3(256), 0, st, part, nslots, wpk, dtail); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    return launch<k_tail_finish>("k_tail_finish", st, dim3(16), dim3(256), 0, part, nslots, wpk, dtail);
 }
 
 // GNR_OPT_POISON_PARTIALS: fill a partial buffer with NaN bit patterns before its kernels run, so that a slot entry the kernels fail
@@ -176,23 +202,14 @@ static int poison_partials(void* p, size_t bytes, hipStream_t st, unsigned optio
 
 template <int V, bool RENDER, bool SAVE, bool USEVIS, bool SP>
 static int launch_chain_one(const ChainArgs& a, hipStream_t st, const char* label) {
-    const size_t lds_bytes = (size_t)((SP ? pk::C16_END : pk::CHAIN_END) + COOP_TAB_FLOATS) * sizeof(float);
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) {
-        GNR_HIP(hipFuncSetAttribute((const void*)k_chain<V, RENDER, SAVE, USEVIS, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    }
+    constexpr size_t lds_bytes = (size_t)((SP ? pk::C16_END : pk::CHAIN_END) + COOP_TAB_FLOATS) * sizeof(float);
     const int tps = (a.P + 15) / 16;
     const long ntiles = (long)a.B * tps;
     constexpr int WPB = GNR_CHAIN_THREADS / 64;
     long blocks = (ntiles + WPB - 1) / WPB;
     const long maxb = num_cus();
     if (blocks > maxb) blocks = maxb;
-    {
-        KScope ks(label, st);
-        hipLaunchKernelGGL((k_chain<V, RENDER, SAVE, USEVIS, SP>), dim3((unsigned)blocks), dim3(GNR_CHAIN_THREADS), lds_bytes, st, a);
-    }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    return launch<k_chain<V, RENDER, SAVE, USEVIS, SP>, lds_bytes>(label, st, dim3((unsigned)blocks), dim3(GNR_CHAIN_THREADS), lds_bytes, a);
 }
 
 // One chain launch of the product = the pair kernel + its fp32-MFMA twin on the same arguments with only_if_flagged set: the
@@ -217,26 +234,22 @@ static int launch_chain_t(const ChainArgs& a, hipStream_t st, bool force_fp32) {
     }
 }
 
-template <bool RENDER, bool SAVE, bool USEVIS>
-static int launch_chain_v(int V, const ChainArgs& a, hipStream_t st, bool f32) {
-    switch (V) {
-        case 2: return launch_chain_t<2, RENDER, SAVE, USEVIS>(a, st, f32);
-        case 3: return launch_chain_t<3, RENDER, SAVE, USEVIS>(a, st, f32);
-        case 4: return launch_chain_t<4, RENDER, SAVE, USEVIS>(a, st, f32);
-        case 5: return launch_chain_t<5, RENDER, SAVE, USEVIS>(a, st, f32);
-        case 6: return launch_chain_t<6, RENDER, SAVE, USEVIS>(a, st, f32);
-        case 7: return launch_chain_t<7, RENDER, SAVE, USEVIS>(a, st, f32);
-        case 8: return launch_chain_t<8, RENDER, SAVE, USEVIS>(a, st, f32);
-        default: return fail(GNR_ERR_SHAPE, "unsupported view count");
-    }
-}
-
 // use_vis (GnrScene.use_vis: the levels' decoders carry the fourth branch, gnr_pack_vis_decoder / gnr_pack_vis_decoder_bwd)
 template <bool RENDER, bool SAVE = false>
 static int launch_chain(const GnrScene* s, const ChainArgs& a, hipStream_t st) {
     if (s->use_vis != 0 && s->use_vis != 1) return fail(GNR_ERR_ARG, "GnrScene.use_vis must be 0 or 1");
     const bool f32 = opt(s, GNR_OPT_FP32_CHAIN);
-    return s->use_vis ? launch_chain_v<RENDER, SAVE, true>(s->V, a, st, f32) : launch_chain_v<RENDER, SAVE, false>(s->V, a, st, f32);
+    return with_views(s->V, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        return s->use_vis ? launch_chain_t<V, RENDER, SAVE, true>(a, st, f32) : launch_chain_t<V, RENDER, SAVE, false>(a, st, f32);
+    });
+}
+// The range guard and the tile hand-out of a chain launch: the scene's status words, the watch word of this launch (slot) and, unless
+// GNR_OPT_STATIC_TILES, the tile counters behind them (part: the half of a GNR_OPT_SPLIT_LAUNCH call, each with counters of its own)
+static void wire_chain(ChainArgs& a, const GnrScene* s, const Workspace& w, int slot, int part = 0) {
+    a.range_flag = w.range_flag;
+    a.range_launch = w.range_flag ? w.range_flag + slot : nullptr;
+    a.tile_ctr = (w.range_flag && !opt(s, GNR_OPT_STATIC_TILES)) ? w.range_flag + RS_WORDS + 16 * part : nullptr;
 }
 
 // The backward's view kernels (csrc/gnr_bwd.inc).  Default: the partner-wavefront kernels (gnr_bwd_view{1,2}_pw.inc: same outputs, same
@@ -247,11 +260,34 @@ static int launch_chain(const GnrScene* s, const ChainArgs& a, hipStream_t st) {
 #endif
 static bool view1_partner(const GnrScene* s) { return GNR_VIEW1_PARTNER != 0 && GNR_BWD_PAIRS != 0 && !opt(s, GNR_OPT_VIEW1_ONE_WAVEFRONT) && !opt(s, GNR_OPT_FP32_CHAIN) && !s->use_vis; }
 static bool view2_partner(const GnrScene* s) { return GNR_VIEW1_PARTNER != 0 && GNR_BWD_PAIRS != 0 && !opt(s, GNR_OPT_VIEW2_ONE_WAVEFRONT) && !opt(s, GNR_OPT_FP32_CHAIN); }
-// range guard of a backward pass (BwdGuard, gnr_bwd.inc): volume = the volume's training forward (RS_VOLUME_TRAIN), else the render
-// passes' training forwards (RS_COARSE_TRAIN and RS_DEPTHS_TRAIN together: the backward is not told which of them it follows)
-static BwdGuard bwd_guard(const GnrScene* s, const Workspace& w, bool volume, int run_if) {
+// What tells the two chain backwards (gnr_sample_volume_bwd, gnr_render_chain_bwd) apart in the stages they share (chain_bwd):
+//   slot, slot2: the watch words of the training forwards the backward follows -- the volume's, or the render passes' RS_COARSE_TRAIN and
+//                RS_DEPTHS_TRAIN together (the backward is not told which of them it follows); slot2 < 0: none
+//   rg:          the ranges of the canonical blob its stages store (launch_grad_reduce; the third one with use_vis only)
+struct BwdEntry {
+    bool volume;
+    int slot, slot2;
+    GradRange rg[3];
+    const char *view2, *view2_twin, *view1, *view1_twin, *scatter_place, *scatter_scan, *scatter_fill, *scatter_gather, *unpack, *reduce;   // timing labels
+};
+// decoder .. geometry_fc [0, WQ), neuray_fc [NR0_W, VARIANCE) (+ the vis branch behind the blob)
+static const BwdEntry BWD_VOLUME = {
+    true, RS_VOLUME_TRAIN, -1, {{0, can::WQ, 0}, {can::NR0_W, can::VARIANCE, can::NR0_W}, {can::TOTAL, can::TOTAL_VIS, can::TOTAL}},
+    "k_view2_bwd@gnr_sample_volume_bwd", "k_view2_bwd.fp32_twin@gnr_sample_volume_bwd",
+    "k_view1_bwd@gnr_sample_volume_bwd", "k_view1_bwd.fp32_twin@gnr_sample_volume_bwd",
+    "k_scatter_place@gnr_sample_volume_bwd", "k_scatter_scan@gnr_sample_volume_bwd", "k_scatter_fill@gnr_sample_volume_bwd",
+    "k_scatter_gather@gnr_sample_volume_bwd", "k_unpack_feat_grad@gnr_sample_volume_bwd", "k_grad_reduce@gnr_sample_volume_bwd"};
+// decoder .. vis_fc2 [0, GEO0_W), rgb_fc + neuray_fc [RGB0_W, VARIANCE) (+ the vis branch behind the blob)
+static const BwdEntry BWD_RENDER = {
+    false, RS_COARSE_TRAIN, RS_DEPTHS_TRAIN, {{0, can::GEO0_W, 0}, {can::RGB0_W, can::VARIANCE, can::RGB0_W}, {can::TOTAL, can::TOTAL_VIS, can::TOTAL}},
+    "k_view2_bwd@gnr_render_chain_bwd", "k_view2_bwd.fp32_twin@gnr_render_chain_bwd",
+    "k_view1_bwd@gnr_render_chain_bwd", "k_view1_bwd.fp32_twin@gnr_render_chain_bwd",
+    "k_scatter_place@gnr_render_chain_bwd", "k_scatter_scan@gnr_render_chain_bwd", "k_scatter_fill@gnr_render_chain_bwd",
+    "k_scatter_gather@gnr_render_chain_bwd", "k_unpack_feat_grad@gnr_render_chain_bwd", "k_grad_reduce@gnr_render_chain_bwd"};
+// range guard of a backward pass (BwdGuard, gnr_bwd.inc)
+static BwdGuard bwd_guard(const GnrScene* s, const Workspace& w, const BwdEntry& e, int run_if) {
     unsigned* f = w.range_flag;
-    return BwdGuard{f, f ? f + (volume ? RS_VOLUME_TRAIN : RS_COARSE_TRAIN) : nullptr, (f && !volume) ? f + RS_DEPTHS_TRAIN : nullptr, f ? run_if : 0,
+    return BwdGuard{f, f ? f + e.slot : nullptr, (f && e.slot2 >= 0) ? f + e.slot2 : nullptr, f ? run_if : 0,
                     f ? f + RS_BACKWARD : nullptr, opt(s, GNR_OPT_TEST_LOSE_PARTNER) ? 1 : 0};
 }
 // The channel-last feature-gradient buffer of an entry point: nfeat entries of 8 bytes (the fixed-point mode's; the float mode uses
@@ -272,20 +308,17 @@ static int feat_grad_begin(const GnrScene* s, void* region, const Workspace& w, 
         int blocks = (int)((n_upstream + 256 * 16 - 1) / (256 * 16));
         if (blocks > 4 * num_cus()) blocks = 4 * num_cus();
         if (blocks < 1) blocks = 1;
-        KScope ks("k_absmax_bits", st);
         const BwdGuard* g = only_if_flagged;
-        hipLaunchKernelGGL(k_absmax_bits, dim3(blocks), dim3(256), 0, st, upstream, n_upstream, upmax, g ? g->word0 : nullptr, g ? g->slot : nullptr, g ? g->slot2 : nullptr);
-        GNR_HIP(hipGetLastError());
+        return launch<k_absmax_bits>("k_absmax_bits", st, dim3(blocks), dim3(256), 0, upstream, n_upstream, upmax, g ? g->word0 : nullptr,
+                                     g ? g->slot : nullptr, g ? g->slot2 : nullptr);
     }
     return GNR_OK;
 }
 static int feat_grad_unpack(const GnrScene* s, const FeatGradBuf& g, float* d_ray_feats, float* d_img_feats, const char* label, hipStream_t st) {
     const int npix = s->fh * s->fw;
-    KScope ks(label, st);
-    if (g.fixed) hipLaunchKernelGGL(k_unpack_feat_grad<true>, dim3((npix + 63) / 64, s->B * s->V), dim3(256), 0, st, g.buf, d_ray_feats, d_img_feats, npix, g.fx);
-    else hipLaunchKernelGGL(k_unpack_feat_grad<false>, dim3((npix + 63) / 64, s->B * s->V), dim3(256), 0, st, g.buf, d_ray_feats, d_img_feats, npix, g.fx);
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    const dim3 grid((npix + 63) / 64, s->B * s->V);
+    return g.fixed ? launch<k_unpack_feat_grad<true>>(label, st, grid, dim3(256), 0, g.buf, d_ray_feats, d_img_feats, npix, g.fx)
+                   : launch<k_unpack_feat_grad<false>>(label, st, grid, dim3(256), 0, g.buf, d_ray_feats, d_img_feats, npix, g.fx);
 }
 
 // Binned scatter of the feature-map gradient (csrc/gnr_bwd_scatter.inc): its buffers inside a training workspace, for T tiles of 16 points
@@ -311,30 +344,20 @@ static ScatterBins scatter_bins(const GnrScene* s, size_t T, char* base) {
                        (int*)(base + c.list), (int*)(base + c.nseg)};
 }
 // the launches behind k_view1_bwd_pw when it parked its rows: places of the bins, row ids into them, sums per pixel
-static int launch_scatter_bins(const GnrScene* s, const ScatterBins& sc, float* dfeat64, int ntiles, const char* entry, bool fixed, const FeatFx& fx, hipStream_t st) {
+static int launch_scatter_bins(const GnrScene* s, const ScatterBins& sc, float* dfeat64, int ntiles, const BwdEntry& e, bool fixed, const FeatFx& fx, hipStream_t st) {
     const int BV = s->B * s->V, npix = s->fh * s->fw, cap = (ntiles / s->B) * 16, N = ntiles * s->V * 16;
-    const bool vol = strstr(entry, "volume") != nullptr;
-    if ((size_t)npix * sizeof(int) <= 150 * 1024) {
-        static std::atomic<unsigned long long> attr_done{0};
-        if (attr_needed(attr_done)) GNR_HIP(hipFuncSetAttribute((const void*)k_scatter_place, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        KScope ks(vol ? "k_scatter_place@gnr_sample_volume_bwd" : "k_scatter_place@gnr_render_chain_bwd", st);
-        hipLaunchKernelGGL(k_scatter_place, dim3(BV), dim3(1024), (size_t)npix * sizeof(int), st, (const int*)sc.cnt, (const int*)sc.key, sc.list, sc.nseg, npix, cap, s->V);
-        GNR_HIP(hipGetLastError());
+    constexpr size_t PLACE_LDS = 150 * 1024;                   // k_scatter_place counts a scene-view's pixels in LDS
+    if ((size_t)npix * sizeof(int) <= PLACE_LDS) {
+        if (int rc = launch<k_scatter_place, PLACE_LDS>(e.scatter_place, st, dim3(BV), dim3(1024), (size_t)npix * sizeof(int), (const int*)sc.cnt,
+                                                        (const int*)sc.key, sc.list, sc.nseg, npix, cap, s->V)) return rc;
     } else {
-        { KScope ks(vol ? "k_scatter_scan@gnr_sample_volume_bwd" : "k_scatter_scan@gnr_render_chain_bwd", st);
-          hipLaunchKernelGGL(k_scatter_scan, dim3(BV), dim3(1024), 0, st, (const int*)sc.cnt, sc.cursor, sc.nseg, npix, cap); }
-        GNR_HIP(hipGetLastError());
-        { KScope ks(vol ? "k_scatter_fill@gnr_sample_volume_bwd" : "k_scatter_fill@gnr_render_chain_bwd", st);
-          hipLaunchKernelGGL(k_scatter_fill, dim3((N + 255) / 256), dim3(256), 0, st, (const int*)sc.key, sc.cursor, sc.list, N); }
-        GNR_HIP(hipGetLastError());
+        if (int rc = launch<k_scatter_scan>(e.scatter_scan, st, dim3(BV), dim3(1024), 0, (const int*)sc.cnt, sc.cursor, sc.nseg, npix, cap)) return rc;
+        if (int rc = launch<k_scatter_fill>(e.scatter_fill, st, dim3((N + 255) / 256), dim3(256), 0, (const int*)sc.key, sc.cursor, sc.list, N)) return rc;
     }
     ScatterGatherArgs g{sc, dfeat64, BV, cap, npix, s->fh, s->fw, fx};
     const int chunks = BV * ((cap + 63) / 64);
-    { KScope ks(vol ? "k_scatter_gather@gnr_sample_volume_bwd" : "k_scatter_gather@gnr_render_chain_bwd", st);
-      if (fixed) hipLaunchKernelGGL(k_scatter_gather<true>, dim3((chunks + 3) / 4), dim3(256), 0, st, g);
-      else hipLaunchKernelGGL(k_scatter_gather<false>, dim3((chunks + 3) / 4), dim3(256), 0, st, g); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    return fixed ? launch<k_scatter_gather<true>>(e.scatter_gather, st, dim3((chunks + 3) / 4), dim3(256), 0, g)
+                 : launch<k_scatter_gather<false>>(e.scatter_gather, st, dim3((chunks + 3) / 4), dim3(256), 0, g);
 }
 
 // One launch of the first view loop's backward = the fp16-pair kernel of the call's options (partner wavefronts + binned scatter by
@@ -342,63 +365,49 @@ static int launch_scatter_bins(const GnrScene* s, const ScatterBins& sc, float* 
 // return at once when the pass is range-flagged and the latter unless (~6 us of launch; nothing synchronises with the host).
 // GNR_OPT_FP32_CHAIN: the fp32 instantiation alone.
 template <bool USEVIS, bool BP>
-static void launch_view1_single(const View1BwdArgs& a, bool fixed, int blocks, hipStream_t st) {
-    const size_t lds = (USEVIS ? l1::TOTAL_VIS : l1::TOTAL) * sizeof(float);
-    if (fixed) hipLaunchKernelGGL((k_view1_bwd<USEVIS, true, BP>), dim3(blocks), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((k_view1_bwd<USEVIS, false, BP>), dim3(blocks), dim3(256), lds, st, a);
+static int launch_view1_single(const char* label, const View1BwdArgs& a, bool fixed, int blocks, hipStream_t st) {
+    constexpr size_t lds = (USEVIS ? l1::TOTAL_VIS : l1::TOTAL) * sizeof(float);
+    return fixed ? launch<k_view1_bwd<USEVIS, true, BP>, lds>(label, st, dim3(blocks), dim3(256), lds, a)
+                 : launch<k_view1_bwd<USEVIS, false, BP>, lds>(label, st, dim3(blocks), dim3(256), lds, a);
 }
 static bool view1_bins(const GnrScene* s) { return view1_partner(s) && !opt(s, GNR_OPT_DIRECT_SCATTER) && !opt(s, GNR_OPT_FP32_CHAIN) && GNR_BWD_PAIRS != 0; }
-static int launch_view1_bwd(const GnrScene* s, const Workspace& w, View1BwdArgs a, bool fixed, int ntiles, char* scatter_region, bool volume, hipStream_t st) {
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) {
-        const int n = (int)(l1::TOTAL * sizeof(float)), nv = (int)(l1::TOTAL_VIS * sizeof(float)), np = (int)(l1p::TOTAL * sizeof(float));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, n));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, n));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, n));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, n));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, nv));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, nv));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, nv));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, nv));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd_pw<false>, hipFuncAttributeMaxDynamicSharedMemorySize, np));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd_pw<true>, hipFuncAttributeMaxDynamicSharedMemorySize, np));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view1_bwd_pw<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, np));
-    }
-    int blocks = (ntiles + 3) / 4;
-    if (blocks > num_cus()) blocks = num_cus();
+static int launch_view1_bwd(const GnrScene* s, const Workspace& w, const BwdEntry& e, View1BwdArgs a, bool fixed, int ntiles, char* scatter_region, hipStream_t st) {
+    const int blocks = chain_blocks(ntiles);
     const bool f32 = opt(s, GNR_OPT_FP32_CHAIN) || GNR_BWD_PAIRS == 0;
     const bool pw = view1_partner(s);
     const bool bins = view1_bins(s) && scatter_region;       // (both feature-gradient modes: the rows are parked as floats either way)
-    const char* label = volume ? "k_view1_bwd@gnr_sample_volume_bwd" : "k_view1_bwd@gnr_render_chain_bwd";
     if (!f32) {
-        a.guard = bwd_guard(s, w, volume, 1);
+        a.guard = bwd_guard(s, w, e, 1);
         if (bins) {
             a.sc = scatter_bins(s, (size_t)ntiles, scatter_region);
             a.sc.upmax = fixed ? const_cast<unsigned*>(a.fx.upmax) : nullptr;
             GNR_HIP(hipMemsetAsync(a.sc.cnt, 0, (size_t)s->B * s->V * s->fh * s->fw * sizeof(int), st));
         }
-        {
-            KScope ks(label, st);
-            if (pw) {
-                if (bins) hipLaunchKernelGGL((k_view1_bwd_pw<false, true>), dim3(blocks), dim3(512), l1p::TOTAL * sizeof(float), st, a);
-                else if (fixed) hipLaunchKernelGGL(k_view1_bwd_pw<true>, dim3(blocks), dim3(512), l1p::TOTAL * sizeof(float), st, a);
-                else hipLaunchKernelGGL(k_view1_bwd_pw<false>, dim3(blocks), dim3(512), l1p::TOTAL * sizeof(float), st, a);
-            } else if (s->use_vis) launch_view1_single<true, true>(a, fixed, blocks, st);
-            else launch_view1_single<false, true>(a, fixed, blocks, st);
-        }
-        GNR_HIP(hipGetLastError());
+        constexpr size_t ldsp = l1p::TOTAL * sizeof(float);
+        int rc;
+        if (pw && bins) rc = launch<k_view1_bwd_pw<false, true>, ldsp>(e.view1, st, dim3(blocks), dim3(512), ldsp, a);
+        else if (pw && fixed) rc = launch<k_view1_bwd_pw<true>, ldsp>(e.view1, st, dim3(blocks), dim3(512), ldsp, a);
+        else if (pw) rc = launch<k_view1_bwd_pw<false>, ldsp>(e.view1, st, dim3(blocks), dim3(512), ldsp, a);
+        else if (s->use_vis) rc = launch_view1_single<true, true>(e.view1, a, fixed, blocks, st);
+        else rc = launch_view1_single<false, true>(e.view1, a, fixed, blocks, st);
+        if (rc) return rc;
         if (bins)                                               // (a flagged pass parked nothing: the bins are empty, the twin below scatters directly)
-            if (int rc = launch_scatter_bins(s, a.sc, a.dfeat64, ntiles, label, fixed, a.fx, st)) return rc;
+            if (int rc2 = launch_scatter_bins(s, a.sc, a.dfeat64, ntiles, e, fixed, a.fx, st)) return rc2;
         a.sc = ScatterBins{};
     }
-    a.guard = bwd_guard(s, w, volume, f32 ? 0 : 2);
-    if (f32 || a.guard.run_if) {
-        KScope ks(f32 ? label : (volume ? "k_view1_bwd.fp32_twin@gnr_sample_volume_bwd" : "k_view1_bwd.fp32_twin@gnr_render_chain_bwd"), st);
-        if (s->use_vis) launch_view1_single<true, false>(a, fixed, blocks, st);
-        else launch_view1_single<false, false>(a, fixed, blocks, st);
-    }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    a.guard = bwd_guard(s, w, e, f32 ? 0 : 2);
+    if (!f32 && !a.guard.run_if) return GNR_OK;
+    const char* label = f32 ? e.view1 : e.view1_twin;
+    return s->use_vis ? launch_view1_single<true, false>(label, a, fixed, blocks, st) : launch_view1_single<false, false>(label, a, fixed, blocks, st);
+}
+
+// k_ray, k_ray_bwd and k_ray_dual_bwd keep `ray_floats` floats of LDS per ray and give a ray `slots` lanes: -> rays per workgroup, what
+// its 256 lanes and the LDS budget hold (0: a ray does not fit), and the LDS stride of a ray.  Consecutive rays start 16 banks apart: a
+// wavefront spans up to 3 rays whose broadcast reads then hit disjoint banks.
+static int pack_rays(int ray_floats, int slots, int lds_budget_bytes, int* ray_stride) {
+    *ray_stride = ((ray_floats + 63) / 64) * 64 + 16;
+    const int fit = lds_budget_bytes / (*ray_stride * (int)sizeof(float));
+    return 256 / slots < fit ? 256 / slots : fit;
 }
 
 // (RS_RAY_WATCH: the watch word of k_ray<true>'s matrix-core tail, bit 1.  Sticky until the next gnr_prepare: once tripped, every later
@@ -406,33 +415,22 @@ static int launch_view1_bwd(const GnrScene* s, const Workspace& w, View1BwdArgs 
 // k_ray packs floor(256/slots) rays into a workgroup (slots = lanes per ray); two workgroups share a CU's LDS.
 template <bool RENDER>
 static int launch_ray(RayArgs& a, hipStream_t st) {
-    constexpr int PER = ray_per(RENDER);
     const int fdn = (RENDER && a.fine_depth) ? a.fdn : 0;
     a.slots = a.dn > fdn ? a.dn : fdn;
-    int stride = a.dn * PER;
-    if (RENDER && stride < rt::END) stride = rt::END;
-    // consecutive rays start 16 banks apart: a wavefront spans up to 3 rays whose broadcast reads then hit disjoint banks
-    a.ray_stride = ((stride + 63) / 64) * 64 + 16;
+    int ray_floats = a.dn * ray_per(RENDER);
+    if (RENDER && ray_floats < rt::END) ray_floats = rt::END;
     const int lds_budget = (RENDER && GNR_RAY_BLOCKS >= 3 ? 52 : 78) * 1024;      // three / two workgroups per CU
-    int rpb = 256 / a.slots;
-    const int fit = lds_budget / (a.ray_stride * (int)sizeof(float));
-    if (rpb > fit) rpb = fit;
+    const int rpb = pack_rays(ray_floats, a.slots, lds_budget, &a.ray_stride);
     if (rpb < 1) return fail(GNR_ERR_SHAPE, "k_ray: a ray does not fit the LDS budget");
     a.rays_per_block = rpb;
+    constexpr size_t MAX_LDS = 80 * 1024;
     const size_t lds_bytes = (size_t)rpb * a.ray_stride * sizeof(float);
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) {
-        GNR_HIP(hipFuncSetAttribute((const void*)k_ray<RENDER>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        if (RENDER) GNR_HIP(hipFuncSetAttribute((const void*)k_ray<RENDER, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    }
-    { KScope ks(RENDER ? "k_ray.render" : "k_ray.volume", st); hipLaunchKernelGGL((k_ray<RENDER>), dim3((unsigned)((a.nrays + rpb - 1) / rpb)), dim3(256), lds_bytes, st, a); }
-    GNR_HIP(hipGetLastError());
+    const dim3 grid((unsigned)((a.nrays + rpb - 1) / rpb));
+    if (int rc = launch<k_ray<RENDER>, MAX_LDS>(RENDER ? "k_ray.render" : "k_ray.volume", st, grid, dim3(256), lds_bytes, a)) return rc;
     if (RENDER && GNR_RAY_GEO_MFMA != 0 && a.range_word) {
         // the fp32 twin of the matrix-core tail: returns at once unless that launch flagged a non-finite value (range guard, k_ray)
         a.only_if = a.range_word;
-        KScope ks("k_ray.render.fp32_twin", st);
-        hipLaunchKernelGGL((k_ray<RENDER, false>), dim3((unsigned)((a.nrays + rpb - 1) / rpb)), dim3(256), lds_bytes, st, a);
-        GNR_HIP(hipGetLastError());
+        return launch<k_ray<RENDER, false>, MAX_LDS>("k_ray.render.fp32_twin", st, grid, dim3(256), lds_bytes, a);
     }
     return GNR_OK;
 }
@@ -459,11 +457,8 @@ extern "C" int gnr_prepare(const GnrScene* s, void* ws, size_t ws_bytes, void* s
     hipStream_t st = (hipStream_t)stream;
     const int npix = s->fh * s->fw, BV = s->B * s->V;
     // k_view_setup first: it also zeroes the range word that k_repack_feats and the chain launches OR into
-    { KScope ks("k_view_setup@gnr_prepare", st); hipLaunchKernelGGL(k_view_setup, dim3((BV + 63) / 64), dim3(64), 0, st, s->poses, s->Ks, s->depth_range, w.viewp, BV, w.range_flag); }
-    GNR_HIP(hipGetLastError());
-    { KScope ks("k_repack_feats@gnr_prepare", st); hipLaunchKernelGGL(k_repack_feats, dim3((npix + 63) / 64, BV), dim3(256), 0, st, s->ray_feats, s->img_feats, w.feat64, npix, w.range_flag); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    if (int rc = launch<k_view_setup>("k_view_setup@gnr_prepare", st, dim3((BV + 63) / 64), dim3(64), 0, s->poses, s->Ks, s->depth_range, w.viewp, BV, w.range_flag)) return rc;
+    return launch<k_repack_feats>("k_repack_feats@gnr_prepare", st, dim3((npix + 63) / 64, BV), dim3(256), 0, s->ray_feats, s->img_feats, w.feat64, npix, w.range_flag);
 }
 
 // range guard of the pair form: bit 0 = a feature-map value beyond +-6e4 or not finite (k_repack_feats), bit 1 = an activation or
@@ -525,10 +520,8 @@ static int volume_impl(const GnrScene* s, const float* bbox_min, int R, const fl
     const int P = R * R * R;
     // the inference path's chain kernel computes the grid points itself (ChainArgs::pts_R); the per-column kernel never reads them: no k_points_volume
     const bool inline_pts = GNR_VOLUME_POINTS_INLINE != 0 && chain && ray && !dbg && R * R * R < (1 << 22);
-    if (points && !inline_pts) {
-        { KScope ks("k_points_volume@volume_impl", st); hipLaunchKernelGGL(k_points_volume, dim3((s->B * P + 255) / 256), dim3(256), 0, st, bbox_min, w.desc, R, s->B); }
-        GNR_HIP(hipGetLastError());
-    }
+    if (points && !inline_pts)
+        if (int rc = launch<k_points_volume>("k_points_volume@volume_impl", st, dim3((s->B * P + 255) / 256), dim3(256), 0, bbox_min, w.desc, R, s->B)) return rc;
     // GNR_OPT_SPLIT_LAUNCH: scenes [0, B/2) on the caller's stream, [B/2, B) on the library's side stream: the second half's chain launch
     // starts on the CUs the first half's workgroups leave, the first half's per-column kernel on those the second half's leave
     const bool split = opt(s, GNR_OPT_SPLIT_LAUNCH) && chain && ray && !dbg && s->B >= 2;
@@ -544,9 +537,7 @@ static int volume_impl(const GnrScene* s, const float* bbox_min, int R, const fl
                         nb, P, s->H, s->W, s->fh, s->fw, brick_order_ok(R) ? R : 0};
             a.b0 = b0;
             if (inline_pts) { a.bbox_min = bbox_min; a.pts_R = R; }
-            a.range_flag = w.range_flag;
-            a.range_launch = w.range_flag ? w.range_flag + RS_VOLUME : nullptr;
-            a.tile_ctr = (w.range_flag && !opt(s, GNR_OPT_STATIC_TILES)) ? w.range_flag + RS_WORDS + 16 * part : nullptr;
+            wire_chain(a, s, w, RS_VOLUME, part);
             if (int rc = launch_chain<false>(s, a, ps)) return rc;
         }
         if (ray) {
@@ -587,8 +578,7 @@ static int order_rays(const GnrScene* s, const GnrRays* q, Workspace& w, hipStre
     if (!opt(s, GNR_OPT_RAY_ORDER_MORTON) || q->rn > MAX_SORT_RAYS || q->rn < 2) return GNR_OK;
     int shift = 0;
     while (((s->W > s->H ? s->W : s->H) >> shift) > 1024) ++shift;
-    { KScope ks("k_ray_order@render_pass", st); hipLaunchKernelGGL(k_ray_order, dim3(s->B), dim3(256), 0, st, q->coords, w.ray_perm, q->rn, shift); }
-    GNR_HIP(hipGetLastError());
+    if (int rc = launch<k_ray_order>("k_ray_order@render_pass", st, dim3(s->B), dim3(256), 0, q->coords, w.ray_perm, q->rn, shift)) return rc;
     *perm_out = w.ray_perm;
     return GNR_OK;
 }
@@ -605,8 +595,32 @@ static bool sample_order_wanted(const GnrScene* s, const Workspace& w, int P) {
     return ntiles >= SAMPLE_ORDER_MIN_TILES_PER_SLOT * slots;
 }
 static int launch_sample_order(const unsigned char* keys, int* perm, int B, int P, int nkeys, hipStream_t st) {
-    { KScope ks("k_sample_order@render_pass", st); hipLaunchKernelGGL(k_sample_order, dim3(B), dim3(1024), 0, st, keys, perm, P, nkeys); }
-    GNR_HIP(hipGetLastError());
+    return launch<k_sample_order>("k_sample_order@render_pass", st, dim3(B), dim3(1024), 0, keys, perm, P, nkeys);
+}
+// The per-ray kernel's arguments for a render pass (inference: render_pass; training: gnr_render_tail_fwd_train) on the records the pass's
+// chain left in the workspace; desc = the pass's point descriptors.  The caller adds the resampler's outputs and the ray order.
+static RayArgs render_ray_args(const GnrScene* s, const GnrRays* q, const float* depth, int dn, const float* wl, const GnrRenderOut* out,
+                               const Workspace& w, const float* desc) {
+    RayArgs r;
+    memset(&r, 0, sizeof(r));
+    r.wpk = wl; r.rec = w.rec; r.desc = desc; r.depth = depth; r.colors = out->colors_nr; r.que_dr = q->que_depth_range;
+    r.nrays = s->B * q->rn; r.dn = dn; r.rays_per_scene = q->rn;
+    r.sdf = out->sdf_values; r.alpha = out->alpha_values; r.hit = out->hit_prob_nr; r.pix = out->pixel_colors_nr;
+    r.rdepth = out->render_depth; r.gerr_part = out->sdf_gradient_error ? w.gerr_part : nullptr; r.grad = out->sdf_gradient;
+    r.rmask = out->ray_mask; r.view_num = q->ray_mask_view_num; r.point_num = q->ray_mask_point_num;
+    r.range_word = w.range_flag ? w.range_flag + RS_RAY_WATCH : nullptr;
+    return r;
+}
+// ... and what follows that kernel: the chunk means of the eikonal term and the rays' ground-truth colours (want_gt; gt_also: a second copy)
+static int render_ray_epilogue(const GnrScene* s, const GnrRays* q, const GnrRenderOut* out, int dn, const Workspace& w, const char* gerr_label,
+                               const char* gt_label, bool want_gt, float* gt_also, hipStream_t st) {
+    const int B = s->B, rn = q->rn;
+    if (out->sdf_gradient_error) {
+        const int chunk = q->ray_batch_num > 0 ? q->ray_batch_num : rn;
+        if (int rc = launch<k_gerr_reduce>(gerr_label, st, dim3(B, (rn + chunk - 1) / chunk), dim3(256), 0, w.gerr_part, out->sdf_gradient_error, rn, dn, chunk)) return rc;
+    }
+    if (out->pixel_colors_gt && q->que_imgs && want_gt)
+        if (int rc = launch<k_pixel_gt>(gt_label, st, dim3((B * rn + 255) / 256), dim3(256), 0, q->que_imgs, q->coords, out->pixel_colors_gt, rn, s->H, s->W, B, gt_also)) return rc;
     return GNR_OK;
 }
 // gt_also / skip_gt: the ground-truth colours of the rays are the same in both passes of gnr_render_rays_fwd: the coarse pass's launch writes
@@ -619,41 +633,21 @@ static int render_pass(const GnrScene* s, const GnrRays* q, const float* depth, 
     const int B = s->B, rn = q->rn;
     const int P = rn * dn;
     const bool ordered = !sample_perm_in && sample_order_wanted(s, w, P);      // the pass's own view-mask order: keys from k_points_rays, then the sort
-    { KScope ks("k_points_rays@render_pass", st); hipLaunchKernelGGL(k_points_rays, dim3((B * P + 255) / 256), dim3(256), 0, st, q->coords, q->que_pose, q->que_K,
-                       q->que_depth_range, depth, w.desc, rn, dn, B, perm, gen_depth ? const_cast<float*>(depth) : nullptr,     // gen_depth: the coarse pass's depths are generated here, into `depth`
-                       ordered ? w.sample_keys : nullptr, w.viewp, s->V, s->H, s->W); }
-    GNR_HIP(hipGetLastError());
+    if (int rc = launch<k_points_rays>("k_points_rays@render_pass", st, dim3((B * P + 255) / 256), dim3(256), 0, q->coords, q->que_pose, q->que_K,
+                                       q->que_depth_range, depth, w.desc, rn, dn, B, perm, gen_depth ? const_cast<float*>(depth) : nullptr,     // gen_depth: the coarse pass's depths are generated here, into `depth`
+                                       ordered ? w.sample_keys : nullptr, w.viewp, s->V, s->H, s->W)) return rc;
     if (ordered)
         if (int rc = launch_sample_order(w.sample_keys, w.sample_perm, B, P, 1 << s->V, st)) return rc;
     ChainArgs a{wl, w.feat64, s->imgs, w.viewp, w.desc, w.rec, out->colors_nr, out->view_mask, nullptr,
                 B, P, s->H, s->W, s->fh, s->fw, 0};
-    a.range_flag = w.range_flag;
-    a.range_launch = w.range_flag ? w.range_flag + range_slot : nullptr;      // watch word of this pass (RS_COARSE: coarse / by-depth, RS_FINE)
-    a.tile_ctr = (w.range_flag && !opt(s, GNR_OPT_STATIC_TILES)) ? w.range_flag + RS_WORDS : nullptr;
+    wire_chain(a, s, w, range_slot);                       // watch word of this pass (RS_COARSE: coarse / by-depth, RS_FINE)
     a.ray_perm = perm; a.perm_rn = rn; a.perm_dn = dn;
     a.sample_perm = ordered ? w.sample_perm : sample_perm_in;
     if (int rc = launch_chain<true>(s, a, st)) return rc;
-    RayArgs r;
-    memset(&r, 0, sizeof(r));
-    r.wpk = wl; r.rec = w.rec; r.desc = w.desc; r.depth = depth; r.colors = out->colors_nr; r.que_dr = q->que_depth_range;
-    r.nrays = B * rn; r.dn = dn; r.rays_per_scene = rn;
-    r.sdf = out->sdf_values; r.alpha = out->alpha_values; r.hit = out->hit_prob_nr; r.pix = out->pixel_colors_nr;
-    r.rdepth = out->render_depth; r.gerr_part = out->sdf_gradient_error ? w.gerr_part : nullptr; r.grad = out->sdf_gradient;
-    r.rmask = out->ray_mask; r.view_num = q->ray_mask_view_num; r.point_num = q->ray_mask_point_num;
+    RayArgs r = render_ray_args(s, q, depth, dn, wl, out, w, w.desc);
     r.fine_depth = fine_depth; r.fine_inds = fine_inds; r.fdn = fdn; r.fine_u = fine_u; r.ray_perm = perm;
-    r.range_word = w.range_flag ? w.range_flag + RS_RAY_WATCH : nullptr;
     if (int rc = launch_ray<true>(r, st)) return rc;
-    if (out->sdf_gradient_error) {
-        const int chunk = q->ray_batch_num > 0 ? q->ray_batch_num : rn;
-        { KScope ks("k_gerr_reduce@render_pass", st); hipLaunchKernelGGL(k_gerr_reduce, dim3(B, (rn + chunk - 1) / chunk), dim3(256), 0, st, w.gerr_part,
-                           out->sdf_gradient_error, rn, dn, chunk); }
-        GNR_HIP(hipGetLastError());
-    }
-    if (out->pixel_colors_gt && q->que_imgs && !skip_gt) {
-        { KScope ks("k_pixel_gt@render_pass", st); hipLaunchKernelGGL(k_pixel_gt, dim3((B * rn + 255) / 256), dim3(256), 0, st, q->que_imgs, q->coords, out->pixel_colors_gt,
-                           rn, s->H, s->W, B, gt_also); }
-        GNR_HIP(hipGetLastError());
-    }
+    if (int rc = render_ray_epilogue(s, q, out, dn, w, "k_gerr_reduce@render_pass", "k_pixel_gt@render_pass", !skip_gt, gt_also, st)) return rc;
     if (out->depth && out->depth != depth)
         GNR_HIP(hipMemcpyAsync(out->depth, depth, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
     return GNR_OK;
@@ -762,8 +756,7 @@ extern "C" int gnr_render_rays_fwd(const GnrScene* s, const GnrRays* q, const fl
     if (q->fine_depth_use_all && !fine_depth_in) {
         const int n = B * q->rn * fine_dn;
         float* depth_m = fine->depth ? fine->depth : w.depth_m;
-        { KScope ks("k_merge_depths@gnr_render_rays_fwd", st); hipLaunchKernelGGL(k_merge_depths, dim3((n + 255) / 256), dim3(256), 0, st, depth_c, depth_f, depth_m, B * q->rn, q->dn, q->fdn); }
-        GNR_HIP(hipGetLastError());
+        if (int rc = launch<k_merge_depths>("k_merge_depths@gnr_render_rays_fwd", st, dim3((n + 255) / 256), dim3(256), 0, depth_c, depth_f, depth_m, B * q->rn, q->dn, q->fdn)) return rc;
         fdepth = depth_m;
     }
     return render_pass(s, q, fdepth, fine_dn, wf, fine, w, st, nullptr, nullptr, 0, nullptr, perm, RS_FINE, nullptr, one_gt);
@@ -777,9 +770,7 @@ extern "C" int gnr_merge_depths(const float* depth_a, int na, const float* depth
     if (nrays < 1 || na < 1 || nb < 1 || na + nb > MAX_DN_FWD) return fail(GNR_ERR_SHAPE, "gnr_merge_depths: 1 <= na, nb and na + nb <= 128");
     const long n = (long)nrays * (na + nb);
     if (n > ((long)1 << 31) - 1024) return fail(GNR_ERR_SHAPE, "gnr_merge_depths: too many samples in one call");
-    { KScope ks("k_merge_depths@gnr_merge_depths", (hipStream_t)stream); hipLaunchKernelGGL(k_merge_depths, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, depth_a, depth_b, out, nrays, na, nb); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    return launch<k_merge_depths>("k_merge_depths@gnr_merge_depths", (hipStream_t)stream, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, depth_a, depth_b, out, nrays, na, nb);
 }
 
 extern "C" int gnr_depth_mean_fwd(const GnrScene* s, const float* coords, int pn, const float* level_weights, float* mean_out,
@@ -791,9 +782,7 @@ extern "C" int gnr_depth_mean_fwd(const GnrScene* s, const float* coords, int pn
     if (ws_bytes < w.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     DepthMeanArgs a{level_weights, w.feat64, coords, mean_out, s->B, s->V, pn, s->H, s->W, s->fh, s->fw};
     const long tiles = (long)s->B * s->V * ((pn + 15) / 16);
-    { KScope ks("k_depth_mean@gnr_depth_mean_fwd", (hipStream_t)stream); hipLaunchKernelGGL(k_depth_mean, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    return launch<k_depth_mean>("k_depth_mean@gnr_depth_mean_fwd", (hipStream_t)stream, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, a);
 }
 
 // backward of gnr_depth_mean_fwd for one level.  dmean [B,V,pn,2]; gradients are ACCUMULATED into
@@ -830,12 +819,8 @@ extern "C" int gnr_depth_mean_bwd(const GnrScene* s, const float* coords, int pn
     const int cap = 2 * num_cus();
     if (blocks > cap) blocks = cap;
     if (int rc = poison_partials(dpart, (size_t)blocks * 4 * DM_STRIDE * sizeof(float), st, s->options)) return rc;
-    {
-        KScope ks("k_depth_mean_bwd@gnr_depth_mean_bwd", st);
-        if (fg.fixed) hipLaunchKernelGGL(k_depth_mean_bwd<true>, dim3(blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_depth_mean_bwd<false>, dim3(blocks), dim3(256), 0, st, a);
-    }
-    GNR_HIP(hipGetLastError());
+    if (int rc = fg.fixed ? launch<k_depth_mean_bwd<true>>("k_depth_mean_bwd@gnr_depth_mean_bwd", st, dim3(blocks), dim3(256), 0, a)
+                          : launch<k_depth_mean_bwd<false>>("k_depth_mean_bwd@gnr_depth_mean_bwd", st, dim3(blocks), dim3(256), 0, a)) return rc;
     {
         const GradRange rg[1] = {{can::MEAN0_W, can::VAR0_W, can::MEAN0_W}};
         if (int rc = launch_grad_reduce(dpart, blocks * 4, DM_STRIDE, d_canonical, rg, 1, st, "k_grad_reduce@gnr_depth_mean_bwd")) return rc;
@@ -897,14 +882,11 @@ extern "C" int gnr_sample_volume_fwd_train(const GnrScene* s, const float* bbox_
     if (ws_bytes < w.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int P = R * R * R;
-    { KScope ks("k_points_volume@gnr_sample_volume_fwd_train", st); hipLaunchKernelGGL(k_points_volume, dim3((s->B * P + 255) / 256), dim3(256), 0, st, bbox_min, w.desc, R, s->B); }
-    GNR_HIP(hipGetLastError());
+    if (int rc = launch<k_points_volume>("k_points_volume@gnr_sample_volume_fwd_train", st, dim3((s->B * P + 255) / 256), dim3(256), 0, bbox_min, w.desc, R, s->B)) return rc;
     char* tb = (char*)tws;
     ChainArgs a{wc, w.feat64, s->imgs, w.viewp, w.desc, w.rec, nullptr, nullptr, nullptr, s->B, P, s->H, s->W, s->fh, s->fw,
                 brick_order_ok(R) ? R : 0, (float*)(tb + t.save1), (float*)(tb + t.save2), (float*)(tb + t.saveG)};
-    a.range_flag = w.range_flag;
-    a.range_launch = w.range_flag ? w.range_flag + RS_VOLUME_TRAIN : nullptr;
-    a.tile_ctr = (w.range_flag && !opt(s, GNR_OPT_STATIC_TILES)) ? w.range_flag + RS_WORDS : nullptr;
+    wire_chain(a, s, w, RS_VOLUME_TRAIN);
     if (int rc = launch_chain<false, true>(s, a, st)) return rc;
     RayArgs r;
     memset(&r, 0, sizeof(r));
@@ -917,61 +899,71 @@ extern "C" int gnr_sample_volume_fwd_train(const GnrScene* s, const float* bbox_
 // guard, and behind it the fp32-input-MFMA instantiation of k_view2_bwd (launch_view1_bwd has the scheme).  The render pass's
 // single-wavefront kernel IS the fp32 instantiation: with GNR_OPT_VIEW2_ONE_WAVEFRONT it serves both sides of the flag in one launch.
 template <bool RENDER>
-static int launch_view2_bwd(const GnrScene* s, const Workspace& w, View2BwdArgs a, int blocks, hipStream_t st) {
-    constexpr size_t lds1 = (RENDER ? l3::TOTAL_RENDER : l3::TOTAL) * sizeof(float);
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) {
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view2_bwd<RENDER, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        if constexpr (!RENDER) GNR_HIP(hipFuncSetAttribute((const void*)k_view2_bwd<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_view2_bwd_pw<RENDER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(l3p::total(RENDER) * sizeof(float))));
-    }
-    const char* label = RENDER ? "k_view2_bwd@gnr_render_chain_bwd" : "k_view2_bwd@gnr_sample_volume_bwd";
+static int launch_view2_bwd(const GnrScene* s, const Workspace& w, const BwdEntry& e, View2BwdArgs a, int blocks, hipStream_t st) {
+    constexpr size_t lds1 = (RENDER ? l3::TOTAL_RENDER : l3::TOTAL) * sizeof(float), ldsp = l3p::total(RENDER) * sizeof(float);
     const bool f32 = opt(s, GNR_OPT_FP32_CHAIN) || GNR_BWD_PAIRS == 0;
     const bool pw = view2_partner(s);
     const bool single_is_f32 = RENDER && !pw;               // k_view2_bwd<true> has no pair form
     if (!f32 && !single_is_f32) {
-        a.guard = bwd_guard(s, w, !RENDER, 1);
-        KScope ks(label, st);
-        if (pw) hipLaunchKernelGGL(k_view2_bwd_pw<RENDER>, dim3(blocks), dim3(512), l3p::total(RENDER) * sizeof(float), st, a);
-        else if constexpr (!RENDER) hipLaunchKernelGGL((k_view2_bwd<false, true>), dim3(blocks), dim3(256), lds1, st, a);
-        GNR_HIP(hipGetLastError());
+        a.guard = bwd_guard(s, w, e, 1);
+        if (pw) {
+            if (int rc = launch<k_view2_bwd_pw<RENDER>, ldsp>(e.view2, st, dim3(blocks), dim3(512), ldsp, a)) return rc;
+        } else if constexpr (!RENDER) {
+            if (int rc = launch<k_view2_bwd<false, true>, lds1>(e.view2, st, dim3(blocks), dim3(256), lds1, a)) return rc;
+        }
     }
     const bool always = f32 || single_is_f32;
-    a.guard = bwd_guard(s, w, !RENDER, always ? 0 : 2);
-    if (always || a.guard.run_if) {
-        KScope ks(always ? label : (RENDER ? "k_view2_bwd.fp32_twin@gnr_render_chain_bwd" : "k_view2_bwd.fp32_twin@gnr_sample_volume_bwd"), st);
-        hipLaunchKernelGGL((k_view2_bwd<RENDER, false>), dim3(blocks), dim3(256), lds1, st, a);
-    }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    a.guard = bwd_guard(s, w, e, always ? 0 : 2);
+    if (!always && !a.guard.run_if) return GNR_OK;
+    return launch<k_view2_bwd<RENDER, false>, lds1>(always ? e.view2 : e.view2_twin, st, dim3(blocks), dim3(256), lds1, a);
 }
 
-template <int V>
-static int launch_geo_bwd(const GeoBwdArgs& a, hipStream_t st) {
-    constexpr size_t lds_floats = frag_floats(23, 4) + frag_floats(16, 1) + 64 + 16 + frag_floats(16, 4) + frag_floats(16, 1) +
-                                  frag_floats(4, 4) + 4 * 2 * 16 * TS2;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) {
-        GNR_HIP(hipFuncSetAttribute((const void*)k_geo_bwd<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_floats * sizeof(float))));
-    }
-    int blocks = (a.ntiles + 3) / 4;
-    if (blocks > num_cus()) blocks = num_cus();
-    { KScope ks("k_geo_bwd@launch_geo_bwd", st); hipLaunchKernelGGL(k_geo_bwd<V>, dim3(blocks), dim3(256), lds_floats * sizeof(float), st, a); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+// dynamic LDS of k_geo_bwd / k_hoist_bwd: their weight fragments + two tiles per wavefront.  (Their timing labels, and k_red2_bwd's, end in
+// "@launch_<kernel>_bwd", not in an entry point's name: tools/ and profiles/ key on the labels as they are.)
+constexpr size_t GEO_BWD_LDS = (frag_floats(23, 4) + frag_floats(16, 1) + 64 + 16 + frag_floats(16, 4) + frag_floats(16, 1) + frag_floats(4, 4) +
+                                4 * 2 * 16 * TS2) * sizeof(float);
+constexpr size_t HOIST_BWD_LDS = (2 * frag_floats(16, 4) + frag_floats(16, 1) + 4 * 2 * 16 * TS3) * sizeof(float);
+
+// The parameter stages of a chain backward run the same grid (chain_blocks): one slot of the partial-gradient buffer per wavefront, summed
+// once at the end (chain_bwd).  A partial run (tests: stage by stage) leaves ranges of the slots unwritten: zero them; a full run stores
+// every entry (GNR_OPT_POISON_PARTIALS shows one that it does not).
+static int chain_partials_begin(const GnrScene* s, float* dpart, int ntiles, int stages, hipStream_t st) {
+    const size_t bytes = (size_t)chain_blocks(ntiles) * 4 * GP_STRIDE * sizeof(float);
+    if ((stages & 15) == 0) return GNR_OK;
+    if ((stages & 15) != 15) { GNR_HIP(hipMemsetAsync(dpart, 0, bytes, st)); return GNR_OK; }
+    return poison_partials(dpart, bytes, st, s->options);
 }
 
-template <int V>
-static int launch_hoist_bwd(const HoistBwdArgs& a, hipStream_t st) {
-    constexpr size_t lds_floats = 2 * frag_floats(16, 4) + frag_floats(16, 1) + 4 * 2 * 16 * TS3;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) {
-        GNR_HIP(hipFuncSetAttribute((const void*)k_hoist_bwd<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_floats * sizeof(float))));
+// The stages gnr_sample_volume_bwd and gnr_render_chain_bwd share, behind the stages of their own: second view loop (stages bit 2) ->
+// hoisted columns + first reduction (bit 1) -> first view loop + feature-map gradients (bit 0) -> the fixed-order sum of the partial
+// parameter gradients into d_canonical.  BwdWs: the sections of the entry's training workspace they work on; desc = the P points' descriptors.
+struct BwdWs { const float *desc, *save1, *saveG, *dS2; float *dG, *dS1, *dpart; char *dfeat64, *scatter; };
+static int chain_bwd(const GnrScene* s, const Workspace& w, const BwdEntry& e, const BwdWs& t, const float* wl, const float* wb, int P, int stages,
+                     float* d_canonical, float* d_ray_feats, float* d_img_feats, hipStream_t st) {
+    const int ntiles = s->B * ((P + 15) / 16), blocks = chain_blocks(ntiles);
+    if (stages & 4) {                                    // stage 3: second view loop
+        View2BwdArgs a{wl, wb, t.save1, t.saveG, t.dS2, t.dS1, t.dG, t.dpart, s->V, ntiles, nullptr, nullptr, 0, 0, 0};
+        if (!e.volume) { a.desc = t.desc; a.viewp = w.viewp; a.P = P; a.H = s->H; a.W = s->W; }     // (the colour head needs the direction differences)
+        if (int rc = e.volume ? launch_view2_bwd<false>(s, w, e, a, blocks, st) : launch_view2_bwd<true>(s, w, e, a, blocks, st)) return rc;
     }
-    int blocks = (a.ntiles + 3) / 4;
-    if (blocks > num_cus()) blocks = num_cus();
-    { KScope ks("k_hoist_bwd@launch_hoist_bwd", st); hipLaunchKernelGGL(k_hoist_bwd<V>, dim3(blocks), dim3(256), lds_floats * sizeof(float), st, a); }
-    GNR_HIP(hipGetLastError());
+    if (stages & 2) {                                    // stage 2: hoisted columns + first reduction
+        HoistBwdArgs a{wb, t.save1, t.saveG, t.dG, t.dS1, t.dpart, ntiles};
+        if (int rc = with_views(s->V, [&](auto v) {
+                return launch<k_hoist_bwd<decltype(v)::value>, HOIST_BWD_LDS>("k_hoist_bwd@launch_hoist_bwd", st, dim3(blocks), dim3(256), HOIST_BWD_LDS, a);
+            })) return rc;
+    }
+    if (stages & 1) {                                    // stage 1: first view loop + feature-map gradients
+        FeatGradBuf fg;
+        const BwdGuard gmax = bwd_guard(s, w, e, 2);
+        if (int rc = feat_grad_begin(s, t.dfeat64, w, t.dS1, (size_t)ntiles * s->V * DS1 * 64, st, &fg, (view1_bins(s) && gmax.run_if) ? &gmax : nullptr)) return rc;
+        View1BwdArgs a{wl, wb, w.feat64, w.viewp, t.desc, t.dS1, fg.buf, t.dpart,
+                       s->B, s->V, P, s->H, s->W, s->fh, s->fw, ntiles, e.volume ? 0 : 1, fg.fx};
+        if (int rc = launch_view1_bwd(s, w, e, a, fg.fixed, ntiles, t.scatter, st)) return rc;
+        if (d_ray_feats || d_img_feats)
+            if (int rc = feat_grad_unpack(s, fg, d_ray_feats, d_img_feats, e.unpack, st)) return rc;
+    }
+    if (stages & 15)                                     // every entry of every slot was stored by exactly one of the stages (or zeroed in a partial run)
+        return launch_grad_reduce(t.dpart, blocks * 4, GP_STRIDE, d_canonical, e.rg, s->use_vis ? 3 : 2, st, e.reduce);
     return GNR_OK;
 }
 
@@ -1012,94 +1004,31 @@ extern "C" int gnr_sample_volume_bwd(const GnrScene* s, int R, const float* wc, 
     if (ws_bytes < w.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     char* tb = (char*)tws;
+    auto sec = [tb](size_t off) { return (float*)(tb + off); };
     const int P = R * R * R, ntiles = s->B * ((P + 15) / 16);
-    // stages 4..1 run the same grid: one slot of the partial-gradient buffer per wavefront, summed once at the end
-    float* dpart = (float*)(tb + t.dpart);
-    int cblocks = (ntiles + 3) / 4;
-    if (cblocks > num_cus()) cblocks = num_cus();
-    const int cslots = cblocks * 4;
-    if (stages & 15) {
-        // a partial run (tests: stage by stage) leaves ranges of the slots unwritten: zero them; a full run stores every entry
-        if ((stages & 15) != 15) GNR_HIP(hipMemsetAsync(dpart, 0, (size_t)cslots * GP_STRIDE * sizeof(float), st));
-        else if (int rc = poison_partials(dpart, (size_t)cslots * GP_STRIDE * sizeof(float), st, s->options)) return rc;
-    }
+    if (int rc = chain_partials_begin(s, sec(t.dpart), ntiles, stages, st)) return rc;
     if (stages & 16) {                                   // stage 5: tail
-        RayBwdArgs a{wc, w.rec, dvol, (float*)(tb + t.dg16), (float*)(tb + t.dtail_part), s->B * R * R, R, 0, 0, 0};
-        a.ray_stride = ((R * 76 + 63) / 64) * 64 + 16;
-        int rpb = 256 / R;
-        const int fit = (78 * 1024) / (a.ray_stride * (int)sizeof(float));
-        if (rpb > fit) rpb = fit;
+        RayBwdArgs a{wc, w.rec, dvol, sec(t.dg16), sec(t.dtail_part), s->B * R * R, R, 0, 0, 0};
+        const int rpb = pack_rays(R * 76, R, 78 * 1024, &a.ray_stride);
         if (rpb < 1) return fail(GNR_ERR_SHAPE, "k_ray_bwd: a ray does not fit the LDS budget");
         a.rays_per_block = rpb;
         a.nblocks = (a.nrays + rpb - 1) / rpb;
         size_t lds_bytes = (size_t)rpb * a.ray_stride * sizeof(float);
         if (lds_bytes < 2 * 256 * 16 * sizeof(float)) lds_bytes = 2 * 256 * 16 * sizeof(float);
-        static std::atomic<unsigned long long> attr_done{0};
-        if (attr_needed(attr_done)) {
-            GNR_HIP(hipFuncSetAttribute((const void*)k_ray_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        }
         int blocks = a.nblocks < 2 * num_cus() ? a.nblocks : 2 * num_cus();
-        if (int rc = poison_partials(tb + t.dtail_part, (size_t)blocks * 4 * tp::STRIDE * sizeof(float), st, s->options)) return rc;
-        { KScope ks("k_ray_bwd@gnr_sample_volume_bwd", st); hipLaunchKernelGGL(k_ray_bwd, dim3(blocks), dim3(256), lds_bytes, st, a); }
-        GNR_HIP(hipGetLastError());
-        if (int rc = launch_tail_reduce((const float*)(tb + t.dtail_part), blocks * 4, wc, (float*)(tb + t.dtail), st)) return rc;
-        { KScope ks("k_tail_unfold@gnr_sample_volume_bwd", st); hipLaunchKernelGGL(k_tail_unfold, dim3(1), dim3(256), 0, st, (const float*)(tb + t.dtail), canonical_dev, d_canonical); }
-        GNR_HIP(hipGetLastError());
+        if (int rc = poison_partials(sec(t.dtail_part), (size_t)blocks * 4 * tp::STRIDE * sizeof(float), st, s->options)) return rc;
+        if (int rc = launch<k_ray_bwd, 80 * 1024>("k_ray_bwd@gnr_sample_volume_bwd", st, dim3(blocks), dim3(256), lds_bytes, a)) return rc;
+        if (int rc = launch_tail_reduce(sec(t.dtail_part), blocks * 4, wc, sec(t.dtail), st)) return rc;
+        if (int rc = launch<k_tail_unfold>("k_tail_unfold@gnr_sample_volume_bwd", st, dim3(1), dim3(256), 0, (const float*)sec(t.dtail), canonical_dev, d_canonical)) return rc;
     }
     if (stages & 8) {                                    // stage 4: geometry_fc + second reduction
-        GeoBwdArgs a{wc, wb, w.desc, (const float*)(tb + t.save2), (const float*)(tb + t.dg16), (float*)(tb + t.dS2), dpart,
-                     s->B, P, ntiles};
-        int rc;
-        switch (s->V) {
-            case 2: rc = launch_geo_bwd<2>(a, st); break;
-            case 3: rc = launch_geo_bwd<3>(a, st); break;
-            case 4: rc = launch_geo_bwd<4>(a, st); break;
-            case 5: rc = launch_geo_bwd<5>(a, st); break;
-            case 6: rc = launch_geo_bwd<6>(a, st); break;
-            case 7: rc = launch_geo_bwd<7>(a, st); break;
-            default: rc = launch_geo_bwd<8>(a, st); break;
-        }
-        if (rc) return rc;
+        GeoBwdArgs a{wc, wb, w.desc, sec(t.save2), sec(t.dg16), sec(t.dS2), sec(t.dpart), s->B, P, ntiles};
+        if (int rc = with_views(s->V, [&](auto v) {
+                return launch<k_geo_bwd<decltype(v)::value>, GEO_BWD_LDS>("k_geo_bwd@launch_geo_bwd", st, dim3(chain_blocks(ntiles)), dim3(256), GEO_BWD_LDS, a);
+            })) return rc;
     }
-    if (stages & 4) {                                    // stage 3: second view loop
-        View2BwdArgs a{wc, wb, (const float*)(tb + t.save1), (const float*)(tb + t.saveG), (const float*)(tb + t.dS2),
-                       (float*)(tb + t.dS1), (float*)(tb + t.dG), dpart, s->V, ntiles, nullptr, nullptr, 0, 0, 0};
-        int blocks = (ntiles + 3) / 4;
-        if (blocks > num_cus()) blocks = num_cus();
-        if (int rc = launch_view2_bwd<false>(s, w, a, blocks, st)) return rc;
-    }
-    if (stages & 2) {                                    // stage 2: hoisted columns + first reduction
-        HoistBwdArgs a{wb, (const float*)(tb + t.save1), (const float*)(tb + t.saveG), (const float*)(tb + t.dG),
-                       (float*)(tb + t.dS1), dpart, ntiles};
-        int rc;
-        switch (s->V) {
-            case 2: rc = launch_hoist_bwd<2>(a, st); break;
-            case 3: rc = launch_hoist_bwd<3>(a, st); break;
-            case 4: rc = launch_hoist_bwd<4>(a, st); break;
-            case 5: rc = launch_hoist_bwd<5>(a, st); break;
-            case 6: rc = launch_hoist_bwd<6>(a, st); break;
-            case 7: rc = launch_hoist_bwd<7>(a, st); break;
-            default: rc = launch_hoist_bwd<8>(a, st); break;
-        }
-        if (rc) return rc;
-    }
-    if (stages & 1) {                                    // stage 1: first view loop + feature-map gradients
-        FeatGradBuf fg;
-        const BwdGuard gmax = bwd_guard(s, w, true, 2);
-        if (int rc = feat_grad_begin(s, tb + t.dfeat64, w, (const float*)(tb + t.dS1), (size_t)ntiles * s->V * DS1 * 64, st, &fg, (view1_bins(s) && gmax.run_if) ? &gmax : nullptr)) return rc;
-        View1BwdArgs a{wc, wb, w.feat64, w.viewp, w.desc, (const float*)(tb + t.dS1), fg.buf, dpart,
-                       s->B, s->V, P, s->H, s->W, s->fh, s->fw, ntiles, 0, fg.fx};
-        if (int rc = launch_view1_bwd(s, w, a, fg.fixed, ntiles, tb + t.scatter, true, st)) return rc;
-        if (d_ray_feats || d_img_feats)
-            if (int rc = feat_grad_unpack(s, fg, d_ray_feats, d_img_feats, "k_unpack_feat_grad@gnr_sample_volume_bwd", st)) return rc;
-    }
-    if (stages & 15) {
-        // decoder .. geometry_fc [0, WQ), neuray_fc [NR0_W, VARIANCE) (+ the vis branch behind the blob): every entry of every slot
-        // was stored by exactly one of the four stages (or zeroed above in a partial run)
-        const GradRange rg[3] = {{0, can::WQ, 0}, {can::NR0_W, can::VARIANCE, can::NR0_W}, {can::TOTAL, can::TOTAL_VIS, can::TOTAL}};
-        if (int rc = launch_grad_reduce(dpart, cslots, GP_STRIDE, d_canonical, rg, s->use_vis ? 3 : 2, st, "k_grad_reduce@gnr_sample_volume_bwd")) return rc;
-    }
-    return GNR_OK;
+    const BwdWs b{w.desc, sec(t.save1), sec(t.saveG), sec(t.dS2), sec(t.dG), sec(t.dS1), sec(t.dpart), tb + t.dfeat64, tb + t.scatter};
+    return chain_bwd(s, w, BWD_VOLUME, b, wc, wb, P, stages, d_canonical, d_ray_feats, d_img_feats, st);
 }
 
 // ---- render path, hybrid training: per-view chain in HIP (both directions), per-ray tail in PyTorch ----------
@@ -1154,36 +1083,23 @@ extern "C" int gnr_render_chain_fwd_train(const GnrScene* s, const GnrRays* q, c
     const int B = s->B, P = q->rn * dn, ntiles = B * ((P + 15) / 16);
     float* desc = (float*)(tb + t.desc);
     const int range_slot = depth ? RS_DEPTHS_TRAIN : RS_COARSE_TRAIN;      // watch word of this training pass
+    const dim3 pgrid((B * P + 255) / 256);
     if (!depth) {
-        { KScope ks("k_coarse_depth@gnr_render_chain_fwd_train", st); hipLaunchKernelGGL(k_coarse_depth, dim3((B * P + 255) / 256), dim3(256), 0, st, q->que_depth_range, w.depth_c, q->rn, dn, B); }
-        GNR_HIP(hipGetLastError());
+        if (int rc = launch<k_coarse_depth>("k_coarse_depth@gnr_render_chain_fwd_train", st, pgrid, dim3(256), 0, q->que_depth_range, w.depth_c, q->rn, dn, B)) return rc;
         depth = w.depth_c;
     }
     if (depth_out && depth_out != depth)
         GNR_HIP(hipMemcpyAsync(depth_out, depth, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
-    { KScope ks("k_points_rays@gnr_render_chain_fwd_train", st); hipLaunchKernelGGL(k_points_rays, dim3((B * P + 255) / 256), dim3(256), 0, st, q->coords, q->que_pose, q->que_K,
-                       q->que_depth_range, depth, desc, q->rn, dn, B); }
-    GNR_HIP(hipGetLastError());
-    if (pts_out || qdir_out) {
-        { KScope ks("k_desc_unpack@gnr_render_chain_fwd_train", st); hipLaunchKernelGGL(k_desc_unpack, dim3((B * P + 255) / 256), dim3(256), 0, st, (const float*)desc, pts_out, qdir_out, dn, B * P); }
-        GNR_HIP(hipGetLastError());
-    }
+    // (no ray order, no generated depths, no sample keys: the training pass keeps the caller's order)
+    if (int rc = launch<k_points_rays>("k_points_rays@gnr_render_chain_fwd_train", st, pgrid, dim3(256), 0, q->coords, q->que_pose, q->que_K, q->que_depth_range,
+                                       depth, desc, q->rn, dn, B, (const int*)nullptr, (float*)nullptr, (unsigned char*)nullptr, (const float*)nullptr, 0, 0, 0)) return rc;
+    if (pts_out || qdir_out)
+        if (int rc = launch<k_desc_unpack>("k_desc_unpack@gnr_render_chain_fwd_train", st, pgrid, dim3(256), 0, (const float*)desc, pts_out, qdir_out, dn, B * P)) return rc;
     ChainArgs a{wl, w.feat64, s->imgs, w.viewp, desc, w.rec, colors_out, nullptr, nullptr, B, P, s->H, s->W, s->fh, s->fw, 0,
                 (float*)(tb + t.save1), (float*)(tb + t.save2), (float*)(tb + t.saveG), (float*)(tb + t.saveZ)};
-    a.range_flag = w.range_flag;
-    a.range_launch = w.range_flag ? w.range_flag + range_slot : nullptr;
-    a.tile_ctr = (w.range_flag && !opt(s, GNR_OPT_STATIC_TILES)) ? w.range_flag + RS_WORDS : nullptr;
+    wire_chain(a, s, w, range_slot);
     if (int rc = launch_chain<true, true>(s, a, st)) return rc;
-    { KScope ks("k_stats_unpack@gnr_render_chain_fwd_train", st); hipLaunchKernelGGL(k_stats_unpack, dim3((ntiles + 3) / 4), dim3(256), 0, st, (const float*)(tb + t.saveZ), stats_out, P, ntiles); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
-}
-
-template <int V>
-static int launch_red2_bwd(const Red2BwdArgs& a, hipStream_t st) {
-    { KScope ks("k_red2_bwd@launch_red2_bwd", st); hipLaunchKernelGGL(k_red2_bwd<V>, dim3((a.ntiles + 3) / 4), dim3(256), 0, st, a); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    return launch<k_stats_unpack>("k_stats_unpack@gnr_render_chain_fwd_train", st, dim3((ntiles + 3) / 4), dim3(256), 0, (const float*)(tb + t.saveZ), stats_out, P, ntiles);
 }
 
 // Backward of gnr_render_chain_fwd_train: d stats [B,P,65] (mean, var, wbar), d colours [B,P,3] -> gradients of the
@@ -1199,62 +1115,15 @@ extern "C" int gnr_render_chain_bwd(const GnrScene* s, int rn, int dn, const flo
     if (ws_bytes < w.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     char* tb = (char*)tws;
+    auto sec = [tb](size_t off) { return (float*)(tb + off); };
     const int P = rn * dn, ntiles = s->B * ((P + 15) / 16);
-    int blocks = (ntiles + 3) / 4;
-    if (blocks > num_cus()) blocks = num_cus();
-    float* dpart = (float*)(tb + t.dpart);                 // the three parameter stages run this grid: one slot per wavefront
-    if (int rc = poison_partials(dpart, (size_t)blocks * 4 * GP_STRIDE * sizeof(float), st, s->options)) return rc;
-    {
-        Red2BwdArgs a{(const float*)(tb + t.save2), dstats, dcolors, (float*)(tb + t.dS2), P, ntiles};
-        int rc;
-        switch (s->V) {
-            case 2: rc = launch_red2_bwd<2>(a, st); break;
-            case 3: rc = launch_red2_bwd<3>(a, st); break;
-            case 4: rc = launch_red2_bwd<4>(a, st); break;
-            case 5: rc = launch_red2_bwd<5>(a, st); break;
-            case 6: rc = launch_red2_bwd<6>(a, st); break;
-            case 7: rc = launch_red2_bwd<7>(a, st); break;
-            default: rc = launch_red2_bwd<8>(a, st); break;
-        }
-        if (rc) return rc;
-    }
-    {
-        View2BwdArgs a{wl, wb, (const float*)(tb + t.save1), (const float*)(tb + t.saveG), (const float*)(tb + t.dS2),
-                       (float*)(tb + t.dS1), (float*)(tb + t.dG), dpart, s->V, ntiles, (const float*)(tb + t.desc), w.viewp,
-                       P, s->H, s->W};
-        if (int rc = launch_view2_bwd<true>(s, w, a, blocks, st)) return rc;
-    }
-    {
-        HoistBwdArgs a{wb, (const float*)(tb + t.save1), (const float*)(tb + t.saveG), (const float*)(tb + t.dG),
-                       (float*)(tb + t.dS1), dpart, ntiles};
-        int rc;
-        switch (s->V) {
-            case 2: rc = launch_hoist_bwd<2>(a, st); break;
-            case 3: rc = launch_hoist_bwd<3>(a, st); break;
-            case 4: rc = launch_hoist_bwd<4>(a, st); break;
-            case 5: rc = launch_hoist_bwd<5>(a, st); break;
-            case 6: rc = launch_hoist_bwd<6>(a, st); break;
-            case 7: rc = launch_hoist_bwd<7>(a, st); break;
-            default: rc = launch_hoist_bwd<8>(a, st); break;
-        }
-        if (rc) return rc;
-    }
-    {
-        FeatGradBuf fg;
-        const BwdGuard gmax = bwd_guard(s, w, false, 2);
-        if (int rc = feat_grad_begin(s, tb + t.dfeat64, w, (const float*)(tb + t.dS1), (size_t)ntiles * s->V * DS1 * 64, st, &fg, (view1_bins(s) && gmax.run_if) ? &gmax : nullptr)) return rc;
-        View1BwdArgs a{wl, wb, w.feat64, w.viewp, (const float*)(tb + t.desc), (const float*)(tb + t.dS1), fg.buf, dpart,
-                       s->B, s->V, P, s->H, s->W, s->fh, s->fw, ntiles, 1, fg.fx};
-        if (int rc = launch_view1_bwd(s, w, a, fg.fixed, ntiles, tb + t.scatter, false, st)) return rc;
-        if (d_ray_feats || d_img_feats)
-            if (int rc = feat_grad_unpack(s, fg, d_ray_feats, d_img_feats, "k_unpack_feat_grad@gnr_render_chain_bwd", st)) return rc;
-    }
-    {
-        // decoder .. vis_fc2 [0, GEO0_W), rgb_fc + neuray_fc [RGB0_W, VARIANCE) (+ the vis branch behind the blob)
-        const GradRange rg[3] = {{0, can::GEO0_W, 0}, {can::RGB0_W, can::VARIANCE, can::RGB0_W}, {can::TOTAL, can::TOTAL_VIS, can::TOTAL}};
-        if (int rc = launch_grad_reduce(dpart, blocks * 4, GP_STRIDE, d_canonical, rg, s->use_vis ? 3 : 2, st, "k_grad_reduce@gnr_render_chain_bwd")) return rc;
-    }
-    return GNR_OK;
+    if (int rc = chain_partials_begin(s, sec(t.dpart), ntiles, 15, st)) return rc;
+    Red2BwdArgs a{sec(t.save2), dstats, dcolors, sec(t.dS2), P, ntiles};
+    if (int rc = with_views(s->V, [&](auto v) {
+            return launch<k_red2_bwd<decltype(v)::value>>("k_red2_bwd@launch_red2_bwd", st, dim3((ntiles + 3) / 4), dim3(256), 0, a);
+        })) return rc;
+    const BwdWs b{sec(t.desc), sec(t.save1), sec(t.saveG), sec(t.dS2), sec(t.dG), sec(t.dS1), sec(t.dpart), tb + t.dfeat64, tb + t.scatter};
+    return chain_bwd(s, w, BWD_RENDER, b, wl, wb, P, 15, d_canonical, d_ray_feats, d_img_feats, st);
 }
 
 // Forward of the per-ray tail + NeuS alpha + compositing of a training render pass: k_ray<true> on the records the chain of
@@ -1277,29 +1146,10 @@ extern "C" int gnr_render_tail_fwd_train(const GnrScene* s, const GnrRays* q, co
     Workspace w = carve(s, (size_t)q->rn * dn, q->rn, ws);
     if (ws_bytes < w.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const int B = s->B, rn = q->rn;
-    RayArgs r;
-    memset(&r, 0, sizeof(r));
-    r.wpk = wl; r.rec = w.rec; r.desc = (const float*)((char*)tws + t.desc); r.depth = depth; r.colors = out->colors_nr;
-    r.que_dr = q->que_depth_range; r.nrays = B * rn; r.dn = dn; r.rays_per_scene = rn;
-    r.sdf = out->sdf_values; r.alpha = out->alpha_values; r.hit = out->hit_prob_nr; r.pix = out->pixel_colors_nr;
-    r.rdepth = out->render_depth; r.gerr_part = out->sdf_gradient_error ? w.gerr_part : nullptr; r.grad = out->sdf_gradient;
-    r.rmask = out->ray_mask; r.view_num = q->ray_mask_view_num; r.point_num = q->ray_mask_point_num;
+    RayArgs r = render_ray_args(s, q, depth, dn, wl, out, w, (const float*)((char*)tws + t.desc));
     if (fine_depth_out) { r.fine_depth = fine_depth_out; r.fdn = q->fdn; r.fine_u = q->fine_u; }
-    r.range_word = w.range_flag ? w.range_flag + RS_RAY_WATCH : nullptr;
     if (int rc = launch_ray<true>(r, st)) return rc;
-    if (out->sdf_gradient_error) {
-        const int chunk = q->ray_batch_num > 0 ? q->ray_batch_num : rn;
-        { KScope ks("k_gerr_reduce@gnr_render_tail_fwd_train", st); hipLaunchKernelGGL(k_gerr_reduce, dim3(B, (rn + chunk - 1) / chunk), dim3(256), 0, st, w.gerr_part,
-                           out->sdf_gradient_error, rn, dn, chunk); }
-        GNR_HIP(hipGetLastError());
-    }
-    if (out->pixel_colors_gt && q->que_imgs) {
-        { KScope ks("k_pixel_gt@gnr_render_tail_fwd_train", st); hipLaunchKernelGGL(k_pixel_gt, dim3((B * rn + 255) / 256), dim3(256), 0, st, q->que_imgs, q->coords, out->pixel_colors_gt,
-                           rn, s->H, s->W, B); }
-        GNR_HIP(hipGetLastError());
-    }
-    return GNR_OK;
+    return render_ray_epilogue(s, q, out, dn, w, "k_gerr_reduce@gnr_render_tail_fwd_train", "k_pixel_gt@gnr_render_tail_fwd_train", true, nullptr, st);
 }
 
 // Backward of NeuS alpha + compositing for a flat list of rays (k_composite_bwd): see csrc/gnr_bwd.inc.
@@ -1319,11 +1169,8 @@ extern "C" int gnr_composite_bwd(const float* wl, const float* sdf, const float*
     hipStream_t st = (hipStream_t)stream;
     const int blocks = (nrays + 63) / 64;
     CompBwdArgs c{wl, sdf, grad, col, depth, qdir, dpix, ddepth, wgerr, dalpha, dhit, a_out, gamma_out, dcol_out, (double*)scratch, nrays, dn};
-    { KScope ks("k_composite_bwd@gnr_composite_bwd", st); hipLaunchKernelGGL(k_composite_bwd, dim3(blocks), dim3(64), 0, st, c); }
-    GNR_HIP(hipGetLastError());
-    { KScope ks("k_dvar_finish@gnr_composite_bwd", st); hipLaunchKernelGGL(k_dvar_finish, dim3(1), dim3(256), 0, st, (const double*)scratch, blocks, dvar_out); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    if (int rc = launch<k_composite_bwd>("k_composite_bwd@gnr_composite_bwd", st, dim3(blocks), dim3(64), 0, c)) return rc;
+    return launch<k_dvar_finish>("k_dvar_finish@gnr_composite_bwd", st, dim3(1), dim3(256), 0, (const double*)scratch, blocks, dvar_out);
 }
 
 extern "C" int gnr_ray_tail_grad_floats(void) { return tl::TOTAL; }
@@ -1344,23 +1191,16 @@ extern "C" int gnr_ray_tail_dual_bwd(const float* wl, const float* g, const floa
     if (scratch_bytes < gnr_ray_tail_dual_bwd_workspace_bytes()) return fail(GNR_ERR_WORKSPACE, "gnr_ray_tail_dual_bwd: scratch too small");
     hipStream_t st = (hipStream_t)stream;
     RayDualArgs r{wl, g, gd, a, nvalid, gbar, gdbar, (float*)scratch, nrays, dn, 0, 0, 0};
-    r.ray_stride = ((dn * dl::PER + 63) / 64) * 64 + 16;
-    int rpb = 256 / dn;
-    const int fit = (160 * 1024) / (r.ray_stride * (int)sizeof(float));
-    if (rpb > fit) rpb = fit;
+    constexpr size_t MAX_LDS = 160 * 1024;                   // one workgroup per CU
+    const int rpb = pack_rays(dn * dl::PER, dn, (int)MAX_LDS, &r.ray_stride);
     if (rpb < 1) return fail(GNR_ERR_SHAPE, "k_ray_dual_bwd: a ray does not fit the LDS budget");
     r.rays_per_block = rpb;
     r.nblocks = (nrays + rpb - 1) / rpb;
     size_t lds_bytes = (size_t)rpb * r.ray_stride * sizeof(float);
     if (lds_bytes < 2 * 256 * 16 * sizeof(float)) lds_bytes = 2 * 256 * 16 * sizeof(float);
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) {
-        GNR_HIP(hipFuncSetAttribute((const void*)k_ray_dual_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
     const int blocks = r.nblocks < num_cus() ? r.nblocks : num_cus();
     if (int rc = poison_partials(scratch, (size_t)blocks * 4 * tp::STRIDE * sizeof(float), st, options)) return rc;
-    { KScope ks("k_ray_dual_bwd@gnr_ray_tail_dual_bwd", st); hipLaunchKernelGGL(k_ray_dual_bwd, dim3(blocks), dim3(256), lds_bytes, st, r); }
-    GNR_HIP(hipGetLastError());
+    if (int rc = launch<k_ray_dual_bwd, MAX_LDS>("k_ray_dual_bwd@gnr_ray_tail_dual_bwd", st, dim3(blocks), dim3(256), lds_bytes, r)) return rc;
     return launch_tail_reduce((const float*)scratch, blocks * 4, wl, dtail, st);
 }
 
@@ -1376,27 +1216,20 @@ extern "C" int gnr_geo_dual_fwd(const float* canon, const float* stats, const fl
     if (P < 1) return fail(GNR_ERR_SHAPE, "P must be >= 1");
     hipStream_t st = (hipStream_t)stream;
     GeoDualArgs a{canon, stats, pts, gamma, nullptr, nullptr, g, gd, nullptr, nullptr, P, 0, nullptr};
-    if (options & GNR_OPT_GEO_DUAL_FP32) {
-        KScope ks("k_geo_dual_fwd@gnr_geo_dual_fwd", st);
-        hipLaunchKernelGGL(k_geo_dual_fwd, dim3((P + 255) / 256), dim3(256), 0, st, a, (const unsigned*)nullptr);
-    } else {
-        if (!scratch) return fail(GNR_ERR_ARG, "gnr_geo_dual_fwd: null scratch");
-        if (scratch_bytes < gnr_geo_dual_fwd_workspace_bytes()) return fail(GNR_ERR_WORKSPACE, "gnr_geo_dual_fwd: scratch too small");
-        float* frags = (float*)scratch;
-        unsigned* range_word = (unsigned*)((char*)scratch + al256(gdf::TOTAL * sizeof(float)));
-        { KScope ks("k_pack_geo_dual@gnr_geo_dual_fwd", st); hipLaunchKernelGGL(k_pack_geo_dual, dim3(16), dim3(256), 0, st, canon, frags); }
-        GNR_HIP(hipGetLastError());
-        GNR_HIP(hipMemsetAsync(range_word, 0, sizeof(unsigned), st));
-        const int ngroups = (P + 15) / 16;
-        int blocks = (ngroups + 3) / 4;
-        if (blocks > 4 * num_cus()) blocks = 4 * num_cus();
-        { KScope ks("k_geo_dual_fwd@gnr_geo_dual_fwd", st); hipLaunchKernelGGL(k_geo_dual_fwd_mm, dim3(blocks), dim3(256), gdf::W2T * sizeof(float), st, a, (const float*)frags, ngroups, range_word); }
-        GNR_HIP(hipGetLastError());
-        // the fp32 twin: returns at once unless the matrix-core kernel flagged its outputs (a weight or an operand beyond the fp16 range)
-        { KScope ks("k_geo_dual_fwd.fp32_twin", st); hipLaunchKernelGGL(k_geo_dual_fwd, dim3((P + 255) / 256), dim3(256), 0, st, a, (const unsigned*)range_word); }
-    }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    if (options & GNR_OPT_GEO_DUAL_FP32)
+        return launch<k_geo_dual_fwd>("k_geo_dual_fwd@gnr_geo_dual_fwd", st, dim3((P + 255) / 256), dim3(256), 0, a, (const unsigned*)nullptr);
+    if (!scratch) return fail(GNR_ERR_ARG, "gnr_geo_dual_fwd: null scratch");
+    if (scratch_bytes < gnr_geo_dual_fwd_workspace_bytes()) return fail(GNR_ERR_WORKSPACE, "gnr_geo_dual_fwd: scratch too small");
+    float* frags = (float*)scratch;
+    unsigned* range_word = (unsigned*)((char*)scratch + al256(gdf::TOTAL * sizeof(float)));
+    if (int rc = launch<k_pack_geo_dual>("k_pack_geo_dual@gnr_geo_dual_fwd", st, dim3(16), dim3(256), 0, canon, frags)) return rc;
+    GNR_HIP(hipMemsetAsync(range_word, 0, sizeof(unsigned), st));
+    const int ngroups = (P + 15) / 16;
+    int blocks = (ngroups + 3) / 4;
+    if (blocks > 4 * num_cus()) blocks = 4 * num_cus();
+    if (int rc = launch<k_geo_dual_fwd_mm>("k_geo_dual_fwd@gnr_geo_dual_fwd", st, dim3(blocks), dim3(256), gdf::W2T * sizeof(float), a, (const float*)frags, ngroups, range_word)) return rc;
+    // the fp32 twin: returns at once unless the matrix-core kernel flagged its outputs (a weight or an operand beyond the fp16 range)
+    return launch<k_geo_dual_fwd>("k_geo_dual_fwd.fp32_twin", st, dim3((P + 255) / 256), dim3(256), 0, a, (const unsigned*)range_word);
 }
 
 //   gbar, gdbar [P,16] -> dstats [P,66] (overwritten, column 65 = 0); gradients of geometry_fc.{0,2} ACCUMULATED into
@@ -1419,34 +1252,27 @@ extern "C" int gnr_geo_dual_bwd(const float* canon, const float* stats, const fl
     float* dpart = (float*)scratch;                          // partial geometry_fc gradients first, the per-point adjoints behind them
     GeoDualArgs a{canon, stats, pts, gamma, gbar, gdbar, nullptr, nullptr, dstats, dpart, P, (P + gd2::NT - 1) / gd2::NT,
                   (float*)((char*)scratch + geo_dual_part_bytes())};
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) {
-        GNR_HIP(hipFuncSetAttribute((const void*)k_geo_dual_bwd_gemm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(gd2::TOTAL * sizeof(float))));
-        GNR_HIP(hipFuncSetAttribute((const void*)k_geo_dual_bwd_pts_mm, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(gdf::TOTAL * sizeof(float))));
-    }
+    const dim3 pgrid((P + 255) / 256);                       // k_geo_dual_bwd_pts: one lane per point
     if (!(options & GNR_OPT_GEO_DUAL_FP32)) {
+        constexpr size_t PTS_LDS = gdf::TOTAL * sizeof(float);
         float* frags = (float*)((char*)scratch + geo_dual_part_bytes() + al256((size_t)P * gd2::YCOLS * sizeof(float)));
-        { KScope ks("k_pack_geo_dual@gnr_geo_dual_bwd", st); hipLaunchKernelGGL(k_pack_geo_dual, dim3(16), dim3(256), 0, st, canon, frags); }
-        GNR_HIP(hipGetLastError());
+        if (int rc = launch<k_pack_geo_dual>("k_pack_geo_dual@gnr_geo_dual_bwd", st, dim3(16), dim3(256), 0, canon, frags)) return rc;
         const int ngroups = (P + 15) / 16;
         int pblocks = (ngroups + 3) / 4;
         if (pblocks > 2 * num_cus()) pblocks = 2 * num_cus();
         unsigned* range_word = (unsigned*)((char*)frags + al256(gdf::TOTAL * sizeof(float)));
         GNR_HIP(hipMemsetAsync(range_word, 0, sizeof(unsigned), st));
-        { KScope ks("k_geo_dual_bwd_pts@gnr_geo_dual_bwd", st); hipLaunchKernelGGL(k_geo_dual_bwd_pts_mm, dim3(pblocks), dim3(256), gdf::TOTAL * sizeof(float), st, a, (const float*)frags, ngroups, range_word); }
-        GNR_HIP(hipGetLastError());
+        if (int rc = launch<k_geo_dual_bwd_pts_mm, PTS_LDS>("k_geo_dual_bwd_pts@gnr_geo_dual_bwd", st, dim3(pblocks), dim3(256), PTS_LDS, a, (const float*)frags, ngroups, range_word)) return rc;
         // the fp32 twin: returns at once unless the matrix-core kernel flagged its outputs (a weight beyond the fp16 range)
-        { KScope ks("k_geo_dual_bwd_pts.fp32_twin", st); hipLaunchKernelGGL(k_geo_dual_bwd_pts, dim3((P + 255) / 256), dim3(256), 0, st, a, (const unsigned*)range_word); }
+        if (int rc = launch<k_geo_dual_bwd_pts>("k_geo_dual_bwd_pts.fp32_twin", st, pgrid, dim3(256), 0, a, (const unsigned*)range_word)) return rc;
     } else {
-        KScope ks("k_geo_dual_bwd_pts@gnr_geo_dual_bwd", st);
-        hipLaunchKernelGGL(k_geo_dual_bwd_pts, dim3((P + 255) / 256), dim3(256), 0, st, a, (const unsigned*)nullptr);
+        if (int rc = launch<k_geo_dual_bwd_pts>("k_geo_dual_bwd_pts@gnr_geo_dual_bwd", st, pgrid, dim3(256), 0, a, (const unsigned*)nullptr)) return rc;
     }
-    GNR_HIP(hipGetLastError());
     const int blocks = a.nblocks < 2 * num_cus() ? a.nblocks : 2 * num_cus();
     const int slots = blocks * gd2::NW;
     if (int rc = poison_partials(dpart, (size_t)slots * GD_STRIDE * sizeof(float), st, options)) return rc;
-    { KScope ks("k_geo_dual_bwd_gemm@gnr_geo_dual_bwd", st); hipLaunchKernelGGL(k_geo_dual_bwd_gemm, dim3(blocks), dim3(64 * gd2::NW), gd2::TOTAL * sizeof(float), st, a); }
-    GNR_HIP(hipGetLastError());
+    constexpr size_t GEMM_LDS = gd2::TOTAL * sizeof(float);
+    if (int rc = launch<k_geo_dual_bwd_gemm, GEMM_LDS>("k_geo_dual_bwd_gemm@gnr_geo_dual_bwd", st, dim3(blocks), dim3(64 * gd2::NW), GEMM_LDS, a)) return rc;
     const GradRange rg[1] = {{0, can::WQ - can::GEO0_W, can::GEO0_W}};
     return launch_grad_reduce(dpart, slots, GD_STRIDE, d_canonical, rg, 1, st, "k_grad_reduce@gnr_geo_dual_bwd");
 }
@@ -1518,11 +1344,7 @@ __global__ __launch_bounds__(256) void k_fill_lds(unsigned pattern, int words, u
 }  // namespace gnr
 extern "C" int gnr_debug_fill_lds(unsigned pattern, void* stream) {
     constexpr int BYTES = 160 * 1024 - 256;
-    static std::atomic<unsigned long long> attr_done{0};
-    if (attr_needed(attr_done)) GNR_HIP(hipFuncSetAttribute((const void*)k_fill_lds, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES));
-    hipLaunchKernelGGL(k_fill_lds, dim3(1024), dim3(256), BYTES, (hipStream_t)stream, pattern, BYTES / 4, (unsigned*)nullptr);
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
+    return launch<k_fill_lds, BYTES>(nullptr, (hipStream_t)stream, dim3(1024), dim3(256), BYTES, pattern, BYTES / 4, (unsigned*)nullptr);   // (no timing label)
 }
 
 // the two calls bench.py round 1 used: average duration of the volume k_chain launches
