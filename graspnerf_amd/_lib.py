@@ -114,6 +114,8 @@ def lib():
     L.gnr_debug_sample_order.restype = C.c_int
     L.gnr_sample_order_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.gnr_sample_order_host.restype = C.c_int
+    L.gnr_sample_order_host_chunked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.gnr_sample_order_host_chunked.restype = C.c_int
     L.gnr_sample_order_offsets.argtypes = [C.POINTER(GnrScene), C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.gnr_sample_order_offsets.restype = C.c_int
     L.gnr_render_rays_fwd.argtypes = [C.POINTER(GnrScene), C.POINTER(GnrRays), C.c_void_p, C.c_void_p,
@@ -241,7 +243,7 @@ def lib():
 
 EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pack_weights', 'gnr_pack_vis_decoder', 'gnr_pack_vis_decoder_bwd', 'gnr_canonical_vis_floats', 'gnr_pack_weights_device', 'gnr_pack_weights_bwd_device', 'gnr_pack_vis_decoder_device', 'gnr_pack_vis_decoder_bwd_device', 'gnr_layout_offset', 'gnr_workspace_bytes',
             'gnr_prepare', 'gnr_range_status', 'gnr_status_words_offset', 'gnr_sample_volume_fwd', 'gnr_debug_volume_chain', 'gnr_depth_mean_fwd', 'gnr_merge_depths', 'gnr_render_by_depth_fwd', 'gnr_render_rays_fwd',
-            'gnr_debug_render_by_depth_perm', 'gnr_debug_sample_order', 'gnr_sample_order_host', 'gnr_sample_order_offsets',
+            'gnr_debug_render_by_depth_perm', 'gnr_debug_sample_order', 'gnr_sample_order_host', 'gnr_sample_order_host_chunked', 'gnr_sample_order_offsets',
             'gnr_dominant_kernel_name', 'gnr_last_error', 'gnr_time_chain_kernel', 'gnr_head_canonical_floats',
             'gnr_head_packed_floats', 'gnr_pack_grasp_head', 'gnr_grasp_head_workspace_bytes', 'gnr_grasp_head_fwd',
             'gnr_head_last_error', 'gnr_chain_timing_begin', 'gnr_chain_timing_end', 'gnr_timing_begin', 'gnr_timing_begin_only', 'gnr_timing_end', 'gnr_grasp_select_workspace_bytes',

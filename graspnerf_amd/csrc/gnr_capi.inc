@@ -586,16 +586,18 @@ static int order_rays(const GnrScene* s, const GnrRays* q, Workspace& w, hipStre
 // View-mask order of a render pass's samples (csrc/gnr_sample_order.h) behind its k_points_rays: -> w.sample_perm, or null = natural order:
 //   GNR_OPT_SAMPLE_ORDER_NATURAL;  more than MAX_SORT_SAMPLES samples per scene;  a launch of fewer than SAMPLE_ORDER_MIN_TILES_PER_SLOT tiles
 //   per wavefront slot of the device.  Measured at 512 rays x 40 (0.625 B tiles per slot; profiles/sample_order_ab.json): the two chain launches
-//   of a step gain 0.00 / 0.04 / 0.04 / 0.07 / 0.22 ms at B = 1 / 2 / 4 / 8 / 32, the two sorts cost 0.09 ms at every B (one workgroup per
-//   scene, 43 us a launch): the step loses 0.05 ms at B = 4, 0.02 at B = 8 and wins 0.10 at B = 32; break-even near B = 12 = 7.5 tiles per slot.
+//   of a step gain 0.00 / 0.04 / 0.04 / 0.07 / 0.22 ms at B = 1 / 2 / 4 / 8 / 32, and the two sorts of the EARLIER kernel (one workgroup per
+//   scene, 43 us a launch) cost 0.09 ms at every B: the step lost 0.05 ms at B = 4, 0.02 at B = 8 and won 0.10 at B = 32; break-even near
+//   B = 12 = 7.5 tiles per slot.  k_sample_order now runs one workgroup per SO_CHUNK samples; its break-even has NOT been measured yet
+//   (profiles/sample_place_ab.json), so the constant stays at the last measured one.  Not below 1: less than a tile per slot has no order to gain.
 constexpr int SAMPLE_ORDER_MIN_TILES_PER_SLOT = 8;
 static bool sample_order_wanted(const GnrScene* s, const Workspace& w, int P) {
     if (opt(s, GNR_OPT_SAMPLE_ORDER_NATURAL) || !w.sample_perm || !w.sample_keys || P > MAX_SORT_SAMPLES) return false;
     const long ntiles = (long)s->B * ((P + 15) / 16), slots = (long)num_cus() * (GNR_CHAIN_THREADS / 64);
     return ntiles >= SAMPLE_ORDER_MIN_TILES_PER_SLOT * slots;
 }
-static int launch_sample_order(const unsigned char* keys, int* perm, int B, int P, int nkeys, hipStream_t st) {
-    return launch<k_sample_order>("k_sample_order@render_pass", st, dim3(B), dim3(1024), 0, keys, perm, P, nkeys);
+static int launch_sample_order(const unsigned char* keys, int* perm, int B, int P, hipStream_t st) {
+    return launch<k_sample_order>("k_sample_order@render_pass", st, dim3((P + SO_CHUNK - 1) / SO_CHUNK, B), dim3(SO_THREADS), 0, keys, perm, P);
 }
 // The per-ray kernel's arguments for a render pass (inference: render_pass; training: gnr_render_tail_fwd_train) on the records the pass's
 // chain left in the workspace; desc = the pass's point descriptors.  The caller adds the resampler's outputs and the ray order.
@@ -637,7 +639,7 @@ static int render_pass(const GnrScene* s, const GnrRays* q, const float* depth, 
                                        q->que_depth_range, depth, w.desc, rn, dn, B, perm, gen_depth ? const_cast<float*>(depth) : nullptr,     // gen_depth: the coarse pass's depths are generated here, into `depth`
                                        ordered ? w.sample_keys : nullptr, w.viewp, s->V, s->H, s->W)) return rc;
     if (ordered)
-        if (int rc = launch_sample_order(w.sample_keys, w.sample_perm, B, P, 1 << s->V, st)) return rc;
+        if (int rc = launch_sample_order(w.sample_keys, w.sample_perm, B, P, st)) return rc;
     ChainArgs a{wl, w.feat64, s->imgs, w.viewp, w.desc, w.rec, out->colors_nr, out->view_mask, nullptr,
                 B, P, s->H, s->W, s->fh, s->fw, 0};
     wire_chain(a, s, w, range_slot);                       // watch word of this pass (RS_COARSE: coarse / by-depth, RS_FINE)
@@ -700,7 +702,7 @@ extern "C" int gnr_debug_render_by_depth_perm(const GnrScene* s, const GnrRays* 
 extern "C" int gnr_debug_sample_order(const unsigned char* keys, int B, int P, int* perm, void* stream) {
     if (!keys || !perm) return fail(GNR_ERR_ARG, "gnr_debug_sample_order: null pointer");
     if (B < 1 || P < 1 || P > MAX_SORT_SAMPLES) return fail(GNR_ERR_SHAPE, "gnr_debug_sample_order: 1 <= P <= 2^18 samples per scene");
-    return launch_sample_order(keys, perm, B, P, 256, (hipStream_t)stream);
+    return launch_sample_order(keys, perm, B, P, (hipStream_t)stream);
 }
 extern "C" int gnr_sample_order_host(const unsigned char* keys, int P, int* perm_out) {
     if (!keys || !perm_out) return fail(GNR_ERR_ARG, "gnr_sample_order_host: null pointer");
@@ -712,6 +714,20 @@ extern "C" int gnr_sample_order_host(const unsigned char* keys, int P, int* perm
         for (int k2 = 0; k2 < 256; ++k2) if (sorder::key_before(k2, k)) start[k] += hist[k2];
     }
     for (int i = 0; i < P; ++i) perm_out[sorder::slot_of(start[keys[i]]++, P)] = i;
+    return GNR_OK;
+}
+// gnr_sample_order_host_chunked: the placement by chunks of `chunk` samples (csrc/gnr_sample_order.h) as k_sample_order runs it, one chunk
+// after the other: every chunk counts the scene's keys again -- in front of it and from it on -- and places its samples from those counts.
+extern "C" int gnr_sample_order_host_chunked(const unsigned char* keys, int P, int chunk, int* perm_out) {
+    if (!keys || !perm_out) return fail(GNR_ERR_ARG, "gnr_sample_order_host_chunked: null pointer");
+    if (P < 1 || chunk < 1) return fail(GNR_ERR_SHAPE, "gnr_sample_order_host_chunked: P and chunk must be positive");
+    for (int c0 = 0; c0 < P; c0 += chunk) {
+        int before[sorder::KEYS] = {0}, rest[sorder::KEYS] = {0}, by_rank[sorder::KEYS], scan[sorder::KEYS], in_chunk[sorder::KEYS] = {0};
+        for (int i = 0; i < P; ++i) ++(i < c0 ? before : rest)[keys[i]];
+        for (int k = 0; k < sorder::KEYS; ++k) by_rank[sorder::key_rank(k)] = before[k] + rest[k];
+        for (int r = 0, run = 0; r < sorder::KEYS; ++r) { scan[r] = run; run += by_rank[r]; }
+        for (int i = c0; i < P && i - c0 < chunk; ++i) perm_out[sorder::slot_of(sorder::chunk_pos(scan, before, keys[i], in_chunk[keys[i]]++), P)] = i;
+    }
     return GNR_OK;
 }
 extern "C" int gnr_sample_order_offsets(const GnrScene* s, int rn, int dn_max, size_t* keys_off, size_t* perm_off) {

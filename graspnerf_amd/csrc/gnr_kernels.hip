@@ -780,68 +780,122 @@ DEV unsigned view_mask_key(const float* __restrict__ viewp_b, const float (&p)[3
     }
     return k;
 }
-// perm[b][sorder::slot_of(position of sample i in the stable key sort)] = i.  One workgroup of 16 wavefronts per scene: wavefront w owns the
-// contiguous segment w of the samples; per-(wavefront, key) counts -> exclusive offsets (groups in sorder::key_before order, then wavefront
-// order), then every wavefront walks its segment 64 samples at a time and ranks the lanes of equal key by lane id.  Integer counts and fixed
-// ownership only: the same keys give the same permutation.  The keys of SO_DEPTH steps are loaded together (a step's rank depends on the step
-// before it, and with one load per step the launch took 52 us, all of it load latency).  nkeys: every key is below it (1 << V; 256 = any byte).
-constexpr int MAX_SORT_SAMPLES = 1 << 18;       // per scene; above it the passes keep the natural order (one workgroup per scene: the sort's time grows with P)
-constexpr int SO_DEPTH = 16;
-__global__ __launch_bounds__(1024) void k_sample_order(const unsigned char* __restrict__ keys, int* __restrict__ perm, int P, int nkeys) {
-    __shared__ int hist[256];
-    __shared__ int wbase[16][256];
+// perm[b][sorder::slot_of(position of sample i in the stable key sort)] = i, placed by chunks (csrc/gnr_sample_order.h "the placement by
+// chunks"): grid (chunks of a scene, B); workgroup (c, b) places the SO_CHUNK samples of scene b from c * SO_CHUNK on and takes everything it
+// needs from the scene's keys.  It counts ALL of them (P bytes out of the L2, as aligned 16-byte words, SO_LOADS words per thread loaded
+// before the first is counted; a run of equal keys inside a word is one LDS add) into cnt[k] (samples in front of the chunk) and cnt[256 + k]
+// (from the chunk on), so that cnt[k] + cnt[256 + k] is the scene's histogram.  Wavefront w owns the contiguous segment w of the chunk, SO_STEPS
+// times 64 samples: the rank of a sample among the equal keys of its chunk is its rank among the equal lanes of its step (8 ballots), plus what
+// the steps before it added to the wavefront's count of the key, plus the counts of the wavefronts before it.  No workgroup waits for another,
+// nothing is zeroed or carried between launches, no global atomics; integer counts and fixed ownership only: the same keys give the same
+// permutation.  Always 256 bins (any byte is a key).  An aligned word that holds a byte of the scene lies in that byte's page: the bytes of
+// the first and last word outside [0, P) are read and not counted.
+// Measured alone between the library's event brackets (profiles/sample_place_ab.json; the kernel it replaces, one workgroup per scene, read
+// 55-59 us at every B): 11-14 us per launch at P = 20 480 for B = 1 .. 32.  What a workgroup counts grows with P, and so does the number of
+// workgroups: at P = 2^18, B = 1 (64 workgroups, each counting 256 KB of keys) the launch reads 22-54 us against 345-396 us of the one
+// workgroup per scene, so MAX_SORT_SAMPLES stays where it was and there is no second form for large P.
+constexpr int MAX_SORT_SAMPLES = 1 << 18;       // per scene; above it the passes keep the natural order (every chunk reads all the keys of its scene)
+constexpr int SO_THREADS = 1024;
+constexpr int SO_STEPS = 4;
+constexpr int SO_CHUNK = SO_THREADS * SO_STEPS;
+constexpr int SO_LOADS = 4;
+// the keys of one word: i0 = sample index of its first byte (below 0 in the scene's first word, the last word may reach past P)
+DEV void so_count_word(const uint4& q, int i0, int c0, int P, int* cnt) {
+    const unsigned d[4] = {q.x, q.y, q.z, q.w};
+    // bit j: byte j opens a run -- byte 0, a key other than the byte before it, the first sample of the scene, of the chunk, behind the scene
+    unsigned starts = 0x10001u;                                // (bit 16 ends the last run)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const unsigned t = d[n] ^ ((d[n] << 8) | (n ? d[n - 1] >> 24 : 0u));       // byte j: key j xor key j - 1
+        const unsigned m = ((((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u) >> 7;   // bit 8 j: byte j of t is not zero
+        starts |= (((m * 0x00204081u) >> 21) & 15u) << (4 * n);                    // bits 0, 8, 16, 24 -> bits 21 .. 24
+    }
+    const int edge[3] = {-i0, c0 - i0, P - i0};
+#pragma unroll
+    for (int e = 0; e < 3; ++e) starts |= (unsigned)edge[e] < 16u ? 1u << edge[e] : 0u;
+    for (int j = 0; j < 16;) {                                 // j = the lowest bit of starts
+        starts &= starts - 1u;
+        const int jn = __builtin_ctz(starts), i = i0 + j;
+        const unsigned w = j < 8 ? (j < 4 ? d[0] : d[1]) : (j < 12 ? d[2] : d[3]);
+        if ((unsigned)i < (unsigned)P) atomicAdd(&cnt[(int)((w >> (8 * (j & 3))) & 255u) + (i >= c0 ? sorder::KEYS : 0)], jn - j);
+        j = jn;
+    }
+}
+__global__ __launch_bounds__(SO_THREADS) void k_sample_order(const unsigned char* __restrict__ keys, int* __restrict__ perm, int P) {
+    constexpr int WAVES = SO_THREADS / 64, SCAN_WAVES = sorder::KEYS / 64;
+    static_assert(SO_THREADS % 64 == 0 && SO_THREADS >= sorder::KEYS && SO_THREADS <= 1024, "one thread per key");
+    __shared__ int cnt[2 * sorder::KEYS];
+    __shared__ int wbase[WAVES][sorder::KEYS];
+    __shared__ int scan[sorder::KEYS];
+    __shared__ int wtot[SCAN_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned char* kb = keys + (size_t)blockIdx.x * P;
-    int* pb = perm + (size_t)blockIdx.x * P;
-    for (int i = tid; i < 16 * 256; i += 1024) (&wbase[0][0])[i] = 0;
+    const unsigned char* kb = keys + (size_t)blockIdx.y * P;
+    int* pb = perm + (size_t)blockIdx.y * P;
+    const int c0 = blockIdx.x * SO_CHUNK;
+    const int s0 = c0 + wave * (64 * SO_STEPS) + lane;          // this thread's samples: s0 + 64 u
+    int kk[SO_STEPS];
+#pragma unroll
+    for (int u = 0; u < SO_STEPS; ++u) kk[u] = s0 + 64 * u < P ? (int)kb[s0 + 64 * u] : -1;
+    const int shift = (int)((size_t)kb & 15);                   // the scene's first key is byte `shift` of word 0
+    const uint4* wp = (const uint4*)(kb - shift);
+    const int nwords = (shift + P + 15) >> 4;
+    uint4 q[SO_LOADS];
+#pragma unroll
+    for (int u = 0; u < SO_LOADS; ++u) { const int w = tid + u * SO_THREADS; q[u] = w < nwords ? wp[w] : make_uint4(0, 0, 0, 0); }
+    for (int n = tid; n < 2 * sorder::KEYS; n += SO_THREADS) cnt[n] = 0;
+    for (int n = tid; n < WAVES * sorder::KEYS; n += SO_THREADS) (&wbase[0][0])[n] = 0;
     __syncthreads();
-    const int seg = ((P + 16 * 64 - 1) / (16 * 64)) * 64;
-    const int s0 = min(P, wave * seg), s1 = min(P, s0 + seg);
-    for (int i0 = s0; i0 < s1; i0 += 64 * SO_DEPTH) {
-        int kk[SO_DEPTH];
+    for (int w0 = tid; w0 < nwords; w0 += SO_LOADS * SO_THREADS) {
+        if (w0 != tid) {
 #pragma unroll
-        for (int u = 0; u < SO_DEPTH; ++u) { const int i = i0 + u * 64 + lane; kk[u] = i < s1 ? (int)kb[i] : -1; }
-#pragma unroll
-        for (int u = 0; u < SO_DEPTH; ++u) if (kk[u] >= 0) atomicAdd(&wbase[wave][kk[u]], 1);
-    }
-    __syncthreads();
-    if (tid < nkeys) {
-        int t = 0;
-        for (int w = 0; w < 16; ++w) t += wbase[w][tid];
-        hist[tid] = t;
-    }
-    __syncthreads();
-    if (tid < nkeys) {
-        int run = 0;
-        for (int k2 = 0; k2 < nkeys; ++k2) if (sorder::key_before(k2, tid)) run += hist[k2];
-        for (int w = 0; w < 16; ++w) { const int c = wbase[w][tid]; wbase[w][tid] = run; run += c; }
-    }
-    __syncthreads();
-    volatile int* base = wbase[wave];
-    for (int i0 = s0; i0 < s1; i0 += 64 * SO_DEPTH) {
-        int kk[SO_DEPTH];
-#pragma unroll
-        for (int u = 0; u < SO_DEPTH; ++u) { const int i = i0 + u * 64 + lane; kk[u] = i < s1 ? (int)kb[i] : -1; }
-#pragma unroll
-        for (int u = 0; u < SO_DEPTH; ++u) {
-            if (i0 + u * 64 >= s1) break;                      // wave-uniform
-            const int k = kk[u];
-            const bool ok = k >= 0;
-            unsigned long long same = __ballot(ok);            // -> the lanes of this step that hold the same key
-#pragma unroll
-            for (int bit = 0; bit < 8; ++bit) {
-                const bool on = (k >> bit) & 1;
-                const unsigned long long bb = __ballot(on);
-                same &= on ? bb : ~bb;
-            }
-            const int rank = __popcll(same & ((1ull << lane) - 1ull));
-            const int pos = ok ? base[k] + rank : 0;
-            __builtin_amdgcn_wave_barrier();
-            if (ok && rank == 0) base[k] = pos + __popcll(same);
-            __builtin_amdgcn_wave_barrier();
-            if (ok) pb[sorder::slot_of(pos, P)] = i0 + u * 64 + lane;
+            for (int u = 0; u < SO_LOADS; ++u) { const int w = w0 + u * SO_THREADS; q[u] = w < nwords ? wp[w] : make_uint4(0, 0, 0, 0); }
         }
+#pragma unroll
+        for (int u = 0; u < SO_LOADS; ++u) { const int w = w0 + u * SO_THREADS; if (w < nwords) so_count_word(q[u], w * 16 - shift, c0, P, cnt); }
     }
+    int rank[SO_STEPS];                                         // among the equal keys of the wavefront's segment
+#pragma unroll
+    for (int u = 0; u < SO_STEPS; ++u) {
+        const int k = kk[u];
+        const bool ok = k >= 0;
+        unsigned long long same = __ballot(ok);                // -> the lanes of this step that hold the same key
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const bool on = (k >> bit) & 1;
+            const unsigned long long bb = __ballot(on);
+            same &= on ? bb : ~bb;
+        }
+        const int r = __popcll(same & ((1ull << lane) - 1ull));
+        int seen = 0;                                          // samples of the key in the steps before (the first equal lane asks for all)
+        if (ok && r == 0) seen = atomicAdd(&wbase[wave][k], __popcll(same));
+        rank[u] = r + __shfl(seen, ok ? __builtin_ctzll(same) : lane);
+    }
+    __syncthreads();
+    // scan[r] = start of the group of the key of rank r: the histogram in rank order, then its exclusive prefix (wavefront scans + their totals)
+    if (tid < sorder::KEYS) scan[sorder::key_rank(tid)] = cnt[tid] + cnt[sorder::KEYS + tid];
+    __syncthreads();
+    int h = 0, incl = 0;
+    if (tid < sorder::KEYS) {
+        h = incl = scan[tid];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+        if (lane == 63) wtot[wave] = incl;
+    }
+    __syncthreads();
+    if (tid < sorder::KEYS) {
+        int off = 0;
+        for (int w = 0; w < wave; ++w) off += wtot[w];
+        scan[tid] = off + incl - h;
+    }
+    __syncthreads();
+    if (tid < sorder::KEYS) {                                   // wbase[w][k]: position of the first sample of key k of the chunk's wavefront w
+        int run = sorder::chunk_pos(scan, cnt, tid, 0);
+        for (int w = 0; w < WAVES; ++w) { const int c = wbase[w][tid]; wbase[w][tid] = run; run += c; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < SO_STEPS; ++u)
+        if (kk[u] >= 0) pb[sorder::slot_of(wbase[wave][kk[u]] + rank[u], P)] = s0 + 64 * u;
 }
 
 #ifndef GNR_DYN_TILES

@@ -27,13 +27,38 @@ namespace sorder {
 constexpr int STRIPES = 8;
 constexpr int TILE = 16;
 
-GNR_SO_HD inline int popcount8(int k) { k = (k & 0x55) + ((k >> 1) & 0x55); k = (k & 0x33) + ((k >> 2) & 0x33); return (k & 0x0f) + (k >> 4); }
+GNR_SO_HD constexpr int popcount8(int k) { k = (k & 0x55) + ((k >> 1) & 0x55); k = (k & 0x33) + ((k >> 2) & 0x33); return (k & 0x0f) + (k >> 4); }
 
 // does the group of key a come before the group of key b?
-GNR_SO_HD inline bool key_before(int a, int b) {
+GNR_SO_HD constexpr bool key_before(int a, int b) {
     const int pa = popcount8(a), pb = popcount8(b);
     return pa != pb ? pa > pb : a > b;
 }
+
+// ---- the placement by chunks (k_sample_order and its serial host twin gnr_sample_order_host_chunked) ----
+// A scene's samples are cut into chunks of `chunk` consecutive samples, and a chunk places its samples from the keys alone:
+//   hist[k]    samples of key k in the scene,                      before[k]  those of them in front of the chunk,
+//   by_rank[r] = hist[key of rank r], rank = key_rank() = the key's place in the key_before() order,
+//   scan[r]    = by_rank[0] + .. + by_rank[r - 1] = start of the group of that key in the sorted sequence.
+// Sample i of key k with `rank_in_chunk` samples of key k in front of it inside its chunk stands at chunk_pos() of the sorted sequence
+// (= start[k] + #{ j < i : key_j == k }, what gnr_sample_order_host counts one sample after the other), and in slot slot_of() of it.
+constexpr int KEYS = 256;
+struct KeyRanks { unsigned char r[KEYS]; };
+constexpr KeyRanks make_key_ranks() {
+    KeyRanks t{};
+    for (int k = 0; k < KEYS; ++k) {
+        int n = 0;
+        for (int k2 = 0; k2 < KEYS; ++k2) n += key_before(k2, k) ? 1 : 0;
+        t.r[k] = (unsigned char)n;
+    }
+    return t;
+}
+// number of keys whose group comes before the group of key k (a bijection of 0..255: key_before is a strict total order)
+GNR_SO_HD inline int key_rank(int k) {
+    constexpr KeyRanks t = make_key_ranks();
+    return t.r[k];
+}
+GNR_SO_HD inline int chunk_pos(const int* scan, const int* before, int k, int rank_in_chunk) { return scan[key_rank(k)] + before[k] + rank_in_chunk; }
 
 // tiles of stripe s of a scene with tps tiles: the sorted groups s, s + STRIPES, s + 2 STRIPES, ...
 GNR_SO_HD inline int stripe_tiles(int tps, int s) { return (tps - s + STRIPES - 1) / STRIPES; }

@@ -246,19 +246,26 @@ int gnr_render_rays_fwd(const GnrScene* scene, const GnrRays* rays, const float*
  * so that gnr_workspace_bytes grows with rn * dn_max).
  * A pass keeps the natural order when
  *   - GNR_OPT_SAMPLE_ORDER_NATURAL is set;
- *   - a scene has more than 2^18 samples in the pass (one workgroup sorts a scene);
+ *   - a scene has more than 2^18 samples in the pass (every workgroup of the placement counts all the keys of its scene);
  *   - the chain launch has fewer than 8 tiles per wavefront slot of the device (B * ceil(rn*dn/16) < 8 * 8 * CUs = 16 384 on MI355X; at
  *     512 rays x 40 samples: fewer than 13 scenes).  A launch of a tile or two per slot lasts as long as its longest tiles in any order
- *     (B = 1: no gain at all), and the sort costs 43 us per pass at any B: measured at B = 1, 2, 4, 8, 32 the step loses 0.05 ms at
- *     B = 4, 0.02 ms at B = 8 and wins 0.10 ms at B = 32, break-even near 7.5 tiles per slot (profiles/sample_order_ab.json).
+ *     (B = 1: no gain at all).  The 8 is the break-even of the EARLIER sort (one workgroup per scene, 43 us per pass at any B: measured
+ *     at B = 1, 2, 4, 8, 32 the step lost 0.05 ms at B = 4, 0.02 ms at B = 8 and won 0.10 ms at B = 32, profiles/sample_order_ab.json).
+ *     The placement now runs one workgroup per 4096 samples (csrc/gnr_kernels.hip k_sample_order); its break-even has NOT been measured
+ *     yet (profiles/sample_place_ab.json says what was and was not), so the threshold stays where the last measurement put it.
  * Test tooling: gnr_debug_render_by_depth_perm = gnr_render_by_depth_fwd with a caller-given sample_perm [B][rn*dn] (int32, device; every
  * row a permutation of 0 .. rn*dn-1; entries are clamped into the scene); gnr_debug_sample_order = the device sort alone, keys [B][P] ->
- * perm [B][P] (P <= 2^18); gnr_sample_order_host = the same permutation of one scene computed on the host (no device work);
+ * perm [B][P] (P <= 2^18; the kernel loads the keys as aligned 16-byte words: when `keys` or `keys + B * P` is not 16-byte aligned it READS,
+ * and does not use, up to 15 bytes in front of / behind the array, inside the aligned word that holds the array's first / last byte and
+ * so inside that byte's page); gnr_sample_order_host = the same permutation of one scene computed on the host (no device work);
+ * gnr_sample_order_host_chunked = the same again, computed the way the kernel does: chunk by chunk, every chunk of `chunk` samples from
+ * the scene's histogram, the histogram of the keys in front of the chunk and the rank inside the chunk (csrc/gnr_sample_order.h);
  * gnr_sample_order_offsets = byte offsets of the last pass's keys / permutation in a workspace carved for (rn, dn_max). */
 int gnr_debug_render_by_depth_perm(const GnrScene* scene, const GnrRays* rays, const float* depth, int dn, const float* level_weights,
                                    GnrRenderOut* out, const int* sample_perm, void* workspace, size_t workspace_bytes, void* stream);
 int gnr_debug_sample_order(const unsigned char* keys, int B, int P, int* perm, void* stream);
 int gnr_sample_order_host(const unsigned char* keys_host, int P, int* perm_out_host);
+int gnr_sample_order_host_chunked(const unsigned char* keys_host, int P, int chunk, int* perm_out_host);
 int gnr_sample_order_offsets(const GnrScene* scene, int rn, int dn_max, size_t* keys_offset, size_t* perm_offset);
 
 /* fine_depth_use_all under training (renderer.py:145-146: the fine pass renders torch.sort(torch.cat([coarse depths, resampled depths])))
