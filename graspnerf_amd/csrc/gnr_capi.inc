@@ -1293,7 +1293,10 @@ extern "C" int gnr_geo_dual_bwd(const float* canon, const float* stats, const fl
     return launch_grad_reduce(dpart, slots, GD_STRIDE, d_canonical, rg, 1, st, "k_grad_reduce@gnr_geo_dual_bwd");
 }
 
-// the same bracket for the library's other translation units (gnr_head.hip, gnr_post.hip): not part of the public ABI
+// gnr_last_error's text for an entry point that lives in another translation unit (gnr_metrics.hip): not part of the public ABI
+extern "C" int gnr_internal_fail(int code, const char* what, int hip_error) { return fail(code, what, (hipError_t)hip_error); }
+
+// the same bracket for the library's other translation units (gnr_head.hip, gnr_post.hip, gnr_metrics.hip): not part of the public ABI
 extern "C" int gnr_internal_timing_open(const char* label, void* stream) {
     KScope ks(label, (hipStream_t)stream);                    // claims a slot and records the opening event
     const int idx = ks.idx;

@@ -27,6 +27,13 @@ def load_model(cfg, checkpoint=None, device='cuda:0', depth_coords_rng='device')
     return net.to(device).eval()
 
 
+def full_frame_coords(h, w):
+    """Pixel coordinates (x, y) of every pixel of an h x w query frame, row-major, float32 [1,h*w,2] (build_render_imgs_info,
+    utils/imgs_info.py:126-135): the query view of the planner's forward and of a validation scene."""
+    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
+    return np.stack([xs, ys], -1).reshape(1, -1, 2).astype(np.float32)
+
+
 def core(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8),
          bbox3d=((-0.15, -0.15, -0.05), (0.15, 0.15, 0.25)), que_id=0):
     """images [V,3,H,W] in [0,1]; extrinsics [V,3|4,4] world->camera; intrinsics [V,3,3]; H, W multiples of 32.
@@ -38,9 +45,8 @@ def core(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8),
     ext = np.asarray(extrinsics, np.float32)[:, :3, :]
     dr = np.broadcast_to(np.asarray(depth_range, np.float32), (V, 2)) if np.ndim(depth_range) == 1 else np.asarray(depth_range, np.float32)
     ref = {'imgs': t(images), 'poses': t(ext), 'Ks': t(intrinsics), 'depth_range': t(dr), 'bbox3d': t(bbox3d)}
-    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')               # imgs_info.py:126-135
     que = {'poses': t(ext[que_id])[None], 'Ks': t(np.asarray(intrinsics, np.float32)[que_id])[None],
-           'coords': t(np.stack([xs, ys], -1).reshape(1, -1, 2)), 'depth_range': t(dr[que_id])[None]}
+           'coords': t(full_frame_coords(h, w)), 'depth_range': t(dr[que_id])[None]}
     data = {'step': 0, 'eval': True, 'full_vol': True, 'ref_imgs_info': ref, 'que_imgs_info': que, 'src_imgs_info': dict(ref)}
     with torch.no_grad():
         torch.cuda.synchronize(dev)

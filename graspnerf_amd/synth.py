@@ -179,3 +179,26 @@ def synth_head_outputs(seed, R=40):
     width = 5.0 + 4.5 * field()[0]
     f = lambda a: np.ascontiguousarray(a, np.float32)
     return f(tsdf)[None, None], f(qual)[None, None], f(rot)[None], f(width)[None, None]
+
+
+def synth_metric_frames(seed, h, w, B, n_pred, identical=False):
+    """-> gt [B,h*w,3] in [0,1), preds: n_pred x [B,h*w,3] in [-0.1,1.1), depth_pr [B,h*w], depth_gt [B,h,w] in [0.2,0.8), float32.
+    A prediction is gt plus noise of +-0.02 (so gt near 0 / 1 puts it past both clips of the quantisation), and one pixel in a
+    thousand is drawn from the whole of [-0.1, 1.1): a PSNR of 35 to 40 dB, the range of a trained model -- and the range in which the
+    reference's float32 sums of the integer squared differences stay below 2^24, i.e. exact, up to the benched frame (mse * h * w
+    < 1.6e7), so that what tests/golden/golden_frame_metrics.npz records carries float32 rounding of the final value only.
+    identical: the first prediction equals gt (PSNR +inf).
+    Frames of tools/make_metric_goldens.py and tests/test_frame_metrics.py."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    gt = rng.random((B, h * w, 3), dtype=np.float32)
+    preds = []
+    for _ in range(n_pred):
+        p = gt + (rng.random((B, h * w, 3), dtype=np.float32) - np.float32(0.5)) * np.float32(0.04)
+        wild = rng.random((B, h * w, 1), dtype=np.float32) < 1e-3
+        far = rng.random((B, h * w, 3), dtype=np.float32) * np.float32(1.2) - np.float32(0.1)
+        preds.append(np.where(wild, far, p).astype(np.float32))
+    if identical:
+        preds[0] = gt.copy()
+    depth_gt = rng.random((B, h, w), dtype=np.float32) * np.float32(0.6) + np.float32(0.2)
+    depth_pr = (depth_gt.reshape(B, h * w) + (rng.random((B, h * w), dtype=np.float32) - np.float32(0.5)) * np.float32(0.1)).astype(np.float32)
+    return gt, preds, depth_pr, depth_gt

@@ -1,4 +1,4 @@
-"""Minimal training step for the reference's configuration (BASELINE.json configs[4]):
+"""Training step, validation pass, checkpoints and the loop around them for the reference's configuration (BASELINE.json configs[4]):
 forward in training mode, the configured losses (`loss: [render, depth, sdf, vgn]`), backward, ONE flat gradient
 all-reduce over RCCL, Adam with the exponential-decay schedule.
 ref: src/nr/train/trainer.py:142-158 (step), train/lr_common_manager.py:19-29 (ExpDecayLR), network/loss.py.
@@ -8,11 +8,17 @@ collective is a sum all-reduce of one flat fp32 buffer (4.66 M parameters = 18.6
 Parameters that received no gradient on a rank contribute zeros (a rank with an empty shard, or fix_s > 0 keeping the NeuS
 variance frozen for the first steps, neus.py:17-18), so the buffer layout is static.  On the GPU the volumetric path runs in
 HIP in both directions (renderer.py autograd.Functions over csrc/gnr_bwd.inc); PyTorch autograd connects them with the 2D
-backbones, the grasp head and the losses."""
+backbones, the grasp head and the losses.
+Around the step: `Trainer.validate` (validation.py: eval forward + loss terms + frame metrics per held-out scene), `save_checkpoint` /
+`load_checkpoint` in the reference's layout (trainer.py:199-218: what planner.load_model and the reference's main.py:153-165 read) and
+`fit`, the reference's run() (trainer.py:115-197)."""
+import os
+
 import torch
 import torch.distributed as dist
 
 from . import losses
+from .validation import Validator, better
 
 
 def train_losses(out, data, cfg=None):
@@ -75,6 +81,8 @@ class Trainer:
         self._fused = bool(self.params) and all(p.is_cuda for p in self.params)
         self.optimizer = torch.optim.Adam(self.params, lr=1e-3, **({'fused': True} if self._fused else {}))
         self.step_id = 0
+        self.validator = Validator()
+        self.val_history = []                              # fit(): (step, results, key metric value) of every validation pass
 
     def _mode_modules(self):
         ms = self.__dict__.get('_mode_mods')
@@ -215,3 +223,74 @@ class Trainer:
         log = dict(zip(keys, means.tolist()))
         log['lr'] = lr
         return log
+
+    # ---- validation, checkpoints, the loop (ref: train/trainer.py:115-218) -------------------------------------------------------
+    def validate(self, scenes, step=None):
+        """scenes: the global sequence of held-out `data` dicts whose query view is the full frame (planner.full_frame_coords) with
+        `que_imgs_info['true_depth']`; every rank passes the same sequence and evaluates its shard.  The net runs in eval() under
+        no_grad and comes back in the mode it had.  -> (results, key_metric_value), validation.Validator."""
+        return self.validator(self.net, scenes, self.step_id if step is None else step)
+
+    def save_checkpoint(self, path, best_para):
+        """The reference's file (trainer.py:211-218), which its plain torch.optim.Adam and planner.load_model read: the optimiser
+        state is written the way a plain Adam holds it (step counts on the host, no `fused` switch in the groups)."""
+        opt = self.optimizer.state_dict()
+        opt['state'] = {i: {k: (v.cpu() if k == 'step' and torch.is_tensor(v) else v) for k, v in st.items()} for i, st in opt['state'].items()}
+        opt['param_groups'] = [dict(g, fused=None) if 'fused' in g else dict(g) for g in opt['param_groups']]
+        torch.save({'step': int(self.step_id), 'best_para': float(best_para), 'network_state_dict': self.net.state_dict(),
+                    'optimizer_state_dict': opt}, path)
+
+    def load_checkpoint(self, path):
+        """Resume from a checkpoint of save_checkpoint or of the reference (trainer.py:199-209): parameters (in place: the version
+        counters move, so the packed copies of the hot path and the grasp head follow), Adam moments, step_id -- and with it the
+        scheduled learning rate.  -> best_para."""
+        # (a file the user trained: the reference pickles its best_para as a numpy scalar, which weights_only refuses)
+        ck = torch.load(path, map_location='cpu', weights_only=False)
+        self.net.load_state_dict(ck['network_state_dict'])
+        opt = dict(ck['optimizer_state_dict'])
+        if self._fused:
+            # the fused Adam wants its step counts on the device: load_state_dict moves them when the loaded groups say `fused`
+            opt['param_groups'] = [dict(g, fused=True, foreach=None) for g in opt['param_groups']]
+        self.optimizer.load_state_dict(opt)
+        self.step_id = int(ck['step'])
+        self._pending = None
+        return float(ck['best_para'])
+
+    def fit(self, train_batches, val_scenes, total_step, val_interval, save_interval, model_dir, key_metric_name='loss_vgn',
+            key_metric_prefer='lower'):
+        """The reference's run() (trainer.py:115-197) around step(): resume from model_dir/model.pth when it exists; validate at
+        step 0, every val_interval-th step and the last one; a better key metric writes model_best.pth (never at step 0), every
+        save_interval-th step writes model.pth.  train_batches: an iterable of this rank's scene lists, restarted when it runs out;
+        val_scenes: the global held-out sequence (validate).  With several ranks only rank 0 writes; all take part in the
+        validation exchange.  -> best_para."""
+        is_better = better(key_metric_prefer)
+        if self.validator.key_metric_name != key_metric_name:
+            v = self.validator
+            self.validator = Validator(key_metric_name, v.loss_fn, v.eval_margin_ratio, v.ssim)
+        writer = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+        pth, best_pth = os.path.join(model_dir, 'model.pth'), os.path.join(model_dir, 'model_best.pth')
+        if writer:
+            os.makedirs(model_dir, exist_ok=True)
+        best_para = 0
+        if os.path.exists(pth):
+            best_para = self.load_checkpoint(pth)
+        if key_metric_prefer == 'lower' and self.step_id == 0:
+            best_para = 1e6
+        it = iter(train_batches)
+        for step in range(self.step_id, total_step):
+            try:
+                batch = next(it)
+            except StopIteration:
+                it = iter(train_batches)
+                batch = next(it)
+            self.step(batch)
+            if step == 0 or (step + 1) % val_interval == 0 or step + 1 == total_step:
+                results, val = self.validate(val_scenes, step)
+                self.val_history.append((step + 1, results, val))
+                if step and is_better(val, best_para):                     # the first step never saves (trainer.py:183)
+                    best_para = val
+                    if writer:
+                        self.save_checkpoint(best_pth, best_para)
+            if (step + 1) % save_interval == 0 and writer:
+                self.save_checkpoint(pth, best_para)
+        return best_para

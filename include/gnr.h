@@ -378,6 +378,29 @@ int gnr_ingest_u8(const unsigned char* frames, int n, int src_h, int src_w, int 
                   const void* tables_dev, float* out, int dst_h, int dst_w, void* stream);
 const char* gnr_ingest_last_error(void);
 
+/* ---- frame metrics of a validation pass (csrc/gnr_metrics.hip) ---------------------------------------------------
+ * The reference's PSNR_SSIM metric (network/metrics.py:14-30,40-84) for B full frames at once, all on the device:
+ *   gt [B,h*w,3], preds[p] [B,h*w,3] for p < n_pred (`preds` is a HOST array of n_pred device pointers, n_pred in
+ *   1..GNR_METRICS_MAX_PRED: pixel_colors_nr, pixel_colors_nr_fine), depth_pr [B,h*w], depth_gt [B,h,w], all float32.
+ *   out: DEVICE float64 [B][2 * n_pred + 1] = psnr[n_pred], ssim[n_pred], depth_mae per scene.
+ * PSNR: both images quantised as color_map_backward does (utils/base_utils.py:496-499: one fp32 multiply by 255, clip to
+ *   [0,255], truncation to uint8), cropped by h_margin rows / w_margin columns on every side (the caller computes
+ *   int(h * (1 - eval_margin_ratio)) // 2), 10 log10(255^2 / mse) with the squared differences summed as 64-bit integers
+ *   (exact) and the rest in double;  mse == 0 -> +inf;  a non-finite gt / prediction value inside the crop -> NaN (SSIM too).
+ * depth_mae: mean of the fp32 |depth_pr - depth_gt| over the UNCROPPED frame (metrics.py:79-83), summed in double.
+ * SSIM (ssim != 0; otherwise NaN is written): skimage.metrics.structural_similarity(gt, pr, win_size=11, multichannel=True,
+ *   data_range=255) on the quantised, cropped images: exact int32 window sums, S in double, the mean over the frame without
+ *   its 5-pixel border, then over the three channels.  Needs a cropped frame of at least 11 x 11: GNR_ERR_SHAPE otherwise.
+ * Every floating-point sum is taken in a fixed order (per-workgroup partials in the workspace, one second stage; no float
+ * atomics): two calls return the same bits.  Stream-ordered, no allocation, no host synchronisation, no library state.
+ * GNR_ERR_ARG: null pointer, n_pred outside 1..4;  GNR_ERR_SHAPE: B outside 1..65535, h or w < 1, h * w >= 2^31, margins
+ * that leave no pixel, a crop below the SSIM window;  GNR_ERR_WORKSPACE: workspace_bytes below
+ * gnr_frame_metrics_workspace_bytes() of the same arguments (0 for arguments the entry point refuses);  text in gnr_last_error(). */
+#define GNR_METRICS_MAX_PRED 4
+size_t gnr_frame_metrics_workspace_bytes(int B, int h, int w, int n_pred, int h_margin, int w_margin, int ssim);
+int gnr_frame_metrics(const float* gt, const float* const* preds, int n_pred, const float* depth_pr, const float* depth_gt, int B, int h,
+                      int w, int h_margin, int w_margin, int ssim, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- backward twins ------------------------------------------------------------------------
  * Parameter gradients are DETERMINISTIC: the kernels use no float atomics on them.  Points / rays are assigned to
  * wavefronts statically, every wavefront stores its partial sums into its own slot of a partial buffer inside the
