@@ -146,11 +146,33 @@ DEV void conv_epilogue(const ConvArgs& a, const f4 (&acc)[4][NB], int b, int bz,
     }
 }
 
+// Blocked summation.  v_mfma_f32_16x16x4_f32 is a chain of four fmaf, so a layer accumulated in one register is ONE sequential fp32
+// sum of taps x cin products (1728 for the 64-channel k3 layers): its rounding error grows with the length of the chain and was up to
+// 8 x that of a blocked fp32 sum (decoder.conv2 against float64 at R = 8: 8.3e-7 of the tensor's rms, PyTorch fp32 1.05e-7).  Both
+// kernels therefore cut the chains: 16 products (16 input channels of one tap) per MFMA chain, the chunks of one (tz, ty) row of taps
+// added up, the rows added to the total (which starts from the bias).  The folded layers (k3, 32 / 16 input channels) keep one chain
+// per row (96 / 48 products): their chains were shorter to begin with, and they are where the head's time goes.
+template <int NB>
+DEV void clear(f4 (&x)[4][NB]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) x[t][nb] = f4{0.f, 0.f, 0.f, 0.f};
+}
+template <int NB>
+DEV void add_into(f4 (&sum)[4][NB], const f4 (&x)[4][NB]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) sum[t][nb] += x[t][nb];
+}
+
 // ---- strided encoder layers (large input footprint per brick, ~2 % of the FLOPs): one wavefront per 4x4x4
 // output brick, B operand gathered straight from global memory, A fragments read coalesced from global.
 template <int CIN, int NB, int KS, int STRIDE, int EPI>
 __global__ __launch_bounds__(256) void k_conv3d_direct(ConvArgs a) {
     constexpr int PAD = KS / 2, C4 = CIN / 4;
+    static_assert(C4 % 4 == 0, "cin multiple of 16 (chunks of the blocked summation)");
     const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
     const int Din = a.Din, Din3 = Din * Din * Din;
     const int nbr = (a.Dout + 3) >> 2;
@@ -182,6 +204,8 @@ __global__ __launch_bounds__(256) void k_conv3d_direct(ConvArgs a) {
             const bool yok = (unsigned)iy < (unsigned)a.Deff;
             const int iyc = yok ? iy : 0;
             const int yoff = (a.umap ? a.umap[iyc] : iyc) * Din;
+            f4 rsum[4][NB];                               // this (tz, ty) row of taps (blocked summation, see add_into)
+            clear(rsum);
 #pragma unroll 1
             for (int tx = 0; tx < KS; ++tx) {
                 const int ix = ox * STRIDE + tx - PAD;
@@ -191,19 +215,26 @@ __global__ __launch_bounds__(256) void k_conv3d_direct(ConvArgs a) {
                 const int xyoff = yoff + (a.umap ? a.umap[ixc] : ixc);
                 const float* wt = wf + (size_t)((tz * KS + ty) * KS + tx) * C4 * NBT * 64;
 #pragma unroll
-                for (int c = 0; c < C4; ++c) {
-                    float av[NB];
+                for (int c0 = 0; c0 < C4; c0 += 4) {      // one chunk = 16 input channels of one tap
+                    f4 part[4][NB];
+                    clear(part);
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) av[nb] = wt[(c * NBT + nb) * 64];
+                    for (int c = c0; c < c0 + 4; ++c) {
+                        float av[NB];
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const float v = ing[(size_t)(4 * c) * Din3 + zoff[t] + xyoff];
-                        const float bv = (xok && zok[t]) ? v : 0.f;
+                        for (int nb = 0; nb < NB; ++nb) av[nb] = wt[(c * NBT + nb) * 64];
 #pragma unroll
-                        for (int nb = 0; nb < NB; ++nb) acc[t][nb] = mfma16(av[nb], bv, acc[t][nb]);
+                        for (int t = 0; t < 4; ++t) {
+                            const float v = ing[(size_t)(4 * c) * Din3 + zoff[t] + xyoff];
+                            const float bv = (xok && zok[t]) ? v : 0.f;
+#pragma unroll
+                            for (int nb = 0; nb < NB; ++nb) part[t][nb] = mfma16(av[nb], bv, part[t][nb]);
+                        }
                     }
+                    add_into(rsum, part);
                 }
             }
+            add_into(acc, rsum);
         }
     }
     conv_epilogue<NB, EPI>(a, acc, b, bz, oy, ox, g, -1, nb0);
@@ -224,7 +255,7 @@ constexpr int halo_max(bool fold) { return fold ? 608 : 320; }
 template <int CIN, int NB, int KS, int TS, int EPI, bool FOLD>
 __global__ __launch_bounds__(256) void k_conv3d_staged(ConvArgs a) {
     constexpr int PAD = KS / 2, C4 = CIN / 4, TAPS = KS * KS * KS, AFL = C4 * NB * 64;   // A floats per tap
-    constexpr int HALO_MAX = halo_max(FOLD);
+    constexpr int HALO_MAX = halo_max(FOLD), ROW_UNROLL = FOLD ? TS / KS : 1;
     static_assert(TAPS % TS == 0, "tap staging step must divide the tap count");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* halo = smem;                                   // [CIN][HALO_MAX]
@@ -292,7 +323,9 @@ __global__ __launch_bounds__(256) void k_conv3d_staged(ConvArgs a) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) pf[k] = srcp[gidx(threadIdx.x + 256 * k)];
         }
-#pragma unroll 1
+        // FOLD (the two layers with 92 % of the MACs, one wavefront per SIMD): a row is one MFMA chain, and the rows of a slice are
+        // unrolled so that the adds of one row sit in the shadow of the next row's MFMAs instead of waiting behind its own
+#pragma unroll ROW_UNROLL
         for (int row = 0; row < TS / KS; ++row) {         // one (tz, ty) row of KS taps, x-taps unrolled
             const int rowi = (s0 % TAPS) / KS + row, tz = rowi / KS, ty = rowi % KS;
             int yz[4] = {0, 0, 0, 0};
@@ -307,25 +340,32 @@ __global__ __launch_bounds__(256) void k_conv3d_staged(ConvArgs a) {
                     for (int t = 0; t < 4; ++t) yz[t] += zo[t][k];
                 }
             }
+            f4 rsum[4][NB];                               // this row of taps (blocked summation, see add_into)
+            clear(rsum);
 #pragma unroll
             for (int tx = 0; tx < KS; ++tx) {
                 const f4* ap = reinterpret_cast<const f4*>(asl + ((row * KS + tx) * NB * 64 + lane) * C4);
 #pragma unroll
-                for (int c4 = 0; c4 < C4 / 4; ++c4) {
+                for (int c4 = 0; c4 < C4 / 4; ++c4) {     // one chunk = 16 input channels of one tap
                     f4 av[NB];
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) av[nb] = ap[nb * 64 * (C4 / 4) + c4];
+                    f4 part[4][NB];
+                    if constexpr (!FOLD) clear(part);
+                    f4 (&chain)[4][NB] = FOLD ? rsum : part;
 #pragma unroll
                     for (int cc = 0; cc < 4; ++cc) {
 #pragma unroll
                         for (int t = 0; t < 4; ++t) {
                             const float bv = hg[4 * (4 * c4 + cc) * HALO_MAX + yz[t] + xo[tx]];
 #pragma unroll
-                            for (int nb = 0; nb < NB; ++nb) acc[t][nb] = mfma16(av[nb][cc], bv, acc[t][nb]);
+                            for (int nb = 0; nb < NB; ++nb) chain[t][nb] = mfma16(av[nb][cc], bv, chain[t][nb]);
                         }
                     }
+                    if constexpr (!FOLD) add_into(rsum, part);
                 }
             }
+            add_into(acc, rsum);
         }
         if ((s0 + TS) % TAPS == 0) {                      // a parity class (or the whole layer) is complete
             conv_epilogue<NB, EPI>(a, acc, b, bz, oy, ox, g, FOLD ? s0 / TAPS : -1, nb0);

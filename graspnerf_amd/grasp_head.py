@@ -36,7 +36,28 @@ def pack(canonical):
     return out
 
 
+def activation_layout(B, R):
+    """(name, float offset, shape) of the six post-ReLU activations a1..a6 in the workspace of gnr_grasp_head_fwd(B, R), laid out as
+    that function lays them out (a1 [B,16,d1^3], a2 [B,32,d2^3], a3 / a4 [B,64,d3^3], a5 [B,32,10^3], a6 [B,16,20^3], then 4096 bytes that
+    hold the three nearest-neighbour index maps).  A layout change in the library fails the assertion here."""
+    if B < 1 or not 8 <= R <= 64:
+        raise ValueError(f'the grasp head takes B >= 1 and R in 8..64, not B = {B}, R = {R}')
+    d1 = (R - 1) // 2 + 1
+    d2 = (d1 - 1) // 2 + 1
+    d3 = (d2 - 1) // 2 + 1
+    out, off = [], 0
+    for i, (c, d) in enumerate([(16, d1), (32, d2), (64, d3), (64, d3), (32, 10), (16, 20)]):
+        out.append((f'a{i + 1}', off, (B, c, d, d, d)))
+        off += B * c * d ** 3
+    assert 4 * off + 4096 == _lib.lib().gnr_grasp_head_workspace_bytes(B, R), 'workspace layout of gnr_grasp_head_fwd has changed'
+    return out
+
+
 class GraspHead:
+    """gd.networks.ConvNet.forward for a volume [B,1,R,R,R] with B >= 1 and a volume edge R in 8..64 (the library refuses anything else
+    with GNR_ERR_SHAPE).  The encoder halves R three times (d -> (d - 1) // 2 + 1); up to R = 40 (bottleneck edge d3 <= 5) decoder.conv1
+    and decoder.conv2 run on the LDS-staged kernel, from R = 41 on the direct-gather kernel.  The outputs are 40^3 whatever R is."""
+
     def __init__(self, state_dict, prefix='', device='cuda:0'):
         self.L = _lib.lib()
         if not torch.cuda.is_available():
@@ -62,3 +83,11 @@ class GraspHead:
             raise _lib.GnrError(f'gnr_grasp_head_fwd failed: {_lib.ERRORS.get(rc, rc)} '
                                 f'({self.L.gnr_head_last_error().decode(errors="replace")})')
         return q, r, w
+
+    def activations(self, B, R):
+        """Views of a1..a6 (the post-ReLU output of encoder.conv1..3 and decoder.conv1..3) in the workspace of the last call, which must
+        have been a call with this B and R: {'a1': [B,16,d1,d1,d1], ..., 'a6': [B,16,20,20,20]}.  The next call overwrites them."""
+        layout = activation_layout(B, R)
+        if self._ws is None or self._ws.numel() < self.L.gnr_grasp_head_workspace_bytes(B, R):
+            raise _lib.GnrError('activations(): no call with this B and R has been made')
+        return {name: self._ws[4 * off:4 * (off + int(np.prod(shape)))].view(torch.float32).view(shape) for name, off, shape in layout}
