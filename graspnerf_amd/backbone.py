@@ -51,8 +51,7 @@ def _img_lib():
 
 def _img_check(rc, what):
     if rc:
-        _lib, L = _img_lib()
-        raise _lib.GnrError(f'{what} failed: {_lib.ERRORS.get(rc, rc)} ({L.gnr_img_last_error().decode(errors="replace")})')
+        _img_lib()[0].check(rc, what)
 
 
 def _stream(t):
@@ -470,8 +469,7 @@ def _hip_conv3d_same(x, w, b, mode, mask=None):
     rc = L.gnr_conv3d_same_masked(x.data_ptr(), w.data_ptr(), b.contiguous().data_ptr() if (b is not None and not mode) else None, y.data_ptr(),
                                   B, cin, cout, D, H, W, k, mode | (GNR_CONV3D_FIRST_GEN if CONV3D_FIRST_GEN else 0), mask.data_ptr() if mask is not None else None, ws.data_ptr(), ws.numel(),
                                   C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc:
-        raise _lib.GnrError(f'gnr_conv3d_same failed: {_lib.ERRORS.get(rc, rc)} ({L.gnr_head_last_error().decode(errors="replace")})')
+    _lib.check(rc, 'gnr_conv3d_same')
     return y
 
 
@@ -510,8 +508,7 @@ class _Conv3dSame(torch.autograd.Function):
             kflag = k | (GNR_CONV3D_FIRST_GEN if CONV3D_FIRST_GEN else 0)
             rc = L.gnr_conv3d_same_bwd_weight_masked(xc.data_ptr(), dy.data_ptr(), dw.data_ptr(), *dims[:-1], kflag, mask.data_ptr() if mask is not None else None,
                                                      _CONV_WS[key].data_ptr(), need, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-            if rc:
-                raise _lib.GnrError(f'gnr_conv3d_same_bwd_weight failed: {rc}')
+            _lib.check(rc, 'gnr_conv3d_same_bwd_weight')
         db = dy.sum((0, 2, 3, 4)) if ctx.needs_input_grad[2] else None
         return dx, dw, db, None
 

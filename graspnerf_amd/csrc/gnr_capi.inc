@@ -5,32 +5,11 @@
 #include <mutex>
 #include <type_traits>
 
-#include "../../include/gnr.h"
+#include "gnr_host.h"
 
 namespace gnr {
 
-static thread_local char g_err[512] = "";
-static int fail(int code, const char* what, hipError_t e = hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "%s%s%s", what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString(e) : "");
-    return code;
-}
-#define GNR_HIP(call)                                                         \
-    do {                                                                      \
-        hipError_t e_ = (call);                                               \
-        if (e_ != hipSuccess) return fail(GNR_ERR_HIP, #call, e_);            \
-    } while (0)
-
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: one bit per device id and kernel (launch())
-static bool attr_needed(std::atomic<unsigned long long>& done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return true;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load() & bit) return false;
-    done.fetch_or(bit);
-    return true;
-}
+static thread_local char g_err[512] = "";     // the library's one error text: written by gnr_internal_fail (fail(), gnr_host.h), read by gnr_last_error
 
 struct Workspace {
     float* feat64; float* viewp; unsigned* range_flag;             // persistent between gnr_prepare and the forwards
@@ -127,36 +106,6 @@ struct KTiming {
     struct Rec { const char* label; hipEvent_t e0, e1; } rec[MAX];
 };
 static KTiming g_kt;
-struct KScope {
-    hipStream_t st; int idx = -1;
-    KScope(const char* label, hipStream_t s) : st(s) {            // label == nullptr: a launch that is never bracketed
-        if (!label || !g_kt.on.load() || (g_kt.only[0] && !strstr(label, g_kt.only))) return;
-        hipEvent_t e0, e1;
-        if (hipEventCreate(&e0) != hipSuccess) return;
-        if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return; }
-        const int i = g_kt.n.fetch_add(1);
-        if (i >= KTiming::MAX) { g_kt.n.fetch_sub(1); hipEventDestroy(e0); hipEventDestroy(e1); return; }
-        g_kt.rec[i] = KTiming::Rec{label, e0, e1};
-        hipEventRecord(e0, st);
-        idx = i;
-    }
-    ~KScope() { if (idx >= 0) hipEventRecord(g_kt.rec[idx].e1, st); }
-};
-
-// Every kernel launch of this file: the timing bracket around the launch alone, then the launch's own error check.  A kernel that takes
-// more dynamic LDS than a launch gets by default names its maximum as MAX_LDS -- the most any launch of it asks for, not this launch's
-// bytes -- and has hipFuncAttributeMaxDynamicSharedMemorySize raised to it on the first launch per device (one static per kernel).
-// A kernel passed as a template argument has lost its default arguments: the call sites spell them out.
-template <auto Kernel, size_t MAX_LDS = 0, typename... Args>
-static int launch(const char* label, hipStream_t st, dim3 grid, dim3 block, size_t lds_bytes, Args... args) {
-    if constexpr (MAX_LDS != 0) {
-        static std::atomic<unsigned long long> attr_done{0};
-        if (attr_needed(attr_done)) GNR_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MAX_LDS));
-    }
-    { KScope ks(label, st); hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...); }
-    GNR_HIP(hipGetLastError());
-    return GNR_OK;
-}
 
 // The kernels with a view loop are templates on the view count: f(std::integral_constant<int, V>) for the scene's V (check_scene: 2..8)
 template <typename F>
@@ -1293,15 +1242,24 @@ extern "C" int gnr_geo_dual_bwd(const float* canon, const float* stats, const fl
     return launch_grad_reduce(dpart, slots, GD_STRIDE, d_canonical, rg, 1, st, "k_grad_reduce@gnr_geo_dual_bwd");
 }
 
-// gnr_last_error's text for an entry point that lives in another translation unit (gnr_metrics.hip): not part of the public ABI
-extern "C" int gnr_internal_fail(int code, const char* what, int hip_error) { return fail(code, what, (hipError_t)hip_error); }
+// fail() of every translation unit (gnr_host.h) ends here: not part of the public ABI
+extern "C" int gnr_internal_fail(int code, const char* what, int hip_error) {
+    const hipError_t e = (hipError_t)hip_error;
+    snprintf(g_err, sizeof(g_err), "%s%s%s", what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString(e) : "");
+    return code;
+}
 
-// the same bracket for the library's other translation units (gnr_head.hip, gnr_post.hip, gnr_metrics.hip): not part of the public ABI
+// TimingScope of every translation unit (gnr_host.h): claims a slot and records the opening event; -1 when the label is not bracketed
 extern "C" int gnr_internal_timing_open(const char* label, void* stream) {
-    KScope ks(label, (hipStream_t)stream);                    // claims a slot and records the opening event
-    const int idx = ks.idx;
-    ks.idx = -1;                                              // the closing event is the caller's (gnr_internal_timing_close)
-    return idx;
+    if (!label || !g_kt.on.load() || (g_kt.only[0] && !strstr(label, g_kt.only))) return -1;
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess) return -1;
+    if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return -1; }
+    const int i = g_kt.n.fetch_add(1);
+    if (i >= KTiming::MAX) { g_kt.n.fetch_sub(1); hipEventDestroy(e0); hipEventDestroy(e1); return -1; }
+    g_kt.rec[i] = KTiming::Rec{label, e0, e1};
+    hipEventRecord(e0, (hipStream_t)stream);
+    return i;
 }
 extern "C" void gnr_internal_timing_close(int idx, void* stream) {
     if (idx >= 0 && idx < g_kt.n.load()) hipEventRecord(g_kt.rec[idx].e1, (hipStream_t)stream);

@@ -15,20 +15,9 @@
 // memory; A fragments are pre-packed [tap][cin/4][cout/16][64 lanes] and read coalesced.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdio.h>
-#include <atomic>
 #include <vector>
 
-#include "../../include/gnr.h"
-
-// per-launch timing brackets of the library (gnr_capi.inc; active between gnr_timing_begin / gnr_timing_end)
-extern "C" int gnr_internal_timing_open(const char* label, void* stream);
-extern "C" void gnr_internal_timing_close(int idx, void* stream);
-struct HeadScope {
-    void* st; int idx;
-    HeadScope(const char* label, void* s) : st(s), idx(gnr_internal_timing_open(label, s)) {}
-    ~HeadScope() { gnr_internal_timing_close(idx, st); }
-};
+#include "gnr_host.h"
 
 namespace gnrh {
 
@@ -381,17 +370,9 @@ __global__ __launch_bounds__(256) void k_conv3d_staged(ConvArgs a) {
 
 using namespace gnrh;
 
-static thread_local char h_err[256] = "";
-// hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: one bit per device id and kernel
-static bool head_attr_needed(std::atomic<unsigned long long>& done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return true;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load() & bit) return false;
-    done.fetch_or(bit);
-    return true;
-}
-extern "C" const char* gnr_head_last_error(void) { return h_err; }
+using namespace gnr;
+
+extern "C" const char* gnr_head_last_error(void) { return gnr_last_error(); }           // alias: the library has one error text
 
 extern "C" int gnr_head_canonical_floats(void) { return C_TOTAL; }
 extern "C" int gnr_head_packed_floats(void) { return P_TOTAL; }
@@ -434,7 +415,7 @@ static void pack_folded(float* dst, const float* W, const float* bias, int cout,
 }
 
 extern "C" int gnr_pack_grasp_head(const float* c, float* p) {
-    if (!c || !p) return GNR_ERR_ARG;
+    if (!c || !p) return fail(GNR_ERR_ARG, "gnr_pack_grasp_head: null pointer");
     for (int i = 0; i < P_TOTAL; ++i) p[i] = 0.f;
     for (int i = 0; i < w_sz(16, 1, 5); ++i) p[P_E1 + i] = c[C_E1W + i];
     for (int i = 0; i < 16; ++i) p[P_E1 + w_sz(16, 1, 5) + i] = c[C_E1B + i];
@@ -453,50 +434,37 @@ extern "C" int gnr_pack_grasp_head(const float* c, float* p) {
     return GNR_OK;
 }
 
-#define HCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(h_err, sizeof(h_err), "%s: %s", #call, hipGetErrorString(e_)); return GNR_ERR_HIP; } } while (0)
-
 extern "C" size_t gnr_grasp_head_workspace_bytes(int B, int R) {
     const int d1 = (R - 1) / 2 + 1, d2 = (d1 - 1) / 2 + 1, d3 = (d2 - 1) / 2 + 1;
     size_t fl = (size_t)16 * d1 * d1 * d1 + (size_t)32 * d2 * d2 * d2 + 2 * (size_t)64 * d3 * d3 * d3 + 32 * 1000 + 16 * 8000;
     return (size_t)B * fl * sizeof(float) + 4096;
 }
 
+// the head's inner launches carry no label of their own: gnr_grasp_head_fwd brackets all of them as one
 template <int CIN, int NB, int KS, int STRIDE, int EPI>
 static int launch_direct(const ConvArgs& a, hipStream_t st) {
     const int nbr = (a.Dout + 3) / 4;
     const long blocks = ((long)a.B * nbr * nbr * nbr + 3) / 4;
-    hipLaunchKernelGGL((k_conv3d_direct<CIN, NB, KS, STRIDE, EPI>), dim3((unsigned)blocks, a.nb_total / NB), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(h_err, sizeof(h_err), "k_conv3d_direct launch: %s", hipGetErrorString(e)); return GNR_ERR_HIP; }
-    return GNR_OK;
+    return launch<k_conv3d_direct<CIN, NB, KS, STRIDE, EPI>>(nullptr, st, dim3((unsigned)blocks, a.nb_total / NB), dim3(256), 0, a);
 }
 
 template <int CIN, int NB, int KS, int TS, int EPI, bool FOLD>
 static int launch_staged(const ConvArgs& a, hipStream_t st) {
     const int nbx = (a.Dout + 7) / 8, nbz = (a.Dout + 3) / 4;
     const long blocks = (long)a.B * nbx * nbx * nbz;
-    const size_t lds = ((size_t)CIN * halo_max(FOLD) + (size_t)TS * (CIN / 4) * NB * 64) * sizeof(float);
-    static std::atomic<unsigned long long> attr{0};
-    if (head_attr_needed(attr)) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_conv3d_staged<CIN, NB, KS, TS, EPI, FOLD>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { snprintf(h_err, sizeof(h_err), "hipFuncSetAttribute: %s", hipGetErrorString(e)); return GNR_ERR_HIP; }
-    }
-    hipLaunchKernelGGL((k_conv3d_staged<CIN, NB, KS, TS, EPI, FOLD>), dim3((unsigned)blocks, a.nb_total / NB), dim3(256), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(h_err, sizeof(h_err), "k_conv3d_staged launch: %s", hipGetErrorString(e)); return GNR_ERR_HIP; }
-    return GNR_OK;
+    constexpr size_t lds = ((size_t)CIN * halo_max(FOLD) + (size_t)TS * (CIN / 4) * NB * 64) * sizeof(float);
+    return launch<k_conv3d_staged<CIN, NB, KS, TS, EPI, FOLD>, lds>(nullptr, st, dim3((unsigned)blocks, a.nb_total / NB), dim3(256), lds, a);
 }
 
 // ConvNet.forward (networks.py:48-54).  volume [B,1,R,R,R]; outputs qual [B,1,40,40,40], rot [B,4,40^3], width [B,1,40^3]
 // (the reference interpolates to the fixed sizes 10/20/40 whatever R is, networks.py:88-96).
 extern "C" int gnr_grasp_head_fwd(int B, int R, const float* volume, const float* packed, float* qual, float* rot, float* width,
                                   void* ws, size_t ws_bytes, void* stream) {
-    if (!volume || !packed || !qual || !rot || !width || !ws) { snprintf(h_err, sizeof(h_err), "gnr_grasp_head_fwd: null pointer"); return GNR_ERR_ARG; }
-    if (B < 1 || R < 8 || R > 64) { snprintf(h_err, sizeof(h_err), "gnr_grasp_head_fwd: bad B/R"); return GNR_ERR_SHAPE; }
-    if (ws_bytes < gnr_grasp_head_workspace_bytes(B, R)) { snprintf(h_err, sizeof(h_err), "workspace too small"); return GNR_ERR_WORKSPACE; }
+    if (!volume || !packed || !qual || !rot || !width || !ws) return fail(GNR_ERR_ARG, "gnr_grasp_head_fwd: null pointer");
+    if (B < 1 || R < 8 || R > 64) return fail(GNR_ERR_SHAPE, "gnr_grasp_head_fwd: bad B/R");
+    if (ws_bytes < gnr_grasp_head_workspace_bytes(B, R)) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    HeadScope hs("grasp_head_fwd(all kernels)@gnr_grasp_head_fwd", stream);
+    TimingScope ts("grasp_head_fwd(all kernels)@gnr_grasp_head_fwd", stream);
     const int d1 = (R - 1) / 2 + 1, d2 = (d1 - 1) / 2 + 1, d3 = (d2 - 1) / 2 + 1;      // conv k, s2, pad k/2
     float* a1 = (float*)ws;                                   // [B][16][d1^3]
     float* a2 = a1 + (size_t)B * 16 * d1 * d1 * d1;           // [B][32][d2^3]
@@ -505,16 +473,11 @@ extern "C" int gnr_grasp_head_fwd(int B, int R, const float* volume, const float
     float* a5 = a4 + (size_t)B * 64 * d3 * d3 * d3;           // [B][32][10^3]
     float* a6 = a5 + (size_t)B * 32 * 1000;                   // [B][16][20^3]
     int* umaps = (int*)(a6 + (size_t)B * 16 * 8000);          // 3 nearest-neighbour index maps
-    hipLaunchKernelGGL(k_umaps, dim3(1), dim3(128), 0, st, umaps, d3);
-    HCHK(hipGetLastError());
-    {
-        const int n = B * d1 * d1 * d1;
-        hipLaunchKernelGGL(k_conv_first, dim3((n + 255) / 256), dim3(256), 0, st, volume, packed + P_E1, a1, R, d1, B);
-        HCHK(hipGetLastError());
-    }
+    int rc;
+    if ((rc = launch<k_umaps>(nullptr, st, dim3(1), dim3(128), 0, umaps, d3))) return rc;
+    if ((rc = launch<k_conv_first>(nullptr, st, dim3((B * d1 * d1 * d1 + 255) / 256), dim3(256), 0, volume, packed + P_E1, a1, R, d1, B))) return rc;
     ConvArgs c{};
     c.B = B;
-    int rc;
     c.in = a1; c.wfrag = packed + P_E2; c.bias = c.wfrag + frag_sz(32, 16, 3); c.umap = nullptr; c.out = a2; c.Din = d1; c.Deff = d1; c.Dout = d2; c.cout = 32; c.nb_total = 2;
     if ((rc = launch_direct<16, 1, 3, 2, 0>(c, st))) return rc;
     c.in = a2; c.wfrag = packed + P_E3; c.bias = c.wfrag + frag_sz(64, 32, 3); c.out = a3; c.Din = d2; c.Deff = d2; c.Dout = d3; c.cout = 64; c.nb_total = 4;
@@ -596,14 +559,13 @@ __global__ __launch_bounds__(256) void k_conv3d_bwd_weight(const float* __restri
 // dw [Cout][Cin][K][K][K] is ACCUMULATED (zero it first).  x [B][Cin][D][H][W], dy [B][Cout][D][H][W], stride 1, padding K/2.
 extern "C" int gnr_conv3d_bwd_weight(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int K,
                                      void* stream) {
-    if (!x || !dy || !dw || B < 1 || Cin < 1 || Cout < 1 || D < 1 || H < 1 || W < 1 || K < 1 || !(K & 1)) return GNR_ERR_ARG;
+    if (!x || !dy || !dw || B < 1 || Cin < 1 || Cout < 1 || D < 1 || H < 1 || W < 1 || K < 1 || !(K & 1))
+        return fail(GNR_ERR_ARG, "gnr_conv3d_bwd_weight: null pointer, a size below 1 or an even K");
     const long total = (long)B * D * H * W;
     const int nchunk = (int)((total + gnr_head::BW_CHUNK - 1) / gnr_head::BW_CHUNK);
     const long njobs = (long)nchunk * K * K * K * ((Cin + 15) / 16) * ((Cout + 15) / 16);
-    HeadScope hs("k_conv3d_bwd_weight@gnr_conv3d_bwd_weight", stream);
-    hipLaunchKernelGGL(gnr_head::k_conv3d_bwd_weight, dim3((unsigned)((njobs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, dy, dw, B,
-                       Cin, Cout, D, H, W, K, nchunk);
-    return hipGetLastError() == hipSuccess ? GNR_OK : GNR_ERR_HIP;
+    return launch<gnr_head::k_conv3d_bwd_weight>("k_conv3d_bwd_weight@gnr_conv3d_bwd_weight", (hipStream_t)stream, dim3((unsigned)((njobs + 3) / 4)), dim3(256), 0,
+                                                 x, dy, dw, B, Cin, Cout, D, H, W, K, nchunk);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -903,19 +865,9 @@ extern "C" size_t gnr_conv3d_tap_mask_words(int Cin, int Cout) {
 // mask [Cin blocks][Cout blocks][4 words] <- which taps of each 16 x 16 weight block exist in `pattern` [Cout][Cin][K^3] (device, any
 // non-zero = the weight exists).  Made once per layer shape; the masked entry points below skip the absent taps in all three directions.
 extern "C" int gnr_conv3d_tap_mask(const float* pattern, unsigned* mask, int Cin, int Cout, int K, void* stream) {
-    if (!pattern || !mask || Cin < 1 || Cout < 1 || (K != 3 && K != 5)) return GNR_ERR_ARG;
+    if (!pattern || !mask || Cin < 1 || Cout < 1 || (K != 3 && K != 5)) return fail(GNR_ERR_ARG, "gnr_conv3d_tap_mask: null pointer, a size below 1 or K not 3 or 5");
     const int nbi = (Cin + 15) / 16, nbo = (Cout + 15) / 16;
-    hipLaunchKernelGGL(gnr_head::k_conv3d_tap_mask, dim3(nbi * nbo), dim3(64), 0, (hipStream_t)stream, pattern, mask, Cin, Cout, K * K * K, nbo);
-    HCHK(hipGetLastError());
-    return GNR_OK;
-}
-
-extern "C" int gnr_conv3d_same_masked(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int D, int H,
-                                      int W, int K, int mode, const unsigned* mask, void* ws, size_t ws_bytes, void* stream);
-
-extern "C" int gnr_conv3d_same(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int D, int H,
-                               int W, int K, int mode, void* ws, size_t ws_bytes, void* stream) {
-    return gnr_conv3d_same_masked(x, w, bias, y, B, Cin, Cout, D, H, W, K, mode, nullptr, ws, ws_bytes, stream);
+    return launch<gnr_head::k_conv3d_tap_mask>(nullptr, (hipStream_t)stream, dim3(nbi * nbo), dim3(64), 0, pattern, mask, Cin, Cout, K * K * K, nbo);
 }
 
 // `mask` = gnr_conv3d_tap_mask of the layer's weight pattern (or NULL: dense): taps without a weight are skipped.
@@ -923,42 +875,36 @@ extern "C" int gnr_conv3d_same_masked(const float* x, const float* w, const floa
                                       int W, int K, int mode, const unsigned* mask, void* ws, size_t ws_bytes, void* stream) {
     const bool first_gen = (mode & GNR_CONV3D_FIRST_GEN) != 0;
     mode &= ~GNR_CONV3D_FIRST_GEN;
-    if (!x || !w || !y || !ws) { snprintf(h_err, sizeof(h_err), "gnr_conv3d_same: null pointer"); return GNR_ERR_ARG; }
-    if (B < 1 || Cin < 1 || Cout < 1 || D < 1 || H < 1 || W < 1 || (K != 3 && K != 5) || (mode != 0 && mode != 1)) {
-        snprintf(h_err, sizeof(h_err), "gnr_conv3d_same: bad shape / mode (K must be 3 or 5)"); return GNR_ERR_SHAPE; }
-    if (ws_bytes < gnr_conv3d_same_workspace_bytes(Cin, Cout, K)) { snprintf(h_err, sizeof(h_err), "gnr_conv3d_same: workspace too small"); return GNR_ERR_WORKSPACE; }
+    if (!x || !w || !y || !ws) return fail(GNR_ERR_ARG, "gnr_conv3d_same: null pointer");
+    if (B < 1 || Cin < 1 || Cout < 1 || D < 1 || H < 1 || W < 1 || (K != 3 && K != 5) || (mode != 0 && mode != 1))
+        return fail(GNR_ERR_SHAPE, "gnr_conv3d_same: bad shape / mode (K must be 3 or 5)");
+    if (ws_bytes < gnr_conv3d_same_workspace_bytes(Cin, Cout, K)) return fail(GNR_ERR_WORKSPACE, "gnr_conv3d_same: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int cin = mode ? Cout : Cin, cout = mode ? Cin : Cout;
     const int nchunks = (cin + 15) / 16, nbt = (cout + 15) / 16, K3 = K * K * K;
     float* frag = (float*)ws;
-    {
-        const long n = (long)nchunks * K3 * 4 * nbt * 64;
-        HeadScope hs("k_pack_conv3d_frag@gnr_conv3d_same", stream);
-        hipLaunchKernelGGL(gnr_head::k_pack_conv3d_frag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, frag, Cin, Cout, K, mode, nchunks, nbt);
-        HCHK(hipGetLastError());
-    }
+    const long n = (long)nchunks * K3 * 4 * nbt * 64;
+    if (int rc = launch<gnr_head::k_pack_conv3d_frag>("k_pack_conv3d_frag@gnr_conv3d_same", st, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, w, frag, Cin, Cout, K, mode,
+                                                      nchunks, nbt)) return rc;
     gnr_head::Conv1Args a{x, frag, mode ? nullptr : bias, y, B, cin, cout, D, H, W, nchunks, nbt, mask, mode};
-    const long blocks = (long)B * ((W + 7) / 8) * ((H + 7) / 8) * ((D + 3) / 4);
-    HeadScope hs(mode ? "k_conv3d_s1.bwd_data@gnr_conv3d_same" : "k_conv3d_s1.fwd@gnr_conv3d_same", stream);
+    const dim3 grid((unsigned)((long)B * ((W + 7) / 8) * ((H + 7) / 8) * ((D + 3) / 4)), nbt), block(256);
+    const char* label = mode ? "k_conv3d_s1.bwd_data@gnr_conv3d_same" : "k_conv3d_s1.fwd@gnr_conv3d_same";
     if (K == 5) {
-        const size_t lds = (16 * (12 * 12 * 8) + 5 * 256) * sizeof(float);
-        static std::atomic<unsigned long long> attr{0};
-        if (head_attr_needed(attr)) { HCHK(hipFuncSetAttribute((const void*)gnr_head::k_conv3d_s1<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
-        hipLaunchKernelGGL(gnr_head::k_conv3d_s1<5>, dim3((unsigned)blocks, nbt), dim3(256), lds, st, a);
-    } else if (first_gen || (size_t)16 * D * H * W * sizeof(float) >= ((size_t)1 << 31) || (size_t)27 * 4 * nbt * 64 * sizeof(float) >= ((size_t)1 << 31)) {
-        // a chunk's 16 channels do not fit the 32-bit byte offsets of the buffer loads (> 32 M voxels): the first-generation kernel
-        const size_t lds = (16 * (10 * 10 * 6) + 3 * 256) * sizeof(float);
-        static std::atomic<unsigned long long> attr{0};
-        if (head_attr_needed(attr)) { HCHK(hipFuncSetAttribute((const void*)gnr_head::k_conv3d_s1<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
-        hipLaunchKernelGGL(gnr_head::k_conv3d_s1<3>, dim3((unsigned)blocks, nbt), dim3(256), lds, st, a);
-    } else {
-        const size_t lds = (16 * (10 * 10 * 6) + 27 * 256) * sizeof(float);
-        static std::atomic<unsigned long long> attr{0};
-        if (head_attr_needed(attr)) { HCHK(hipFuncSetAttribute((const void*)gnr_head::k_conv3d_s1_k3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
-        hipLaunchKernelGGL(gnr_head::k_conv3d_s1_k3, dim3((unsigned)blocks, nbt), dim3(256), lds, st, a);
+        constexpr size_t lds = (16 * (12 * 12 * 8) + 5 * 256) * sizeof(float);
+        return launch<gnr_head::k_conv3d_s1<5>, lds>(label, st, grid, block, lds, a);
     }
-    HCHK(hipGetLastError());
-    return GNR_OK;
+    if (first_gen || (size_t)16 * D * H * W * sizeof(float) >= ((size_t)1 << 31) || (size_t)27 * 4 * nbt * 64 * sizeof(float) >= ((size_t)1 << 31)) {
+        // a chunk's 16 channels do not fit the 32-bit byte offsets of the buffer loads (> 32 M voxels): the first-generation kernel
+        constexpr size_t lds = (16 * (10 * 10 * 6) + 3 * 256) * sizeof(float);
+        return launch<gnr_head::k_conv3d_s1<3>, lds>(label, st, grid, block, lds, a);
+    }
+    constexpr size_t lds = (16 * (10 * 10 * 6) + 27 * 256) * sizeof(float);
+    return launch<gnr_head::k_conv3d_s1_k3, lds>(label, st, grid, block, lds, a);
+}
+
+extern "C" int gnr_conv3d_same(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int D, int H,
+                               int W, int K, int mode, void* ws, size_t ws_bytes, void* stream) {
+    return gnr_conv3d_same_masked(x, w, bias, y, B, Cin, Cout, D, H, W, K, mode, nullptr, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1231,50 +1177,38 @@ extern "C" size_t gnr_conv3d_same_bwd_weight_workspace_bytes(int B, int Cin, int
 }
 
 // dw [Cout][Cin][K][K][K] is ACCUMULATED (zero it first); K = 3 or 5; workspace = gnr_conv3d_same_bwd_weight_workspace_bytes(...).
-extern "C" int gnr_conv3d_same_bwd_weight_masked(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W,
-                                                 int K, const unsigned* mask, void* ws, size_t ws_bytes, void* stream);
-
-extern "C" int gnr_conv3d_same_bwd_weight(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int K,
-                                          void* ws, size_t ws_bytes, void* stream) {
-    return gnr_conv3d_same_bwd_weight_masked(x, dy, dw, B, Cin, Cout, D, H, W, K, nullptr, ws, ws_bytes, stream);
-}
-
 // `mask` = gnr_conv3d_tap_mask of the layer's weight pattern (or NULL): the gradient of an absent weight is not computed (stays as it was in dw).
 extern "C" int gnr_conv3d_same_bwd_weight_masked(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W,
                                                  int K, const unsigned* mask, void* ws, size_t ws_bytes, void* stream) {
     const bool first_gen = (K & GNR_CONV3D_FIRST_GEN) != 0;
     K &= ~GNR_CONV3D_FIRST_GEN;
-    if (!x || !dy || !dw || !ws || B < 1 || Cin < 1 || Cout < 1 || D < 1 || H < 1 || W < 1 || (K != 3 && K != 5)) return GNR_ERR_ARG;
-    if (ws_bytes < gnr_conv3d_same_bwd_weight_workspace_bytes(B, Cin, Cout, D, H, W, K)) return GNR_ERR_WORKSPACE;
+    if (!x || !dy || !dw || !ws || B < 1 || Cin < 1 || Cout < 1 || D < 1 || H < 1 || W < 1 || (K != 3 && K != 5))
+        return fail(GNR_ERR_ARG, "gnr_conv3d_same_bwd_weight: null pointer, a size below 1 or K not 3 or 5");
+    if (ws_bytes < gnr_conv3d_same_bwd_weight_workspace_bytes(B, Cin, Cout, D, H, W, K)) return fail(GNR_ERR_WORKSPACE, "gnr_conv3d_same_bwd_weight: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int nbi = (Cin + 15) / 16, nbo = (Cout + 15) / 16;
     const long gx = wgrad_grid(B, Cin, Cout, D, H, W);
     float* part = (float*)ws;
-    {
-        HeadScope hs("k_conv3d_wgrad_s1@gnr_conv3d_same_bwd_weight", stream);
-        if (K == 5) {
-            const size_t lds = (16 * (12 * 12 * 8) + 16 * 256) * sizeof(float);
-            static std::atomic<unsigned long long> attr{0};
-            if (head_attr_needed(attr)) { HCHK(hipFuncSetAttribute((const void*)gnr_head::k_conv3d_wgrad_s1<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
-            hipLaunchKernelGGL(gnr_head::k_conv3d_wgrad_s1<5>, dim3((unsigned)gx, nbi * nbo), dim3(256), lds, st, x, dy, part, B, Cin, Cout, D, H, W, nbi, mask);
-        } else if (first_gen || (size_t)16 * D * H * W * sizeof(float) >= ((size_t)1 << 31)) {      // beyond the buffer loads' 32-bit byte offsets
-            const size_t lds = (16 * (10 * 10 * 6) + 16 * 256) * sizeof(float);
-            static std::atomic<unsigned long long> attr{0};
-            if (head_attr_needed(attr)) { HCHK(hipFuncSetAttribute((const void*)gnr_head::k_conv3d_wgrad_s1<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
-            hipLaunchKernelGGL(gnr_head::k_conv3d_wgrad_s1<3>, dim3((unsigned)gx, nbi * nbo), dim3(256), lds, st, x, dy, part, B, Cin, Cout, D, H, W, nbi, mask);
-        } else {
-            const size_t lds = (16 * (10 * 10 * 6) + 16 * 256) * sizeof(float);
-            static std::atomic<unsigned long long> attr{0};
-            if (head_attr_needed(attr)) { HCHK(hipFuncSetAttribute((const void*)gnr_head::k_conv3d_wgrad_k3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
-            hipLaunchKernelGGL(gnr_head::k_conv3d_wgrad_k3, dim3((unsigned)gx, nbi * nbo), dim3(256), lds, st, x, dy, part, B, Cin, Cout, D, H, W, nbi, mask);
-        }
-        HCHK(hipGetLastError());
+    const dim3 grid((unsigned)gx, nbi * nbo), block(256);
+    const char* label = "k_conv3d_wgrad_s1@gnr_conv3d_same_bwd_weight";
+    int rc;
+    if (K == 5) {
+        constexpr size_t lds = (16 * (12 * 12 * 8) + 16 * 256) * sizeof(float);
+        rc = launch<gnr_head::k_conv3d_wgrad_s1<5>, lds>(label, st, grid, block, lds, x, dy, part, B, Cin, Cout, D, H, W, nbi, mask);
+    } else {
+        constexpr size_t lds = (16 * (10 * 10 * 6) + 16 * 256) * sizeof(float);
+        if (first_gen || (size_t)16 * D * H * W * sizeof(float) >= ((size_t)1 << 31))      // beyond the buffer loads' 32-bit byte offsets
+            rc = launch<gnr_head::k_conv3d_wgrad_s1<3>, lds>(label, st, grid, block, lds, x, dy, part, B, Cin, Cout, D, H, W, nbi, mask);
+        else
+            rc = launch<gnr_head::k_conv3d_wgrad_k3, lds>(label, st, grid, block, lds, x, dy, part, B, Cin, Cout, D, H, W, nbi, mask);
     }
-    {
-        HeadScope hs("k_conv3d_wgrad_reduce@gnr_conv3d_same_bwd_weight", stream);
-        const int K3 = K * K * K, n = nbi * nbo * K3 * 256;
-        hipLaunchKernelGGL(gnr_head::k_conv3d_wgrad_reduce, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)part, dw, Cin, Cout, K3, nbi, nbi * nbo, (int)gx);
-        HCHK(hipGetLastError());
-    }
-    return GNR_OK;
+    if (rc) return rc;
+    const int K3 = K * K * K, n = nbi * nbo * K3 * 256;
+    return launch<gnr_head::k_conv3d_wgrad_reduce>("k_conv3d_wgrad_reduce@gnr_conv3d_same_bwd_weight", st, dim3((n + 255) / 256), dim3(256), 0, part, dw, Cin, Cout, K3,
+                                                   nbi, nbi * nbo, (int)gx);
+}
+
+extern "C" int gnr_conv3d_same_bwd_weight(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int K,
+                                          void* ws, size_t ws_bytes, void* stream) {
+    return gnr_conv3d_same_bwd_weight_masked(x, dy, dw, B, Cin, Cout, D, H, W, K, nullptr, ws, ws_bytes, stream);
 }

@@ -13,7 +13,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/gnr.h"
+#include "gnr_host.h"
 
 namespace {
 
@@ -62,15 +62,16 @@ struct Sparse {
 
 extern "C" int gnr_host_randperm_prefix(unsigned char* torch_cpu_rng_state, long long state_bytes, long long n, int k,
                                         long long* out) {
-    if (!torch_cpu_rng_state || (!out && k > 0)) return GNR_ERR_ARG;
-    if (state_bytes != 5056 || n < 1 || k < 0 || k > n || n >= (long long)(0xffffffffu / 20)) return GNR_ERR_SHAPE;
+    if (!torch_cpu_rng_state || (!out && k > 0)) return gnr::fail(GNR_ERR_ARG, "gnr_host_randperm_prefix: null pointer");
+    if (state_bytes != 5056 || n < 1 || k < 0 || k > n || n >= (long long)(0xffffffffu / 20))
+        return gnr::fail(GNR_ERR_SHAPE, "gnr_host_randperm_prefix: state_bytes must be 5056, 0 <= k <= n, 1 <= n < 2^32 / 20");
     Mt g;
     int32_t left, seeded;
     uint64_t next;
     std::memcpy(&left, torch_cpu_rng_state + 8, 4);
     std::memcpy(&seeded, torch_cpu_rng_state + 12, 4);
     std::memcpy(&next, torch_cpu_rng_state + 16, 8);
-    if (!seeded || left < 1 || left > N || next > (uint64_t)N) return GNR_ERR_SHAPE;
+    if (!seeded || left < 1 || left > N || next > (uint64_t)N) return gnr::fail(GNR_ERR_SHAPE, "gnr_host_randperm_prefix: not the state of a seeded mt19937 CPU generator");
     for (int i = 0; i < N; ++i) {
         uint64_t w;
         std::memcpy(&w, torch_cpu_rng_state + 24 + 8 * i, 8);

@@ -10,19 +10,12 @@
 // between the statistics and the apply pass; no LDS tiles, no MFMA.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
-#include "../../include/gnr.h"
+#include "gnr_host.h"
 
 namespace gnr_img {
 
-static thread_local char g_err[256] = "";
-static int fail(int code, const char* what) { snprintf(g_err, sizeof(g_err), "%s", what); return code; }
-static int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e)); return GNR_ERR_HIP; }
-    return GNR_OK;
-}
+using namespace gnr;
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -332,7 +325,7 @@ using namespace gnr_img;
 
 extern "C" {
 
-const char* gnr_img_last_error(void) { return g_err; }
+const char* gnr_img_last_error(void) { return gnr_last_error(); }             // alias: the library has one error text
 
 int gnr_instnorm_act(const float* x, const float* res, const float* weight, const float* bias, float* y, float* mean, float* rstd,
                      long long planes, int C, int HW, float eps, int act, void* stream) {
@@ -345,12 +338,11 @@ int gnr_instnorm_act(const float* x, const float* res, const float* weight, cons
     const bool vec = HW % 4 == 0 && aligned16(x) && aligned16(y) && (!res || aligned16(res));
     const int n4 = HW / 4;
     const dim3 grid((unsigned)planes);
-    if (vec && n4 <= 64 * 3) k_in_fwd<64, 3><<<grid, 64, 0, st>>>(a);
-    else if (vec && n4 <= 256 * 3) k_in_fwd<256, 3><<<grid, 256, 0, st>>>(a);
-    else if (vec && n4 <= 256 * 9) k_in_fwd<256, 9><<<grid, 256, 0, st>>>(a);
-    else if (vec && n4 <= 1024 * 9) k_in_fwd<1024, 9><<<grid, 1024, 0, st>>>(a);
-    else k_in_fwd_any<<<grid, 256, 0, st>>>(a);
-    return launched("gnr_instnorm_act");
+    if (vec && n4 <= 64 * 3) return launch<k_in_fwd<64, 3>>(nullptr, st, grid, dim3(64), 0, a);
+    if (vec && n4 <= 256 * 3) return launch<k_in_fwd<256, 3>>(nullptr, st, grid, dim3(256), 0, a);
+    if (vec && n4 <= 256 * 9) return launch<k_in_fwd<256, 9>>(nullptr, st, grid, dim3(256), 0, a);
+    if (vec && n4 <= 1024 * 9) return launch<k_in_fwd<1024, 9>>(nullptr, st, grid, dim3(1024), 0, a);
+    return launch<k_in_fwd_any>(nullptr, st, grid, dim3(256), 0, a);
 }
 
 int gnr_instnorm_act_bwd(const float* dy, const float* out, const float* x, const float* mean, const float* rstd, const float* weight,
@@ -361,19 +353,23 @@ int gnr_instnorm_act_bwd(const float* dy, const float* out, const float* x, cons
     if (planes < 0 || C <= 0 || HW <= 0 || planes % C != 0 || act < GNR_ACT_NONE || act > GNR_ACT_ELU || planes > 0x7fffffffLL)
         return fail(GNR_ERR_SHAPE, "gnr_instnorm_act_bwd: planes must be a multiple of C > 0, HW > 0, act in {0,1,2}");
     hipStream_t st = (hipStream_t)stream;
-    if (planes == 0) return hipMemsetAsync(dweight, 0, sizeof(float) * C, st) == hipSuccess && hipMemsetAsync(dbias, 0, sizeof(float) * C, st) == hipSuccess
-                                ? GNR_OK : fail(GNR_ERR_HIP, "gnr_instnorm_act_bwd: hipMemsetAsync");
+    if (planes == 0) {
+        GNR_HIP(hipMemsetAsync(dweight, 0, sizeof(float) * C, st));
+        GNR_HIP(hipMemsetAsync(dbias, 0, sizeof(float) * C, st));
+        return GNR_OK;
+    }
     InBwdArgs a{dy, out, x, mean, rstd, weight, dx, dres, s1, s2, C, HW, act};
     const bool vec = HW % 4 == 0 && aligned16(dy) && aligned16(x) && aligned16(dx) && (!out || aligned16(out)) && (!dres || aligned16(dres));
     const int n4 = HW / 4;
     const dim3 grid((unsigned)planes);
-    if (vec && n4 <= 64 * 3) k_in_bwd<64, 3><<<grid, 64, 0, st>>>(a);
-    else if (vec && n4 <= 256 * 3) k_in_bwd<256, 3><<<grid, 256, 0, st>>>(a);
-    else if (vec && n4 <= 256 * 9) k_in_bwd<256, 9><<<grid, 256, 0, st>>>(a);
-    else if (vec && n4 <= 1024 * 9) k_in_bwd<1024, 9><<<grid, 1024, 0, st>>>(a);
-    else k_in_bwd_any<<<grid, 256, 0, st>>>(a);
-    k_in_wb<<<dim3((unsigned)(C + 63) / 64), 64, 0, st>>>(s1, s2, dweight, dbias, (int)(planes / C), C);
-    return launched("gnr_instnorm_act_bwd");
+    int rc;
+    if (vec && n4 <= 64 * 3) rc = launch<k_in_bwd<64, 3>>(nullptr, st, grid, dim3(64), 0, a);
+    else if (vec && n4 <= 256 * 3) rc = launch<k_in_bwd<256, 3>>(nullptr, st, grid, dim3(256), 0, a);
+    else if (vec && n4 <= 256 * 9) rc = launch<k_in_bwd<256, 9>>(nullptr, st, grid, dim3(256), 0, a);
+    else if (vec && n4 <= 1024 * 9) rc = launch<k_in_bwd<1024, 9>>(nullptr, st, grid, dim3(1024), 0, a);
+    else rc = launch<k_in_bwd_any>(nullptr, st, grid, dim3(256), 0, a);
+    if (rc) return rc;
+    return launch<k_in_wb>(nullptr, st, dim3((unsigned)(C + 63) / 64), dim3(64), 0, s1, s2, dweight, dbias, (int)(planes / C), C);
 }
 
 static int pad_args(const void* a, const void* b, long long planes, int H, int W, int pad, const char* who) {
@@ -388,8 +384,7 @@ int gnr_reflect_pad2d(const float* x, float* y, long long planes, int H, int W, 
     const unsigned long long total = (unsigned long long)planes * (H + 2 * pad) * groups;
     if (total > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_reflect_pad2d: too many pixels for one launch");
     if (total == 0) return GNR_OK;
-    k_reflect_pad<<<dim3((unsigned)((total + 255) / 256)), 256, 0, (hipStream_t)stream>>>(x, y, H, W, pad, groups, (unsigned)total);
-    return launched("gnr_reflect_pad2d");
+    return launch<k_reflect_pad>(nullptr, (hipStream_t)stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, x, y, H, W, pad, groups, (unsigned)total);
 }
 
 int gnr_reflect_pad2d_bwd(const float* dy, float* dx, long long planes, int H, int W, int pad, void* stream) {
@@ -398,8 +393,7 @@ int gnr_reflect_pad2d_bwd(const float* dy, float* dx, long long planes, int H, i
     const unsigned long long total = (unsigned long long)planes * H * groups;
     if (total > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_reflect_pad2d_bwd: too many pixels for one launch");
     if (total == 0) return GNR_OK;
-    k_reflect_pad_bwd<<<dim3((unsigned)((total + 255) / 256)), 256, 0, (hipStream_t)stream>>>(dy, dx, H, W, pad, groups, (unsigned)total);
-    return launched("gnr_reflect_pad2d_bwd");
+    return launch<k_reflect_pad_bwd>(nullptr, (hipStream_t)stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, dy, dx, H, W, pad, groups, (unsigned)total);
 }
 
 int gnr_upsample2x_bilinear(const float* x, float* y, long long planes, int H, int W, void* stream) {
@@ -412,13 +406,11 @@ int gnr_upsample2x_bilinear(const float* x, float* y, long long planes, int H, i
     if (W % 2 == 0 && aligned16(y)) {
         const unsigned long long blocks = (total / 4 + 255) / 256;
         if (blocks > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_upsample2x_bilinear: too large for one launch");
-        k_upsample2x<<<dim3((unsigned)blocks), 256, 0, st>>>(x, y, H, W, sh, sw, (size_t)(total / 4));
-    } else {
-        const unsigned long long blocks = (total + 255) / 256;
-        if (blocks > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_upsample2x_bilinear: too large for one launch");
-        k_upsample2x_any<<<dim3((unsigned)blocks), 256, 0, st>>>(x, y, H, W, sh, sw, (size_t)total);
+        return launch<k_upsample2x>(nullptr, st, dim3((unsigned)blocks), dim3(256), 0, x, y, H, W, sh, sw, (size_t)(total / 4));
     }
-    return launched("gnr_upsample2x_bilinear");
+    const unsigned long long blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_upsample2x_bilinear: too large for one launch");
+    return launch<k_upsample2x_any>(nullptr, st, dim3((unsigned)blocks), dim3(256), 0, x, y, H, W, sh, sw, (size_t)total);
 }
 
 }  // extern "C"

@@ -9,14 +9,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
-#include "../../include/gnr.h"
+#include "gnr_host.h"
 
 namespace gnr_ingest {
 
-static thread_local char g_err[256] = "";
-static int fail(int code, const char* what) { snprintf(g_err, sizeof(g_err), "%s", what); return code; }
+using namespace gnr;
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -100,7 +98,7 @@ using namespace gnr_ingest;
 
 extern "C" {
 
-const char* gnr_ingest_last_error(void) { return g_err; }
+const char* gnr_ingest_last_error(void) { return gnr_last_error(); }       // alias: the library has one error text
 
 size_t gnr_ingest_tables_bytes(int dst_h, int dst_w) {
     if (dst_h < 1 || dst_w < 1 || dst_h > GNR_INGEST_MAX_DIM || dst_w > GNR_INGEST_MAX_DIM) return 0;
@@ -139,11 +137,8 @@ int gnr_ingest_u8(const unsigned char* frames, int n, int src_h, int src_w, int 
            src_h, src_w, channels, dst_h, dst_w, groups, (unsigned)total};
     const dim3 grid((unsigned)((total + 255) / 256));
     hipStream_t st = (hipStream_t)stream;
-    if (dst_w % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) k_ingest_u8<true><<<grid, 256, 0, st>>>(a);
-    else k_ingest_u8<false><<<grid, 256, 0, st>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { snprintf(g_err, sizeof(g_err), "gnr_ingest_u8: %s", hipGetErrorString(e)); return GNR_ERR_HIP; }
-    return GNR_OK;
+    if (dst_w % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) return launch<k_ingest_u8<true>>(nullptr, st, grid, dim3(256), 0, a);
+    return launch<k_ingest_u8<false>>(nullptr, st, grid, dim3(256), 0, a);
 }
 
 }  // extern "C"

@@ -15,28 +15,11 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../../include/gnr.h"
-
-// the library's error text and per-launch timing brackets live in gnr_capi.inc (gnr_last_error, gnr_timing_*): not part of the public ABI
-extern "C" int gnr_internal_fail(int code, const char* what, int hip_error);
-extern "C" int gnr_internal_timing_open(const char* label, void* stream);
-extern "C" void gnr_internal_timing_close(int idx, void* stream);
+#include "gnr_host.h"
 
 namespace gnr_metrics {
 
-static int fail(int code, const char* what) { return gnr_internal_fail(code, what, 0); }
-
-// gnr_capi.inc's launch<> for this translation unit: the timing bracket around the launch alone, then the launch's own error check
-template <auto Kernel, typename... Args>
-static int launch(const char* label, hipStream_t st, dim3 grid, dim3 block, size_t lds_bytes, Args... args) {
-    const int idx = gnr_internal_timing_open(label, st);
-    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
-    gnr_internal_timing_close(idx, st);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GNR_OK : gnr_internal_fail(GNR_ERR_HIP, label, (int)e);
-}
-
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+using namespace gnr;
 
 constexpr int PIX_PER_BLOCK = 1024;                 // k_frame_pixels: 256 lanes x 4 pixels
 constexpr int WIN = 11, HALO = WIN - 1;             // SSIM window; a tile of TH x TW window positions reads (TH + 10) x (TW + 10) pixels
@@ -238,7 +221,7 @@ __global__ __launch_bounds__(256) void k_frame_finish(Dims d, Work k, int ssim, 
 }
 
 static int check_dims(const char* who, int B, int h, int w, int n_pred, int hm, int wm, int ssim, Dims* out) {
-    static thread_local char msg[160];
+    char msg[160];                                          // (fail() copies the text)
     auto say = [&](int code, const char* what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return fail(code, msg); };
     if (n_pred < 1 || n_pred > GNR_METRICS_MAX_PRED) return say(GNR_ERR_ARG, "n_pred must be in 1..4");
     if (B < 1 || B > 65535 || h < 1 || w < 1 || (long long)h * w > (1ll << 31) - PIX_PER_BLOCK)
@@ -276,8 +259,7 @@ int gnr_frame_metrics(const float* gt, const float* const* preds, int n_pred, co
     const Work k = carve(d, ssim != 0, workspace);
     if (workspace_bytes < k.total) return fail(GNR_ERR_WORKSPACE, "gnr_frame_metrics: workspace smaller than gnr_frame_metrics_workspace_bytes()");
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(workspace, 0, k.zero_bytes, st);
-    if (e != hipSuccess) return gnr_internal_fail(GNR_ERR_HIP, "gnr_frame_metrics: hipMemsetAsync", (int)e);
+    if (const hipError_t e = hipMemsetAsync(workspace, 0, k.zero_bytes, st)) return fail(GNR_ERR_HIP, "gnr_frame_metrics: hipMemsetAsync", e);
     if (int rc = launch<k_frame_pixels>("k_frame_pixels@gnr_frame_metrics", st, dim3(d.nblk, B), dim3(256), 0, gt, pr, depth_pr, depth_gt, d, k)) return rc;
     if (ssim)
         if (int rc = launch<k_frame_ssim>("k_frame_ssim@gnr_frame_metrics", st, dim3(d.tx * d.ty, n_pred, B), dim3(256), 0, gt, pr, d, k)) return rc;

@@ -7,7 +7,7 @@
 #include <cstring>
 
 #include "gnr_pack_body.h"
-#include "../../include/gnr.h"
+#include "gnr_host.h"
 
 namespace {
 using namespace gnr;
@@ -55,7 +55,7 @@ extern "C" int gnr_packed_bwd_floats(void) { return gnr::pkb::TOTAL; }
 
 // Transposed fragments for the backward twins (see gnr_layout.h, namespace pkb)
 extern "C" int gnr_pack_weights_bwd(const float* c, float* p) {
-    if (!c || !p) return GNR_ERR_ARG;
+    if (!c || !p) return gnr::fail(GNR_ERR_ARG, "gnr_pack_weights_bwd: null pointer");
     std::memset(p, 0, sizeof(float) * gnr::pkb::TOTAL);
     gnr::packer::pack_backward(gnr::packer::HostExec(), c, p);
     gnr::packer::pack_backward_pairs(gnr::packer::HostExec(), p);
@@ -65,7 +65,7 @@ extern "C" int gnr_pack_weights_bwd(const float* c, float* p) {
 // The fourth decoder branch's transposed fragments (use_vis training) into a blob of gnr_pack_weights_bwd.  v as in
 // gnr_pack_vis_decoder (state-dict order, 2 145 floats).
 extern "C" int gnr_pack_vis_decoder_bwd(const float* v, float* p) {
-    if (!v || !p) return GNR_ERR_ARG;
+    if (!v || !p) return gnr::fail(GNR_ERR_ARG, "gnr_pack_vis_decoder_bwd: null pointer");
     gnr::packer::pack_vis_backward(gnr::packer::HostExec(), v, p);
     gnr::packer::pack_vis_backward_pairs(gnr::packer::HostExec(), p);
     return GNR_OK;
@@ -76,7 +76,7 @@ extern "C" int gnr_canonical_weights_floats(void) { return gnr::can::TOTAL; }
 extern "C" int gnr_packed_weights_floats(void) { return gnr::pk::TOTAL; }
 
 extern "C" int gnr_pack_weights(const float* c, float* p) {
-    if (!c || !p) return GNR_ERR_ARG;
+    if (!c || !p) return gnr::fail(GNR_ERR_ARG, "gnr_pack_weights: null pointer");
     using namespace gnr;
     std::memset(p, 0, sizeof(float) * pk::TOTAL);
     packer::pack_forward(packer::HostExec(), c, p);
@@ -93,7 +93,7 @@ extern "C" int gnr_pack_weights(const float* c, float* p) {
 // already packed blob.  v = vis_decoder.{0.weight [32][32], 0.bias [32], 2.weight [32][32], 2.bias [32], 4.weight [1][32],
 // 4.bias [1]} in state-dict order (2 145 floats).  Sets the flag k_chain tests.
 extern "C" int gnr_pack_vis_decoder(const float* v, float* p) {
-    if (!v || !p) return GNR_ERR_ARG;
+    if (!v || !p) return gnr::fail(GNR_ERR_ARG, "gnr_pack_vis_decoder: null pointer");
     gnr::packer::pack_vis(gnr::packer::HostExec(), v, p);
     return build_c16(p);
 }

@@ -10,7 +10,7 @@
 
 #define GNR_HD __host__ __device__
 #include "gnr_pack_body.h"
-#include "../../include/gnr.h"
+#include "gnr_host.h"
 
 namespace gnr {
 namespace {
@@ -27,38 +27,40 @@ __global__ __launch_bounds__(256) void k_pack_backward_pairs(float* p) { packer:
 __global__ __launch_bounds__(256) void k_pack_vis_backward_pairs(float* p) { packer::pack_vis_backward_pairs(dev_exec(), p); }
 
 constexpr int PACK_BLOCKS = 64, PACK_THREADS = 256;       // 16 384 threads: the largest fragment (HOIST, 9 216 entries) in one sweep
+template <auto Kernel, typename... Args>
+int pack(hipStream_t st, Args... args) { return launch<Kernel>(nullptr, st, dim3(PACK_BLOCKS), dim3(PACK_THREADS), 0, args...); }
+
 int c16_image(float* p, hipStream_t st) {
-    hipLaunchKernelGGL(k_pack_c16_copy, dim3(PACK_BLOCKS), dim3(PACK_THREADS), 0, st, p);
-    hipLaunchKernelGGL(k_pack_c16_pairs, dim3(PACK_BLOCKS), dim3(PACK_THREADS), 0, st, p);
-    return hipGetLastError() == hipSuccess ? GNR_OK : GNR_ERR_HIP;
+    if (int rc = pack<k_pack_c16_copy>(st, p)) return rc;
+    return pack<k_pack_c16_pairs>(st, p);
 }
 }  // namespace
 }  // namespace gnr
 
+using namespace gnr;
+
 extern "C" int gnr_pack_weights_device(const float* canonical_dev, float* packed_dev, void* stream) {
-    if (!canonical_dev || !packed_dev) return GNR_ERR_ARG;
+    if (!canonical_dev || !packed_dev) return fail(GNR_ERR_ARG, "gnr_pack_weights_device: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gnr::k_pack_forward, dim3(gnr::PACK_BLOCKS), dim3(gnr::PACK_THREADS), 0, st, canonical_dev, packed_dev);
-    return gnr::c16_image(packed_dev, st);
+    if (int rc = pack<k_pack_forward>(st, canonical_dev, packed_dev)) return rc;
+    return c16_image(packed_dev, st);
 }
 
 extern "C" int gnr_pack_vis_decoder_device(const float* vis_decoder_dev, float* packed_dev, void* stream) {
-    if (!vis_decoder_dev || !packed_dev) return GNR_ERR_ARG;
+    if (!vis_decoder_dev || !packed_dev) return fail(GNR_ERR_ARG, "gnr_pack_vis_decoder_device: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gnr::k_pack_vis, dim3(gnr::PACK_BLOCKS), dim3(gnr::PACK_THREADS), 0, st, vis_decoder_dev, packed_dev);
-    return gnr::c16_image(packed_dev, st);
+    if (int rc = pack<k_pack_vis>(st, vis_decoder_dev, packed_dev)) return rc;
+    return c16_image(packed_dev, st);
 }
 
 extern "C" int gnr_pack_weights_bwd_device(const float* canonical_dev, float* packed_bwd_dev, void* stream) {
-    if (!canonical_dev || !packed_bwd_dev) return GNR_ERR_ARG;
-    hipLaunchKernelGGL(gnr::k_pack_backward, dim3(gnr::PACK_BLOCKS), dim3(gnr::PACK_THREADS), 0, (hipStream_t)stream, canonical_dev, packed_bwd_dev);
-    hipLaunchKernelGGL(gnr::k_pack_backward_pairs, dim3(gnr::PACK_BLOCKS), dim3(gnr::PACK_THREADS), 0, (hipStream_t)stream, packed_bwd_dev);
-    return hipGetLastError() == hipSuccess ? GNR_OK : GNR_ERR_HIP;
+    if (!canonical_dev || !packed_bwd_dev) return fail(GNR_ERR_ARG, "gnr_pack_weights_bwd_device: null pointer");
+    if (int rc = pack<k_pack_backward>((hipStream_t)stream, canonical_dev, packed_bwd_dev)) return rc;
+    return pack<k_pack_backward_pairs>((hipStream_t)stream, packed_bwd_dev);
 }
 
 extern "C" int gnr_pack_vis_decoder_bwd_device(const float* vis_decoder_dev, float* packed_bwd_dev, void* stream) {
-    if (!vis_decoder_dev || !packed_bwd_dev) return GNR_ERR_ARG;
-    hipLaunchKernelGGL(gnr::k_pack_vis_backward, dim3(gnr::PACK_BLOCKS), dim3(gnr::PACK_THREADS), 0, (hipStream_t)stream, vis_decoder_dev, packed_bwd_dev);
-    hipLaunchKernelGGL(gnr::k_pack_vis_backward_pairs, dim3(gnr::PACK_BLOCKS), dim3(gnr::PACK_THREADS), 0, (hipStream_t)stream, packed_bwd_dev);
-    return hipGetLastError() == hipSuccess ? GNR_OK : GNR_ERR_HIP;
+    if (!vis_decoder_dev || !packed_bwd_dev) return fail(GNR_ERR_ARG, "gnr_pack_vis_decoder_bwd_device: null pointer");
+    if (int rc = pack<k_pack_vis_backward>((hipStream_t)stream, vis_decoder_dev, packed_bwd_dev)) return rc;
+    return pack<k_pack_vis_backward_pairs>((hipStream_t)stream, packed_bwd_dev);
 }

@@ -4,14 +4,12 @@
 // every axis (ni_filters.c, symmetric branch); dilation and the max filter are exact by nature.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
-#include "../../include/gnr.h"
+#include "gnr_host.h"
 
 namespace gnr_post {
 
-static thread_local char g_err[256] = "";
-static int fail(int code, const char* what) { snprintf(g_err, sizeof(g_err), "%s", what); return code; }
+using namespace gnr;
 
 struct GaussW { double w[GNR_GAUSS_MAX_RADIUS + 1]; int radius; };
 
@@ -125,13 +123,11 @@ __global__ __launch_bounds__(1024) void k_compact(const unsigned char* __restric
     if (threadIdx.x == 0) count[b] = base_s;
 }
 
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace gnr_post
 
 using namespace gnr_post;
 
-extern "C" const char* gnr_post_last_error(void) { return g_err; }
+extern "C" const char* gnr_post_last_error(void) { return gnr_last_error(); }       // alias: the library has one error text
 
 extern "C" size_t gnr_grasp_select_workspace_bytes(int B, int R) {
     if (B < 1 || R < 1) return 0;
@@ -162,19 +158,17 @@ extern "C" int gnr_grasp_select_fwd(const float* tsdf, const float* qual, const 
     g.radius = p->gauss_radius;
     for (int k = 0; k <= GNR_GAUSS_MAX_RADIUS; ++k) g.w[k] = k <= p->gauss_radius ? p->gauss_w[k] : 0.0;
     // Gaussian, axes in scipy's order (0, 1, 2), fp32 rounding after each
-    hipLaunchKernelGGL(k_gauss_axis, dim3(blocks), dim3(256), 0, st, qual, fa, R, R * R, g, n);
-    hipLaunchKernelGGL(k_gauss_axis, dim3(blocks), dim3(256), 0, st, fa, fb, R, R, g, n);
-    hipLaunchKernelGGL(k_gauss_axis, dim3(blocks), dim3(256), 0, st, fb, fa, R, 1, g, n);
-    hipLaunchKernelGGL(k_masks, dim3(blocks), dim3(256), 0, st, tsdf, xa, mk, p->tsdf_thres_high, p->tsdf_thres_low, n);
+    const dim3 grid(blocks), block(256);
+    if (int rc = launch<k_gauss_axis>(nullptr, st, grid, block, 0, qual, fa, R, R * R, g, n)) return rc;
+    if (int rc = launch<k_gauss_axis>(nullptr, st, grid, block, 0, fa, fb, R, R, g, n)) return rc;
+    if (int rc = launch<k_gauss_axis>(nullptr, st, grid, block, 0, fb, fa, R, 1, g, n)) return rc;
+    if (int rc = launch<k_masks>(nullptr, st, grid, block, 0, tsdf, xa, mk, p->tsdf_thres_high, p->tsdf_thres_low, n)) return rc;
     unsigned char *xin = xa, *xout = xb;
     for (int it = 0; it < p->dilate_iterations; ++it) {
-        hipLaunchKernelGGL(k_dilate, dim3(blocks), dim3(256), 0, st, xin, mk, xout, R, n);
+        if (int rc = launch<k_dilate>(nullptr, st, grid, block, 0, xin, mk, xout, R, n)) return rc;
         unsigned char* tmp = xin; xin = xout; xout = tmp;
     }
-    hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(256), 0, st, fa, xin, width, qual_out, fb, p->min_width, p->max_width,
-                       p->threshold, n);
-    hipLaunchKernelGGL(k_nms, dim3(blocks), dim3(256), 0, st, fb, xout, R, p->max_filter_size, n);
-    hipLaunchKernelGGL(k_compact, dim3(B), dim3(1024), 0, st, xout, fb, rot, width, R, max_n, count, index, score, quat, width_out);
-    if (hipGetLastError() != hipSuccess) return fail(GNR_ERR_HIP, "gnr_grasp_select_fwd: launch failed");
-    return GNR_OK;
+    if (int rc = launch<k_finalize>(nullptr, st, grid, block, 0, fa, xin, width, qual_out, fb, p->min_width, p->max_width, p->threshold, n)) return rc;
+    if (int rc = launch<k_nms>(nullptr, st, grid, block, 0, fb, xout, R, p->max_filter_size, n)) return rc;
+    return launch<k_compact>(nullptr, st, dim3(B), dim3(1024), 0, xout, fb, rot, width, R, max_n, count, index, score, quat, width_out);
 }

@@ -31,8 +31,7 @@ def pack(canonical):
     canonical = np.ascontiguousarray(canonical, np.float32)
     out = np.zeros(L.gnr_head_packed_floats(), np.float32)
     rc = L.gnr_pack_grasp_head(canonical.ctypes.data_as(_lib.c_float_p), out.ctypes.data_as(_lib.c_float_p))
-    if rc:
-        raise _lib.GnrError(f'gnr_pack_grasp_head failed: {rc}')
+    _lib.check(rc, 'gnr_pack_grasp_head')
     return out
 
 
@@ -79,9 +78,7 @@ class GraspHead:
         rc = self.L.gnr_grasp_head_fwd(B, R, vol.data_ptr(), self.w.data_ptr(), q.data_ptr(), r.data_ptr(), w.data_ptr(),
                                        self._ws.data_ptr(), self._ws.numel(),
                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc:
-            raise _lib.GnrError(f'gnr_grasp_head_fwd failed: {_lib.ERRORS.get(rc, rc)} '
-                                f'({self.L.gnr_head_last_error().decode(errors="replace")})')
+        _lib.check(rc, 'gnr_grasp_head_fwd')
         return q, r, w
 
     def activations(self, B, R):

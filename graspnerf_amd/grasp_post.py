@@ -61,8 +61,7 @@ class GraspSelector:
                                          out['index'].data_ptr(), out['score'].data_ptr(), out['quat'].data_ptr(),
                                          out['width'].data_ptr(), M, self._ws.data_ptr(), self._ws.numel(),
                                          C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
-        if rc:
-            raise _lib.GnrError(f'gnr_grasp_select_fwd failed: {rc} ({self.L.gnr_post_last_error().decode()})')
+        _lib.check(rc, 'gnr_grasp_select_fwd')
         return out
 
 

@@ -35,8 +35,7 @@ def tables_host(src_hw, dst_hw):
     nbytes = L.gnr_ingest_tables_bytes(dh, dw)
     blob = np.empty(max(nbytes, 4) // 4, np.int32)
     rc = L.gnr_ingest_tables_host(sh, sw, dh, dw, blob.ctypes.data_as(C.c_void_p) if nbytes else None)
-    if rc:
-        raise _lib.GnrError(f'gnr_ingest_tables_host failed: {_lib.ERRORS.get(rc, rc)} ({L.gnr_ingest_last_error().decode()})')
+    _lib.check(rc, 'gnr_ingest_tables_host')
     return blob
 
 
@@ -76,6 +75,5 @@ class DeviceIngest:
             raise ValueError(f'out must be a contiguous float32 tensor [{n},3,{dh},{dw}] on {self.device}')
         rc = self.L.gnr_ingest_u8(frames.data_ptr(), n, h, w, c, frames.stride(1), frames.stride(0), tab.data_ptr(), out.data_ptr(),
                                   dh, dw, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc:
-            raise _lib.GnrError(f'gnr_ingest_u8 failed: {_lib.ERRORS.get(rc, rc)} ({self.L.gnr_ingest_last_error().decode()})')
+        _lib.check(rc, 'gnr_ingest_u8')
         return out

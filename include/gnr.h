@@ -30,6 +30,10 @@ extern "C" {
 #define GNR_ERR_SHAPE (-2)     /* unsupported V, dn, feature width ...                      */
 #define GNR_ERR_HIP (-3)       /* a HIP call or kernel launch failed                        */
 #define GNR_ERR_WORKSPACE (-4) /* workspace too small                                       */
+/* One error text per thread for the whole library: after a call that returned an error, gnr_last_error() names the refusal, or
+ * the kernel launch / HIP call that failed and hipGetErrorString of its error ("<label or call>: <text>").  gnr_head_last_error,
+ * gnr_post_last_error, gnr_img_last_error and gnr_ingest_last_error are aliases of it, kept for existing callers: all five return
+ * the text of the thread's last failed call, whichever source file its entry point lives in. */
 
 /* Reference views of B scenes.  Replaces the `ref_imgs_info` dict
  * (ref: src/nr/utils/imgs_info.py:120, src/nr/main.py:228-242) after the 2D backbones
@@ -295,7 +299,7 @@ int gnr_pack_grasp_head(const float* canonical_host, float* packed_host);
 size_t gnr_grasp_head_workspace_bytes(int B, int volume_res);
 int gnr_grasp_head_fwd(int B, int volume_res, const float* volume, const float* packed_head, float* qual, float* rot,
                        float* width, void* workspace, size_t workspace_bytes, void* stream);
-const char* gnr_head_last_error(void);
+const char* gnr_head_last_error(void);       /* alias of gnr_last_error() */
 /* Weight gradient of a stride-1, padding K/2 3D convolution (the grasp head under autograd; MIOpen spends 75 ms on the
  * fused 16 -> 6 k5 head at 40^3, batch 8): dw [Cout,Cin,K,K,K] is ACCUMULATED; x [B,Cin,D,H,W], dy [B,Cout,D,H,W]. */
 int gnr_conv3d_bwd_weight(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int K,
@@ -345,11 +349,11 @@ int gnr_conv3d_same_bwd_weight_masked(const float* x, const float* dy, float* dw
  * gnr_reflect_pad2d: F.pad(x, (pad,)*4, mode='reflect') as nn.Conv2d(padding_mode='reflect') applies it (ops.py:8,134,163):
  *   y [planes][H+2 pad][W+2 pad];  pad < min(H, W).  _bwd: dx[h][w] = sum of dy over the padded positions reading x[h][w].
  * gnr_upsample2x_bilinear: F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True) (ops.py:147): y [planes][2H][2W].
- * All return GNR_OK / GNR_ERR_ARG (null pointer) / GNR_ERR_SHAPE / GNR_ERR_HIP; text in gnr_img_last_error(). */
+ * All return GNR_OK / GNR_ERR_ARG (null pointer) / GNR_ERR_SHAPE / GNR_ERR_HIP; text in gnr_last_error(). */
 #define GNR_ACT_NONE 0
 #define GNR_ACT_RELU 1
 #define GNR_ACT_ELU 2
-const char* gnr_img_last_error(void);
+const char* gnr_img_last_error(void);        /* alias of gnr_last_error() */
 int gnr_instnorm_act(const float* x, const float* res, const float* weight, const float* bias, float* y, float* mean, float* rstd,
                      long long planes, int C, int HW, float eps, int act, void* stream);
 int gnr_instnorm_act_bwd(const float* dy, const float* out, const float* x, const float* mean, const float* rstd, const float* weight,
@@ -370,13 +374,13 @@ int gnr_upsample2x_bilinear(const float* x, float* y, long long planes, int H, i
  * frames: DEVICE uint8, `channels` = 3 or 4 interleaved (a 4th channel is ignored), row y of frame f at
  * frames + f * frame_pitch + y * row_pitch (pitches in bytes).  Stream-ordered, no allocation, no host synchronisation.
  * GNR_ERR_ARG: null pointer, channels not 3 / 4, a pitch shorter than the row / frame it strides;  GNR_ERR_SHAPE: n < 1, a
- * dimension outside 1..16384, more than 2^31 - 1 groups of four output pixels;  text in gnr_ingest_last_error(). */
+ * dimension outside 1..16384, more than 2^31 - 1 groups of four output pixels;  text in gnr_last_error(). */
 #define GNR_INGEST_MAX_DIM 16384
 size_t gnr_ingest_tables_bytes(int dst_h, int dst_w);
 int gnr_ingest_tables_host(int src_h, int src_w, int dst_h, int dst_w, void* tables_host);
 int gnr_ingest_u8(const unsigned char* frames, int n, int src_h, int src_w, int channels, size_t row_pitch, size_t frame_pitch,
                   const void* tables_dev, float* out, int dst_h, int dst_w, void* stream);
-const char* gnr_ingest_last_error(void);
+const char* gnr_ingest_last_error(void);     /* alias of gnr_last_error() */
 
 /* ---- frame metrics of a validation pass (csrc/gnr_metrics.hip) ---------------------------------------------------
  * The reference's PSNR_SSIM metric (network/metrics.py:14-30,40-84) for B full frames at once, all on the device:
@@ -558,10 +562,10 @@ size_t gnr_grasp_select_workspace_bytes(int B, int R);
 int gnr_grasp_select_fwd(const float* tsdf, const float* qual, const float* rot, const float* width, int B, int R,
                          const GnrSelectParams* params, float* qual_out, int* count, int* index, float* score,
                          float* quat, float* width_out, int max_n, void* workspace, size_t workspace_bytes, void* stream);
-const char* gnr_post_last_error(void);
+const char* gnr_post_last_error(void);       /* alias of gnr_last_error() */
 
 /* ---- introspection / measurement -------------------------------------------------------*/
-/* name of the dominant kernel as it appears in rocprofv3 traces, and the last HIP error text */
+/* name of the dominant kernel as it appears in rocprofv3 traces, and the calling thread's last error text (see GNR_ERR_*) */
 const char* gnr_dominant_kernel_name(void);
 const char* gnr_last_error(void);
 /* In-situ timing (process-wide switch, measurement only): between gnr_timing_begin() and gnr_timing_end() every kernel

@@ -1,7 +1,9 @@
-"""What the host layer between include/gnr.h and the kernels (csrc/gnr_capi.inc) promises its callers besides values: every entry
-point that takes a GnrScene refuses a bad call with the documented status code and text BEFORE anything touches the device, and every
-kernel launch is bracketed under a fixed timing label (bench.py, tools/ab_*.py and the profiles key on them)."""
+"""What the host layer between include/gnr.h and the kernels (csrc/gnr_capi.inc, csrc/gnr_host.h) promises its callers besides values:
+every entry point refuses a bad call with the documented status code and text BEFORE anything touches the device, the text is ONE
+string per thread whichever source file the entry point lives in, and every kernel launch is bracketed under a fixed timing label
+(bench.py, tools/ab_*.py and the profiles key on them)."""
 import ctypes as C
+import threading
 
 import numpy as np
 import pytest
@@ -201,6 +203,102 @@ def test_scene_entry_points_refuse_before_touching_the_device():
     refused(WORKSPACE, 'gnr_depth_mean_bwd: scratch too small', mean_bwd, scratch_bytes=dm_scratch - 1, d_ray_feats=None)
 
 
+# ---- one error text for every source file of the library -------------------------------------------------------------------------
+def _unit_refusals():
+    """(unit's reader, call, status, text): refusals of the entry points that live outside gnr_capi.inc, the calls of test_grasp_head,
+    test_backbone_ops, test_ingest and test_frame_metrics.  The texts are what the library built from the commit before the units shared
+    one error text left in the unit's OWN reader (gnr_metrics.hip already wrote gnr_last_error's)."""
+    L = _lib.lib()
+    one, big = C.c_void_p(16), C.c_size_t(1 << 40)        # never dereferenced: the argument checks come first
+    head = lambda B, R, vol=one, ws=one, ws_bytes=big: lambda: L.gnr_grasp_head_fwd(B, R, vol, one, one, one, one, ws, ws_bytes, None)
+    conv = lambda x=one, K=3, mode=0, ws_bytes=big: lambda: L.gnr_conv3d_same(x, one, one, one, 1, 16, 16, 4, 4, 4, K, mode, one, ws_bytes, None)
+    sel_p = _lib.GnrSelectParams(gauss_radius=4, dilate_iterations=2, max_filter_size=4)
+    sel = lambda tsdf=one, R=8, p=sel_p, ws_bytes=big: lambda: L.gnr_grasp_select_fwd(tsdf, one, one, one, 1, R, C.byref(p), one, one, one, one, one, one,
+                                                                                  8, one, ws_bytes, None)
+    norm = lambda x=one, planes=4, act=0: lambda: L.gnr_instnorm_act(x, None, one, one, one, one, one, planes, 2, 16, 1e-5, act, None)
+    ok = dict(frames=P, n=1, sh=4, sw=5, ch=3, rp=15, fp=60, tab=P, out=P, dh=3, dw=4, stream=None)
+    ingest = lambda **kw: lambda: L.gnr_ingest_u8(*dict(ok, **kw).values())
+    ptrs = (C.c_void_p * 2)(P, P)
+    need = L.gnr_frame_metrics_workspace_bytes(2, 33, 64, 2, 0, 0, 1)
+    base = dict(gt=P, preds=ptrs, n_pred=2, depth_pr=P, depth_gt=P, B=2, h=33, w=64, hm=0, wm=0, ssim=1, out=P, ws=P, ws_bytes=need, stream=None)
+    fm = lambda **kw: lambda: L.gnr_frame_metrics(*dict(base, **kw).values())
+    return [
+        ('gnr_head_last_error', head(1, 7), SHAPE, 'gnr_grasp_head_fwd: bad B/R'),
+        ('gnr_head_last_error', head(0, 40), SHAPE, 'gnr_grasp_head_fwd: bad B/R'),
+        ('gnr_head_last_error', head(1, 40, vol=None), ARG, 'gnr_grasp_head_fwd: null pointer'),
+        ('gnr_head_last_error', head(1, 40, ws=None), ARG, 'gnr_grasp_head_fwd: null pointer'),
+        ('gnr_head_last_error', head(3, 41, ws_bytes=C.c_size_t(L.gnr_grasp_head_workspace_bytes(3, 41) - 1)), WORKSPACE, 'workspace too small'),
+        ('gnr_head_last_error', conv(x=None), ARG, 'gnr_conv3d_same: null pointer'),
+        ('gnr_head_last_error', conv(K=4), SHAPE, 'gnr_conv3d_same: bad shape / mode (K must be 3 or 5)'),
+        ('gnr_head_last_error', conv(mode=2), SHAPE, 'gnr_conv3d_same: bad shape / mode (K must be 3 or 5)'),
+        ('gnr_head_last_error', conv(ws_bytes=C.c_size_t(L.gnr_conv3d_same_workspace_bytes(16, 16, 3) - 1)), WORKSPACE, 'gnr_conv3d_same: workspace too small'),
+        ('gnr_post_last_error', sel(tsdf=None), ARG, 'gnr_grasp_select_fwd: null pointer'),
+        ('gnr_post_last_error', sel(R=1), SHAPE, 'gnr_grasp_select_fwd: bad B / R / max_n'),
+        ('gnr_post_last_error', sel(p=_lib.GnrSelectParams(gauss_radius=17, max_filter_size=4)), ARG, 'gnr_grasp_select_fwd: bad filter parameters'),
+        ('gnr_post_last_error', sel(ws_bytes=C.c_size_t(L.gnr_grasp_select_workspace_bytes(1, 8) - 1)), WORKSPACE, 'workspace too small'),
+        ('gnr_img_last_error', norm(x=None), ARG, 'gnr_instnorm_act: null pointer'),
+        ('gnr_img_last_error', norm(planes=5), SHAPE, 'gnr_instnorm_act: planes must be a multiple of C > 0, HW > 0, act in {0,1,2}'),
+        ('gnr_img_last_error', norm(act=3), SHAPE, 'gnr_instnorm_act: planes must be a multiple of C > 0, HW > 0, act in {0,1,2}'),
+        ('gnr_img_last_error', lambda: L.gnr_reflect_pad2d(one, one, 2, 4, 4, 4, None), SHAPE, 'gnr_reflect_pad2d: null pointer or pad outside [0, min(H, W))'),
+        ('gnr_img_last_error', lambda: L.gnr_reflect_pad2d_bwd(one, None, 2, 4, 4, 1, None), ARG, 'gnr_reflect_pad2d_bwd: null pointer or pad outside [0, min(H, W))'),
+        ('gnr_img_last_error', lambda: L.gnr_upsample2x_bilinear(one, one, 2, 0, 4, None), SHAPE, 'gnr_upsample2x_bilinear: H, W > 0'),
+        ('gnr_ingest_last_error', ingest(frames=None), ARG, 'gnr_ingest_u8: null pointer'),
+        ('gnr_ingest_last_error', ingest(ch=5, rp=64), ARG, 'gnr_ingest_u8: channels must be 3 or 4'),
+        ('gnr_ingest_last_error', ingest(sh=16385, rp=1 << 20), SHAPE, 'gnr_ingest_u8: n >= 1 and every dimension in 1..16384'),
+        ('gnr_ingest_last_error', ingest(rp=14), ARG, 'gnr_ingest_u8: row_pitch < src_w * channels'),
+        ('gnr_ingest_last_error', ingest(n=2, fp=59), ARG, 'gnr_ingest_u8: frame_pitch shorter than one frame'),
+        ('gnr_ingest_last_error', lambda: L.gnr_ingest_tables_host(4, 5, 3, 4, None), ARG, 'gnr_ingest_tables_host: null pointer'),
+        ('gnr_ingest_last_error', lambda: L.gnr_ingest_tables_host(4, 16385, 3, 4, P), SHAPE, 'gnr_ingest_tables_host: every dimension must be in 1..16384'),
+        ('gnr_last_error', fm(gt=None), ARG, 'gnr_frame_metrics: null pointer'),
+        ('gnr_last_error', fm(preds=(C.c_void_p * 2)(P, None)), ARG, 'gnr_frame_metrics: null prediction pointer'),
+        ('gnr_last_error', fm(n_pred=5), ARG, 'gnr_frame_metrics: n_pred must be in 1..4'),
+        ('gnr_last_error', fm(hm=17), SHAPE, 'gnr_frame_metrics: the crop margins leave no pixel'),
+        ('gnr_last_error', fm(h=10), SHAPE, 'gnr_frame_metrics: SSIM needs a cropped frame of at least 11 x 11 pixels (the 11 x 11 window)'),
+        ('gnr_last_error', fm(ws_bytes=need - 1), WORKSPACE, 'gnr_frame_metrics: workspace smaller than gnr_frame_metrics_workspace_bytes()'),
+    ]
+
+
+def test_every_unit_refuses_with_its_text_in_the_one_error_string():
+    """Head, gnr_conv3d_same, post, img, ingest and metrics: every refusal keeps its status and its text byte for byte, and the text is
+    the library's ONE error string -- gnr_last_error() and the unit's own reader (an alias now) return the same bytes.  Every call is one
+    that validation refuses (fake pointers); runs without a GPU."""
+    L = _lib.lib()
+    rows = _unit_refusals()
+    assert all(sum(r[0] == unit for r in rows) >= 2 for unit in {r[0] for r in rows}) and len({r[0] for r in rows}) == 5
+    for reader, call, code, text in rows:
+        rc = call()
+        unit_text, one_text = getattr(L, reader)(), L.gnr_last_error()
+        assert (rc, unit_text.decode()) == (code, text), (reader, text, rc, unit_text)
+        assert one_text == unit_text, (reader, one_text, unit_text)
+    for reader in ('gnr_head_last_error', 'gnr_post_last_error', 'gnr_img_last_error', 'gnr_ingest_last_error'):      # all five, after one failure
+        assert getattr(L, reader)() == L.gnr_last_error() == rows[-1][3].encode()
+
+
+def test_the_error_text_belongs_to_the_calling_thread():
+    """Thread A is refused by the head while thread B is refused by the ingest, 100 times each: each thread reads back only its own
+    text (the string is thread_local), through gnr_last_error and through either alias."""
+    L = _lib.lib()
+    one, big = C.c_void_p(16), C.c_size_t(1 << 40)
+    calls = {'gnr_grasp_head_fwd: bad B/R': lambda: L.gnr_grasp_head_fwd(1, 7, one, one, one, one, one, one, big, None),
+             'gnr_ingest_u8: row_pitch < src_w * channels': lambda: L.gnr_ingest_u8(P, 1, 4, 5, 3, 14, 60, P, P, 3, 4, None)}
+    start, seen = threading.Barrier(len(calls)), {}
+
+    def run(text, call):
+        start.wait()
+        got = set()
+        for _ in range(100):
+            rc = call()
+            got.add((rc, L.gnr_last_error(), L.gnr_head_last_error(), L.gnr_ingest_last_error()))
+        seen[text] = got
+    threads = [threading.Thread(target=run, args=item) for item in calls.items()]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert seen == {'gnr_grasp_head_fwd: bad B/R': {(SHAPE,) + (b'gnr_grasp_head_fwd: bad B/R',) * 3},
+                    'gnr_ingest_u8: row_pitch < src_w * channels': {(ARG,) + (b'gnr_ingest_u8: row_pitch < src_w * channels',) * 3}}
+
+
 # What the library built from the commit before the host layer's launches went through one helper reports for the run below.
 LABELS = [
     'k_view_setup@gnr_prepare', 'k_repack_feats@gnr_prepare',
@@ -262,3 +360,62 @@ def test_timing_labels_of_a_tiny_forward_and_backward(weights_np):
     print('timing labels:', sorted(got))
     assert len(set(LABELS)) == len(LABELS)
     assert set(got) == set(LABELS), (sorted(set(got) - set(LABELS)), sorted(set(LABELS) - set(got)))
+
+
+# What the library built from the commit before every source file launched through csrc/gnr_host.h reports for the run below: the grasp
+# head's forward is ONE bracket around all of its kernels, the head's training convolutions and the frame metrics label each launch,
+# and the post-processing, the image ops, the ingest and the device packer report nothing.
+UNIT_LABELS = [
+    'grasp_head_fwd(all kernels)@gnr_grasp_head_fwd',
+    'k_pack_conv3d_frag@gnr_conv3d_same', 'k_conv3d_s1.fwd@gnr_conv3d_same',
+    'k_conv3d_wgrad_s1@gnr_conv3d_same_bwd_weight', 'k_conv3d_wgrad_reduce@gnr_conv3d_same_bwd_weight',
+    'k_conv3d_bwd_weight@gnr_conv3d_bwd_weight',
+    'k_frame_pixels@gnr_frame_metrics', 'k_frame_ssim@gnr_frame_metrics', 'k_frame_finish@gnr_frame_metrics',
+]
+
+
+@pytest.mark.gpu
+def test_timing_labels_of_the_units_outside_the_scene_entry_points():
+    """One smallest accepted call of every unit that is not gnr_capi.inc -- head forward (B = 1, R = 8), gnr_conv3d_same forward and both
+    weight gradients (16 -> 16, k3, 4^3), select (R = 8), the three image ops on an 8 x 8 plane, ingest (8 x 8 -> 4 x 4), the device
+    packers, the frame metrics (16 x 16, one prediction) -- under gnr_timing_begin(): the SET of labels equals UNIT_LABELS."""
+    import torch
+    from graspnerf_amd import backbone, metrics
+    from graspnerf_amd.grasp_post import GraspSelector
+    from graspnerf_amd.ingest import DeviceIngest
+    L = _lib.lib()
+    dev = torch.device('cuda:0')
+    g = torch.Generator().manual_seed(0)
+    t = lambda *shape: torch.rand(*shape, generator=g).to(dev)
+    z = lambda n: torch.zeros(n, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    B, R, n40 = 1, 8, 40 ** 3
+    vol, packed, qual, rot, width = t(B, 1, R, R, R), z(L.gnr_head_packed_floats()), z(B * n40), z(B * 4 * n40), z(B * n40)
+    head_ws = torch.empty(L.gnr_grasp_head_workspace_bytes(B, R), dtype=torch.uint8, device=dev)
+    x, w, dy, dw = t(1, 16, 4, 4, 4), t(16, 16, 3, 3, 3).requires_grad_(), t(1, 16, 4, 4, 4), z(16 * 16 * 27)
+    plane, nw, nb = t(1, 1, 8, 8), torch.ones(1, device=dev), z(1)
+    canon, packed_fwd, packed_bwd = z(L.gnr_canonical_weights_floats()), z(L.gnr_packed_weights_floats()), z(L.gnr_packed_bwd_floats())
+    frames = (t(1, 8, 8, 3) * 255).to(torch.uint8)
+    ingest, select = DeviceIngest(dev), GraspSelector(dev, max_grasps=8)
+    ingest.tables((8, 8), (4, 4))                                      # (the upload of the tables is not a launch of the library)
+    gt, pred, depth = t(1, 256, 3), t(1, 256, 3), t(1, 256)
+    _lib.timing_begin()
+    try:
+        _lib.check(L.gnr_grasp_head_fwd(B, R, vol.data_ptr(), packed.data_ptr(), qual.data_ptr(), rot.data_ptr(), width.data_ptr(),
+                                        head_ws.data_ptr(), head_ws.numel(), stream), 'gnr_grasp_head_fwd')
+        backbone._Conv3dSame.apply(x, w, None).backward(dy)             # forward + gnr_conv3d_same_bwd_weight (x takes no gradient)
+        _lib.check(L.gnr_conv3d_bwd_weight(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), 1, 16, 16, 4, 4, 4, 3, stream), 'gnr_conv3d_bwd_weight')
+        select(t(B, 1, R, R, R), t(B, 1, R, R, R), t(B, 4, R, R, R), t(B, 1, R, R, R))
+        backbone._InstNormActFn.apply(plane, nw, nb, 1e-5, 1, None)
+        backbone._ReflectPadFn.apply(plane, 1)
+        backbone._Upsample2xFn.apply(plane)
+        ingest(frames, (4, 4))
+        _lib.check(L.gnr_pack_weights_device(canon.data_ptr(), packed_fwd.data_ptr(), stream), 'gnr_pack_weights_device')
+        _lib.check(L.gnr_pack_weights_bwd_device(canon.data_ptr(), packed_bwd.data_ptr(), stream), 'gnr_pack_weights_bwd_device')
+        metrics.frame_metrics_device(gt, [pred], depth, depth.clone(), 16, 16, ssim=True)
+        torch.cuda.synchronize()
+    finally:
+        got = _lib.timing_end()
+    print('timing labels:', sorted(got))
+    assert len(set(UNIT_LABELS)) == len(UNIT_LABELS)
+    assert set(got) == set(UNIT_LABELS), (sorted(set(got) - set(UNIT_LABELS)), sorted(set(UNIT_LABELS) - set(got)))
