@@ -9,7 +9,8 @@
 //                    branch; SP: fp16-pair operands, false = the fp32-MFMA twin): per-(point,view) projection + gather + mixture decoder +
 //                    prob-embed + IBRNet aggregation + geometry MLP, all layers as chained MFMAs with
 //                    activations resident in registers: fp32 values, multiplied on the f16 matrix cores
-//                    as fp16 pairs (v_mfma_f32_16x16x32_f16; short remainders on v_mfma_f32_16x16x4_f32)
+//                    as fp16 pairs (v_mfma_f32_16x16x32_f16; short remainders K-stacked on the same instruction,
+//                    the rest on v_mfma_f32_16x16x4_f32)
 //                    (dist_decoder.py:99-142, aggregate_net.py:35-70, ibrnet.py:456-489,506-512)
 //   k_ray<RENDER>    per ray / voxel column: 40-token self-attention + SDF head, and for rays the
 //                    in-forward VJP, NeuS alpha, compositing, ray mask and inverse-CDF resampling
@@ -366,6 +367,62 @@ DEV void mm16u(const float* __restrict__ w, int lane, const P8U* __restrict__ x8
         for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma32h(wh[nb], x8[kb].m, acc[nb]);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma32h(wm[nb], x8[kb].s, acc[nb]);
+    }
+#if GNR_MFMA_PRIO == 2
+    __builtin_amdgcn_s_setprio(0);
+#endif
+    if constexpr (WATCH) range_watch(*rw, acc[0]);
+}
+// ---- K-stacked pair layers (ST section, gnr_layout.h): the per-view layers with SLOTS = 4 or 2 real inputs per lane.  On the
+// fp32-input MFMA such a layer costs one instruction of 32 cycles per k-step and output block for an eighth of an f16 MFMA's
+// products; zero-padded into a K32 block it multiplies zeros in most k-slots (the round-6 GNR_RDF2_PAIRS record).  A lane group's
+// eight k-slots are independent products, and A and B only have to agree slot by slot: the free slots carry the residual terms
+// of the unscaled pair form (mm16u:  W x = wh h + wh m + wm (h 2^-11)),
+//   SLOTS = 4:  A {wh0..3, wm0..3} (as stored) x B {h0..3, s0..3}, then the same A x B {m0..3, 0, 0, 0, 0}: two MFMAs per block,
+//   SLOTS = 2:  A {wh, wm, wh, wm} x B {h0, h1, s0, s1, m0, m1, 0, 0}: one MFMA,
+// all into the layer's own accumulator, no fold.  (The zero slots of B meet finite weight halves: a blob with a weight that has
+// no pair never reaches a pair launch.)  A split costs 5 VALU per two inputs, as split2u.
+struct P8S { h8 a, b; };
+template <int SLOTS, int O, int N>
+DEV P8S split_stacked(const float (&v)[N]) {
+    static_assert((SLOTS == 4 || SLOTS == 2) && O + SLOTS <= N, "split_stacked reads SLOTS slots");
+    const _Float16 z = (_Float16)0.f;
+    P8S p;
+    if constexpr (SLOTS == 4) {
+        h2 h[2], m[2], s[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) split2u(v[O + 2 * q], v[O + 2 * q + 1], h[q], m[q], s[q]);
+        p.a = (h8){h[0].x, h[0].y, h[1].x, h[1].y, s[0].x, s[0].y, s[1].x, s[1].y};
+        p.b = (h8){m[0].x, m[0].y, m[1].x, m[1].y, z, z, z, z};
+    } else {
+        h2 h, m, s;
+        split2u(v[O], v[O + 1], h, m, s);
+        p.a = (h8){h.x, h.y, s.x, s.y, m.x, m.y, z, z};
+        p.b = p.a;
+    }
+    return p;
+}
+// acc[nb] += W x of a stacked layer; w: its fragment in the staged image.  The two MFMAs of a block depend on each other through
+// the accumulator: the first of every block, then the second of every block.
+template <int SLOTS, int NB, bool LF, bool WATCH = false>
+DEV void mm16s(const float* __restrict__ w, int lane, const P8S& x, f4 (&acc)[NB], float* rw = nullptr) {
+    static_assert(SLOTS == 4 || (SLOTS == 2 && NB == 1), "stacked layers: 4 slots, or 2 slots and one output block");
+    if constexpr (LF) asm volatile("" ::: "memory");
+#if GNR_MFMA_PRIO == 2
+    __builtin_amdgcn_s_setprio(1);
+#endif
+    if constexpr (SLOTS == 4) {
+        const h8* w8 = reinterpret_cast<const h8*>(w) + lane;
+        h8 a[NB];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) a[nb] = w8[nb * 64];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma32h(a[nb], x.a, acc[nb]);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma32h(a[nb], x.b, acc[nb]);
+    } else {
+        const f2 d = reinterpret_cast<const f2*>(w)[lane];
+        acc[0] = mfma32h(__builtin_bit_cast(h8, (f4){d.x, d.y, d.x, d.y}), x.a, acc[0]);
     }
 #if GNR_MFMA_PRIO == 2
     __builtin_amdgcn_s_setprio(0);
@@ -964,16 +1021,22 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
     bool range_tripped = false;                           // wave-uniform
     constexpr bool UA = SP && GNR_UNSCALED_ACT != 0;       // inner layers on unscaled activation pairs (split8u / mm16u)
     constexpr bool EP = SP && !SAVE;                       // e1 travels between the view loops as its fp16 pair (the training saves keep fp32)
+    // (in the pair kernels the slots LO(pk::RDF2), LO(pk::RGB2) and pk::ST_AT_RGB1X hold the STACKED fragments while the matching GNR_STACK_* switch is on, the fp32 fragments otherwise: pk::stage_src4)
 #define LO(o) (SP ? pk::c16_off(o) : (o))                  /* offset of a CHAIN-section name inside the staged image */                    // fp16-pair layers on the f16 matrix cores (C16 image) / fp32 MFMA (CHAIN image)
-    // ---- stage the C16 (or CHAIN) section of the packed weights into LDS (once per workgroup)
+    // the pair kernels run the short per-view layers K-stacked (mm16s; each conversion has its switch, gnr_layout.h) -- the training
+    // forward (SAVE) too: its outputs are the inference launch's bit for bit (tests/test_torch_ops.py); the backward twins' recompute of
+    // these three layers stays on the fp32-input MFMA (csrc/gnr_bwd.inc: pre-activations that differ from the forward's by rounding)
+    constexpr bool SK_RDF2 = SP && GNR_STACK_RDF2 != 0, SK_RGB2 = SP && GNR_STACK_RGB2 != 0, SK_RGB1X = SP && GNR_STACK_RGB1X != 0;
+    // ---- stage the C16 (or CHAIN) section of the packed weights into LDS (once per workgroup); the pair kernels take the stacked
+    // fragments in place of the fp32 fragments they no longer read (pk::stage_src4)
     {
-        const f4* src = reinterpret_cast<const f4*>(a.wpk + (SP ? pk::C16 : 0));
+        const f4* src = reinterpret_cast<const f4*>(a.wpk);      // (SP: stage_src4 indexes the blob)
         f4* dst = reinterpret_cast<f4*>(lds);
         constexpr int N4 = (SP ? pk::C16_END : pk::CHAIN_END) / 4, SU = 6;      // six loads in flight per lane (one per trip: 10 us per launch, tools/wave_clock.py)
         for (int i0 = threadIdx.x; i0 < N4; i0 += blockDim.x * SU) {
             f4 tmp[SU];
 #pragma unroll
-            for (int u = 0; u < SU; ++u) { const int i = i0 + u * (int)blockDim.x; tmp[u] = src[i < N4 ? i : N4 - 1]; }
+            for (int u = 0; u < SU; ++u) { const int i = min(i0 + u * (int)blockDim.x, N4 - 1); tmp[u] = src[SP ? pk::stage_src4(i) : i]; }
 #pragma unroll
             for (int u = 0; u < SU; ++u) { const int i = i0 + u * (int)blockDim.x; if (i < N4) dst[i] = tmp[u]; }
         }
@@ -1307,13 +1370,14 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                 mm<1, 1, 0, LF>(lds + LO(pk::RDF1), lane, ddg, acc1);
                 elu_to<1, true>(acc1, d1);
                 load_bias<3, LF>(lds + LO(pk::B_RDF2), g, acc3);
-                // 4 k-steps: stays on the fp32 MFMA (zero-padded into a K32 pair block: 3.68 vs 3.71 ms alone, but 3.80 together
-                // with the padded tails of HOIST / GEO1, which gain more: 3.63)
+                // 4 k-steps: K-stacked in the pair kernels (6 f16 MFMAs for 12 fp32 ones), on the fp32 MFMA in the twin (zero-padded
+                // into a K32 pair block: 3.68 vs 3.71 ms alone, but 3.80 together with the padded tails of HOIST / GEO1, which gain more: 3.63)
 #if GNR_RDF2_PAIRS
                 if constexpr (SP && !USEVIS) { const P8 dp = split8z<0, 4>(d1); mm16<1, 3, LF>(lds + pk::c16_off(pk::DECV1), lane, &dp, acc3); }
                 else
 #endif
-                mm<4, 3, 0, LF>(lds + LO(pk::RDF2), lane, d1, acc3);
+                if constexpr (SK_RDF2) { const P8S dp = split_stacked<4, 0>(d1); mm16s<4, 3, LF, true>(lds + LO(pk::RDF2), lane, dp, acc3, &msum); }
+                else mm<4, 3, 0, LF>(lds + LO(pk::RDF2), lane, d1, acc3);
                 elu_to<3, true>(acc3, df);
 #pragma unroll
                 for (int j = 0; j < 9; ++j) Sv[j] = fmaf(df[j], kLn2, XI[j]);
@@ -1498,12 +1562,16 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                 float c1[4], c2[4];
                 load_bias<1, LF>(lds + LO(pk::B_RGB1), g, acc1);
                 const float ex[2] = {g == 0 ? v2 : (g == 1 ? vg.dd[0] : (g == 2 ? vg.dd[1] : vg.dd[2])), g == 0 ? vg.dd[3] : 0.f};
-                mm<2, 1, 8, LF>(lds + LO(pk::RGB1), lane, ex, acc1);
+                // (v2, dir diff: bounded by construction; the accumulator is watched by the K32 block behind)
+                if constexpr (SK_RGB1X) { const P8S xp = split_stacked<2, 0>(ex); mm16s<2, 1, LF>(lds + pk::ST_AT_RGB1X, lane, xp, acc1); }
+                else mm<2, 1, 8, LF>(lds + LO(pk::RGB1), lane, ex, acc1);
                 if constexpr (SP) { const P8 hp = split8<0>(Hh); mm16<1, 1, LF, true>(lds + LO(pk::RGB1), lane, &hp, acc1, &msum); }
                 else mm<8, 1, 0, LF>(lds + LO(pk::RGB1), lane, Hh, acc1);
                 elu_to<1, !SP>(acc1, c1);
                 load_bias<1, LF>(lds + LO(pk::B_RGB2), g, acc1);
-                mm<4, 1, 0, LF>(lds + LO(pk::RGB2), lane, c1, acc1);               // 4 k-steps, one output block: stays on the fp32 MFMA
+                // 4 k-steps, one output block: K-stacked in the pair kernels, on the fp32 MFMA in the twin
+                if constexpr (SK_RGB2) { const P8S cp = split_stacked<4, 0>(c1); mm16s<4, 1, LF, true>(lds + LO(pk::RGB2), lane, cp, acc1, &msum); }
+                else mm<4, 1, 0, LF>(lds + LO(pk::RGB2), lane, c1, acc1);
                 elu_to<1, true>(acc1, c2);
                 clog = gsum(dot4(lds + LO(pk::T_RGB3), g, c2)) + lds[LO(pk::T_SCAL) + 3];
                 if (m == 0.f) clog = -1e9f;

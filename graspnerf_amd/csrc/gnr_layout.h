@@ -144,7 +144,8 @@ constexpr int R_OUTB = R_OUTVJP + 16;       // folded bias: out_fc.1 . out_fc.0.
 //     element i <-> the block's i-th k-step (lane group g holds input slot phi(k_i, g), as in the fp32 form).
 // A full block takes exactly the room of its 8 fp32 k-steps (4 bytes per weight), so most slots keep their size; the
 // two per-point layers whose 4- / 7-k-step tails are zero-padded into a block of their own grow (c16_off shifts what
-// follows).  ray_dir_fc.2 (4 k-steps, per view) stays fp32: padded as well it costs more than it saves (measured).
+// follows).  ray_dir_fc.2 (4 k-steps, per view) stays fp32 in this image: padded as well it costs more than it saves (measured);
+// k_chain's pair kernels run it, rgb_fc.2 and rgb_fc.0's two left-over k-steps K-STACKED from the ST section below.
 // Which k-steps form the blocks of which layer: gnr_pack.cpp `c16_plan` and the call sites in k_chain.  The fp32 CHAIN
 // section stays in the blob: k_depth_mean and the backward twins read their forward fragments from it.
 // (k32_floats: defined above, in front of the RAY section)
@@ -161,10 +162,52 @@ constexpr int RM_DC = R_OUTB + 4;                   // dT = [Wq^T Wk^T Wv^T I] [
 constexpr int RM_GEOA = RM_DC + 2 * k32_floats(1);  // du = geometry_fc.2^T dc              K = 16: input 4 g + e in elements e < 4 of lane group g (RM_DC's D layout), NB = 4
 constexpr int RM_GEOB = RM_GEOA + k32_floats(4);    // de = geometry_fc.0[:, 65:86]^T da    K = 64 (two blocks), NB = 2 (rows 21.. zero)
 constexpr int RM_END = RM_GEOB + 2 * k32_floats(2);
-constexpr int C16 = RM_END;
+// ST section: K-STACKED fp16-pair fragments of the per-view layers with 1..4 k-steps that the pair instantiations of k_chain
+// (SP: inference and training forward) run on the f16 matrix cores.  A lane group's eight k-slots of a K32 block are independent products, so the slots a
+// short layer leaves empty carry the pair's residual terms instead of zeros.  The layer's inputs are activations, split UNSCALED
+// like mm16u's (h = fp16(x), m = fp16(x - h), s = h 2^-11); its weights are stored as (wh, wm = fp16((w - wh) 2^11)):
+//   SLOTS = 4 real inputs per lane (the layer's k-steps 0..3): per output block nb and lane 8 halfs {wh0..wh3, wm0..wm3} at
+//     16-byte index nb 64 + lane -- the A operand of BOTH MFMAs of the block as it is loaded:
+//       A {wh, wm} x B {h0..h3, s0..s3} = wh h + wm s ,   A {wh, wm} x B {m0..m3, 0, 0, 0, 0} = wh m   (+ wm 0)
+//   SLOTS = 2 (k-steps 8, 9 of rgb_fc.0): per lane 4 halfs {wh0, wh1, wm0, wm1} at 8-byte index lane; the A operand is the two
+//     dwords twice, A {wh, wm, wh, wm} x B {h0, h1, s0, s1, m0, m1, 0, 0}: all three products in ONE MFMA.
+// Scales (log2e folding), input slots and output rows are those of the fp32 fragments they are made from (c16_pairs), so the
+// next layer's B layout does not move.  A weight without an fp16 pair is stored as +-inf and marks the blob (T_VIS + 2).
+// k_chain stages a stacked fragment over the fp32 fragment it replaces (stage_src below): the staged image keeps its size
+// and every offset; the C16 image in the blob still holds the fp32 fragments (its layout is pinned: tests/test_pack_layout.py).
+constexpr int st_floats(int SLOTS, int NB) { return NB * 64 * SLOTS; }       // (2 SLOTS halfs per lane and block)
+constexpr int ST_RDF2 = RM_END;                               // ray_dir_fc.2          SLOTS 4, NB 3   (3 072 B)
+constexpr int ST_RGB2 = ST_RDF2 + st_floats(4, 3);            // rgb_fc.2              SLOTS 4, NB 1   (1 024 B)
+constexpr int ST_RGB1X = ST_RGB2 + st_floats(4, 1);           // rgb_fc.0, k-steps 8, 9  SLOTS 2, NB 1   (512 B)
+constexpr int ST_END = ST_RGB1X + st_floats(2, 1);
+constexpr int C16 = ST_END;
 constexpr int C16_END = c16_off(CHAIN_END);
 static_assert(C16_END % 4 == 0 && C16_END * 4 <= 160 * 1024, "the C16 image must fit the 160 KiB LDS");
 constexpr int TOTAL = C16 + C16_END;
+// The image the pair instantiations of k_chain stage into LDS: the C16 image with the stacked fragments over the fp32
+// fragments they replace (ray_dir_fc.2: the first three quarters of its slot; rgb_fc.2: the whole slot; rgb_fc.0: the first half of
+// its two left-over k-steps behind the K32 block).  Each conversion has a switch of its own (measured one by one: profiles/chain_stacked_ab.json).
+#ifndef GNR_STACK_RDF2
+#define GNR_STACK_RDF2 1
+#endif
+#ifndef GNR_STACK_RGB2
+#define GNR_STACK_RGB2 1
+#endif
+#ifndef GNR_STACK_RGB1X
+#define GNR_STACK_RGB1X 1
+#endif
+constexpr int ST_AT_RGB1X = c16_off(RGB1) + k32_floats(1);     // where the staged image holds rgb_fc.0's stacked k-steps 8, 9
+// 16-byte word i4 of the staged image <- this 16-byte word of the blob
+constexpr int stage_src4(int i4) {
+    const int o = 4 * i4;
+    if (GNR_STACK_RDF2 != 0 && o >= c16_off(RDF2) && o < c16_off(RDF2) + st_floats(4, 3)) return (ST_RDF2 + o - c16_off(RDF2)) / 4;
+    if (GNR_STACK_RGB2 != 0 && o >= c16_off(RGB2) && o < c16_off(RGB2) + st_floats(4, 1)) return (ST_RGB2 + o - c16_off(RGB2)) / 4;
+    if (GNR_STACK_RGB1X != 0 && o >= ST_AT_RGB1X && o < ST_AT_RGB1X + st_floats(2, 1)) return (ST_RGB1X + o - ST_AT_RGB1X) / 4;
+    return (C16 + o) / 4;
+}
+static_assert(ST_RDF2 % 4 == 0 && C16 % 4 == 0 && c16_off(RDF2) % 4 == 0 && c16_off(RGB2) % 4 == 0 && ST_AT_RGB1X % 4 == 0, "staged as 16-byte words");
+static_assert(st_floats(4, 3) <= frag_floats(4, 3) && st_floats(4, 1) <= frag_floats(4, 1) && st_floats(2, 1) <= frag_floats(2, 1),
+              "a stacked fragment fits the fp32 fragment it is staged over");
 }  // namespace pk
 
 // per-point descriptor (k_points_* -> k_chain): 8 floats

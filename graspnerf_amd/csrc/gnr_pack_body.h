@@ -187,7 +187,7 @@ GNR_HD inline C16Plan c16_plan(int n) {
         case 17: return C16Plan{DECV1, 8, 2, 1, {0}, {8}, 0, {0, 0}};
         default: return C16Plan{DECV2, 8, 2, 1, {0}, {8}, 0, {0, 0}};
     }
-    // RDF1 (one k-step), RDF2 and RGB2 (4 k-steps) stay fp32
+    // RDF1 (one k-step), RDF2 and RGB2 (4 k-steps) stay fp32 in the C16 image (RDF2, RGB2 and RGB1's left-over k-steps: also K-stacked, ST section)
 }
 constexpr int C16_PLANS_ALL = 19;
 
@@ -231,6 +231,27 @@ GNR_HD void to_pairs(const Ex& ex, float* dst, const float* src, const C16Plan& 
     }
 }
 
+// K-stacked fragment (ST section, gnr_layout.h) of the k-steps j0 .. j0 + SLOTS - 1 of an fp32 fragment (src, NB output blocks):
+// per output block and lane SLOTS halfs wh, then SLOTS halfs wm = fp16((w - wh) 2^11).  A weight without an fp16 pair is stored
+// as its fp16 conversion (+-inf, NaN) and marks the blob like to_pairs.
+template <class Ex>
+GNR_HD void to_stacked(const Ex& ex, float* dst, const float* src, int SLOTS, int NB, int j0, float* bad0, float* bad1) {
+    uint16_t* o16 = reinterpret_cast<uint16_t*>(dst);
+    ex.run(NB * 64 * SLOTS, [&](int t) {
+#pragma clang fp contract(off)
+        const int i = t % SLOTS, lane = (t / SLOTS) & 63, nb = t / (SLOTS * 64);
+        const float w = src[frag_index(NB, j0 + i, nb, lane)];
+        const uint16_t h = f32_to_f16(w);
+        uint16_t m = 0;
+        bool fin;
+        const float hf = f16_to_f32(h, fin);
+        if (fin) m = f32_to_f16((w - hf) * 2048.f);
+        else { *bad0 = 1.f; *bad1 = 1.f; }
+        o16[((nb * 64 + lane) * 2 + 0) * SLOTS + i] = h;
+        o16[((nb * 64 + lane) * 2 + 1) * SLOTS + i] = m;
+    });
+}
+
 // C16 image, step 1: the CHAIN section's slots copied to their places (two slots grown, gnr_layout.h c16_off)
 template <class Ex>
 GNR_HD void c16_copy_runs(const Ex& ex, float* p) {
@@ -249,6 +270,12 @@ GNR_HD void c16_pairs(const Ex& ex, float* p) {
         const C16Plan pl = c16_plan(n);
         to_pairs(ex, p + pk::C16 + pk::c16_off(pl.off), p + pl.off, pl, p + pk::T_VIS + 2, p + pk::C16 + pk::c16_off(pk::T_VIS) + 2);
     }
+    // ST section: the short per-view layers of k_chain's pair instantiations (inference and training forward), K-stacked
+    float* const bad0 = p + pk::T_VIS + 2;
+    float* const bad1 = p + pk::C16 + pk::c16_off(pk::T_VIS) + 2;
+    to_stacked(ex, p + pk::ST_RDF2, p + pk::RDF2, 4, 3, 0, bad0, bad1);
+    to_stacked(ex, p + pk::ST_RGB2, p + pk::RGB2, 4, 1, 0, bad0, bad1);
+    to_stacked(ex, p + pk::ST_RGB1X, p + pk::RGB1, 2, 1, 8, bad0, bad1);
 #if GNR_RDF2_PAIRS
     // measurement build (tools/ab_chain.py, profiles/r06_*_chain_ab.json): ray_dir_fc.2's 4 k-steps as ONE zero-padded K32 pair block.  The
     // C16 image has no room left (156.3 of 160 KB): the block overlays the vis_decoder's slots, so this build serves use_vis = 0 only.
