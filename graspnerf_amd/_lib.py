@@ -51,6 +51,19 @@ class GnrSelectParams(C.Structure):
                 ('max_filter_size', C.c_int)]
 
 
+GNR_SELECT_ORDER_INDEX, GNR_SELECT_ORDER_SCORE, GNR_SELECT_SCORE_MAX_R = 0, 1, 64
+GNR_SURFACE_COLOR_FIXED, GNR_SURFACE_COLOR_VALUE = 0, 1
+
+
+class GnrSelectParamsV2(C.Structure):
+    _fields_ = [('select', GnrSelectParams), ('tsdf_thres_outside', C.c_float), ('order', C.c_int), ('top_k', C.c_int)]
+
+
+class GnrSurfaceParams(C.Structure):
+    _fields_ = [('lo', C.c_float), ('hi', C.c_float), ('color_mode', C.c_int), ('color', C.c_float * 3),
+                ('bound_a', C.c_float), ('bound_b', C.c_float), ('scale', C.c_double)]
+
+
 class GnrError(RuntimeError):
     pass
 
@@ -205,6 +218,16 @@ def lib():
                                       [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.gnr_grasp_select_fwd.restype = C.c_int
     L.gnr_post_last_error.restype = C.c_char_p
+    L.gnr_grasp_select_v2_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.gnr_grasp_select_v2_workspace_bytes.restype = C.c_size_t
+    L.gnr_grasp_select_v2_fwd.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.POINTER(GnrSelectParamsV2)] + \
+                                         [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.gnr_grasp_select_v2_fwd.restype = C.c_int
+    L.gnr_surface_points_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    L.gnr_surface_points_workspace_bytes.restype = C.c_size_t
+    L.gnr_surface_points_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(GnrSurfaceParams)] + [C.c_void_p] * 4 + \
+                                        [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.gnr_surface_points_fwd.restype = C.c_int
     L.gnr_time_chain_kernel.argtypes = [C.POINTER(GnrScene), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                         c_float_p, C.c_void_p]
     L.gnr_time_chain_kernel.restype = C.c_int
@@ -259,7 +282,8 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_render_tail_fwd_train', 'gnr_ray_tail_grad_floats', 'gnr_ray_tail_dual_bwd', 'gnr_ray_tail_dual_bwd_workspace_bytes', 'gnr_composite_bwd', 'gnr_composite_bwd_workspace_bytes', 'gnr_geo_dual_fwd', 'gnr_geo_dual_fwd_workspace_bytes', 'gnr_geo_dual_bwd', 'gnr_geo_dual_bwd_workspace_bytes', 'gnr_host_randperm_prefix',
             'gnr_debug_fill_lds', 'gnr_img_last_error', 'gnr_instnorm_act', 'gnr_instnorm_act_bwd', 'gnr_reflect_pad2d', 'gnr_reflect_pad2d_bwd', 'gnr_upsample2x_bilinear',
             'gnr_ingest_tables_bytes', 'gnr_ingest_tables_host', 'gnr_ingest_u8', 'gnr_ingest_last_error',
-            'gnr_frame_metrics_workspace_bytes', 'gnr_frame_metrics']
+            'gnr_frame_metrics_workspace_bytes', 'gnr_frame_metrics',
+            'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd']
 
 
 def check(rc, what):

@@ -2,6 +2,8 @@
 // call scipy.ndimage on the host for every plan.  64 000 voxels per scene: byte/float streaming work, one thread per
 // voxel, no MFMA.  Bit-exact with scipy: the Gaussian accumulates in fp64 in scipy's order and rounds to fp32 after
 // every axis (ni_filters.c, symmetric branch); dilation and the max filter are exact by nature.
+// Also the real-robot route of src/nr/utils/grasp_utils.py:40-151 and draw_utils.py:355-377: process with its own outside threshold,
+// the survivors ranked by score (k_rank) and the surface point cloud (k_surf_*).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,13 +29,13 @@ __global__ void k_gauss_axis(const float* __restrict__ in, float* __restrict__ o
     out[t] = (float)acc;
 }
 
-// outside = tsdf > high ; may_change = !(low < tsdf < high)      (main.py:45-49)
+// outside = tsdf > outside ; may_change = !(low < tsdf < high)      (main.py:45-49: outside == high; grasp_utils.py:59-60: 0.1 / -0.1)
 __global__ void k_masks(const float* __restrict__ tsdf, unsigned char* __restrict__ x, unsigned char* __restrict__ m,
-                        float high, float low, size_t n) {
+                        float outside, float high, float low, size_t n) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     const float v = tsdf[t];
-    x[t] = v > high ? 1 : 0;
+    x[t] = v > outside ? 1 : 0;
     m[t] = (low < v && v < high) ? 0 : 1;
 }
 
@@ -86,10 +88,11 @@ __global__ void k_nms(const float* __restrict__ q, unsigned char* __restrict__ k
     keep[t] = (c == m) ? 1 : 0;
 }
 
-// ordered compaction (np.argwhere order = ascending linear index), one workgroup per volume   (main.py:70-77)
+// ordered compaction (np.argwhere order = ascending linear index), one workgroup per volume   (main.py:70-77); rows of max_n
+// entries, the first `limit` <= max_n survivors stored
 __global__ __launch_bounds__(1024) void k_compact(const unsigned char* __restrict__ keep, const float* __restrict__ q,
                                                   const float* __restrict__ rot, const float* __restrict__ width, int R, int max_n,
-                                                  int* __restrict__ count, int* __restrict__ index, float* __restrict__ score,
+                                                  int limit, int* __restrict__ count, int* __restrict__ index, float* __restrict__ score,
                                                   float* __restrict__ quat, float* __restrict__ width_out) {
     __shared__ int wave_tot[16];
     __shared__ int base_s;
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(1024) void k_compact(const unsigned char* __restric
         int off = base_s;
         for (int w = 0; w < wave; ++w) off += wave_tot[w];
         const int pos = off + before;
-        if (f && pos < max_n) {
+        if (f && pos < limit) {
             const int k = (int)(t % R), j = (int)((t / R) % R), i = (int)(t / ((size_t)R * R));
             const size_t o = (size_t)b * max_n + pos;
             index[o * 3] = i; index[o * 3 + 1] = j; index[o * 3 + 2] = k;
@@ -123,6 +126,161 @@ __global__ __launch_bounds__(1024) void k_compact(const unsigned char* __restric
     if (threadIdx.x == 0) count[b] = base_s;
 }
 
+// Exclusive rank of this thread among the threads of a 1024-thread workgroup whose flag is set, and the number of set flags
+// (the ballot scan of k_compact as a function; wave_tot: 16 ints of LDS).  Every thread of the workgroup calls it.
+__device__ inline int block_rank(bool f, int* wave_tot, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(f);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    __syncthreads();                                   // the readers of the previous call are done with wave_tot
+    if (lane == 0) wave_tot[wave] = __popcll(bal);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int w = 0; w < 16; ++w) { const int c = wave_tot[w]; if (w < wave) off += c; tot += c; }
+    total = tot;
+    return off + before;
+}
+
+// float -> unsigned whose ASCENDING order is the floats' DESCENDING order (negative scores included): the usual order-preserving
+// map (flip every bit of a negative, the sign bit of a non-negative), complemented
+__device__ inline unsigned key_desc(float v) {
+    const unsigned u = __float_as_uint(v);
+    return ~(u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u));
+}
+
+// Ranked selection (grasp_utils.py:105, np.argsort(scores)[::-1][:top_k], over ALL survivors), one workgroup per volume:
+//   1. ordered compaction of the survivors' (key, linear index) pairs, as k_compact;
+//   2. a stable least-significant-bit-first binary radix sort of the pairs by key, 32 passes between two buffers (a pass whose bit
+//      is the same in every key moves nothing and is skipped): stable, so equal scores stay in ascending linear index;
+//   3. the first `limit` pairs become the output rows.
+// ka/kb, ia/ib: [B, R^3] each.  count[b] = all survivors.
+__global__ __launch_bounds__(1024) void k_rank(const unsigned char* __restrict__ keep, const float* __restrict__ q,
+                                               const float* __restrict__ rot, const float* __restrict__ width, int R, int max_n,
+                                               int limit, unsigned* ka, unsigned* kb, int* ia, int* ib, int* __restrict__ count,
+                                               int* __restrict__ index, float* __restrict__ score, float* __restrict__ quat,
+                                               float* __restrict__ width_out) {
+    __shared__ int wave_tot[16];
+    __shared__ int zeros[32];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t n = (size_t)R * R * R;
+    const unsigned char* kp = keep + (size_t)b * n;
+    const float* qb = q + (size_t)b * n;
+    ka += (size_t)b * n; kb += (size_t)b * n; ia += (size_t)b * n; ib += (size_t)b * n;
+    if (tid < 32) zeros[tid] = 0;
+    int m = 0;
+    for (size_t c0 = 0; c0 < n; c0 += 1024) {
+        const size_t t = c0 + tid;
+        const bool f = t < n && kp[t];
+        int tot;
+        const int pos = m + block_rank(f, wave_tot, tot);
+        if (f) { ka[pos] = key_desc(qb[t]); ia[pos] = (int)t; }
+        m += tot;
+    }
+    __syncthreads();                                   // the pairs are written (and zeros[] is cleared)
+    for (int c0 = 0; c0 < m; c0 += 1024) {             // zeros[bit] = keys whose bit is 0: a permutation does not change it
+        const bool v = c0 + tid < m;
+        const unsigned key = v ? ka[c0 + tid] : 0u;
+        for (int bit = 0; bit < 32; ++bit) {
+            const unsigned long long bal = __ballot(v && !((key >> bit) & 1u));
+            if ((tid & 63) == 0 && bal) atomicAdd(&zeros[bit], __popcll(bal));
+        }
+    }
+    __syncthreads();
+    for (int bit = 0; bit < 32; ++bit) {
+        const int nz = zeros[bit];
+        if (nz == 0 || nz == m) continue;              // uniform over the workgroup
+        int b0 = 0, b1 = nz;
+        for (int c0 = 0; c0 < m; c0 += 1024) {
+            const bool v = c0 + tid < m;
+            const unsigned key = v ? ka[c0 + tid] : 0u;
+            const int id = v ? ia[c0 + tid] : 0;
+            const bool z = v && !((key >> bit) & 1u);
+            int tz;
+            const int rz = block_rank(z, wave_tot, tz);
+            const int valid = min(m - c0, 1024);
+            if (v) {
+                const int pos = z ? b0 + rz : b1 + (tid - rz);         // tid - rz: the ones in front of this thread
+                kb[pos] = key; ib[pos] = id;
+            }
+            b0 += tz; b1 += valid - tz;
+        }
+        __syncthreads();                               // this pass's writes, before the next pass reads them
+        unsigned* tk = ka; ka = kb; kb = tk;
+        int* ti = ia; ia = ib; ib = ti;
+    }
+    const int rows = min(m, limit);
+    for (int r = tid; r < rows; r += 1024) {
+        const size_t t = (size_t)ia[r];
+        const int k = (int)(t % R), j = (int)((t / R) % R), i = (int)(t / ((size_t)R * R));
+        const size_t o = (size_t)b * max_n + r;
+        index[o * 3] = i; index[o * 3 + 1] = j; index[o * 3 + 2] = k;
+        score[o] = qb[t];
+        for (int c = 0; c < 4; ++c) quat[o * 4 + c] = rot[((size_t)b * 4 + c) * n + t];
+        width_out[o] = width[(size_t)b * n + t];
+    }
+    if (tid == 0) count[b] = m;
+}
+
+// ---- surface point cloud (draw_utils.py:355-377): the voxels with lo < vol < hi in nonzero (ascending linear index) order ----
+// 1. voxels in range per chunk of 1024;  2. exclusive scan of the chunk counts per volume;  3. every chunk writes its rows.
+__device__ inline bool in_range(float v, float lo, float hi) { return v > lo && v < hi; }
+
+__global__ __launch_bounds__(1024) void k_surf_count(const float* __restrict__ vol, size_t n, float lo, float hi, int* __restrict__ chunk) {
+    __shared__ int wave_tot[16];
+    const size_t t = (size_t)blockIdx.x * 1024 + threadIdx.x;
+    int tot;
+    block_rank(t < n && in_range(vol[(size_t)blockIdx.y * n + t], lo, hi), wave_tot, tot);
+    if (threadIdx.x == 0) chunk[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(1024) void k_surf_scan(int* __restrict__ chunk, int nc, int* __restrict__ count) {
+    __shared__ int wave_tot[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int* c = chunk + (size_t)blockIdx.x * nc;
+    int base = 0;
+    for (int c0 = 0; c0 < nc; c0 += 1024) {
+        const int t = c0 + threadIdx.x;
+        const int v = t < nc ? c[t] : 0;
+        int inc = v;
+        for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(inc, d); if (lane >= d) inc += u; }
+        __syncthreads();
+        if (lane == 63) wave_tot[wave] = inc;
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int w = 0; w < 16; ++w) { const int s = wave_tot[w]; if (w < wave) off += s; tot += s; }
+        if (t < nc) c[t] = base + off + inc - v;
+        base += tot;
+    }
+    if (threadIdx.x == 0) count[blockIdx.x] = base;
+}
+
+struct SurfColor { int value_map; float rgb[3]; float a, b, m; };
+
+__global__ __launch_bounds__(1024) void k_surf_write(const float* __restrict__ vol, int R, size_t n, float lo, float hi, SurfColor col,
+                                                     double scale, const int* __restrict__ chunk, int max_n, int* __restrict__ index,
+                                                     double* __restrict__ points, float* __restrict__ colors) {
+    __shared__ int wave_tot[16];
+    const int b = blockIdx.y;
+    const size_t t = (size_t)blockIdx.x * 1024 + threadIdx.x;
+    const float v = t < n ? vol[(size_t)b * n + t] : 0.f;
+    const bool f = t < n && in_range(v, lo, hi);
+    int tot;
+    const int pos = chunk[(size_t)b * gridDim.x + blockIdx.x] + block_rank(f, wave_tot, tot);
+    if (!f || pos >= max_n) return;
+    const int k = (int)(t % R), j = (int)((t / R) % R), i = (int)(t / ((size_t)R * R));
+    const size_t o = ((size_t)b * max_n + pos) * 3;
+    index[o] = i; index[o + 1] = j; index[o + 2] = k;
+    points[o] = (double)i * scale; points[o + 1] = (double)j * scale; points[o + 2] = (double)k * scale;
+    float r = col.rgb[0], g = col.rgb[1], bl = col.rgb[2];
+    if (col.value_map) {                               // draw_utils.py:364-370, float32, no multiplication: nothing to contract
+        const bool low = v <= col.m;
+        r = low ? v - col.a : -v + col.b;
+        g = low ? 0.f : 1.f - r;
+        bl = low ? 1.f - r : 0.f;
+    }
+    colors[o] = r; colors[o + 1] = g; colors[o + 2] = bl;
+}
+
 }  // namespace gnr_post
 
 using namespace gnr_post;
@@ -135,16 +293,31 @@ extern "C" size_t gnr_grasp_select_workspace_bytes(int B, int R) {
     return 2 * al256(n * sizeof(float)) + 3 * al256(n);
 }
 
-extern "C" int gnr_grasp_select_fwd(const float* tsdf, const float* qual, const float* rot, const float* width, int B, int R,
-                                    const GnrSelectParams* p, float* qual_out, int* count, int* index, float* score, float* quat,
-                                    float* width_out, int max_n, void* ws, size_t ws_bytes, void* stream) {
+extern "C" size_t gnr_grasp_select_v2_workspace_bytes(int B, int R, int order) {
+    if (B < 1 || R < 1) return 0;
+    const size_t n = (size_t)B * R * R * R;
+    return gnr_grasp_select_workspace_bytes(B, R) + (order == GNR_SELECT_ORDER_SCORE ? 4 * al256(n * 4) : 0);
+}
+
+// Both select entry points: `who` = 0 the original call (its refusals keep their texts), 1 the v2 call.
+static int select_impl(int who, const float* tsdf, const float* qual, const float* rot, const float* width, int B, int R,
+                       const GnrSelectParams* p, float outside, int order, int top_k, float* qual_out, int* count, int* index,
+                       float* score, float* quat, float* width_out, int max_n, void* ws, size_t ws_bytes, void* stream) {
+    static const char* const text[2][3] = {
+        {"gnr_grasp_select_fwd: null pointer", "gnr_grasp_select_fwd: bad B / R / max_n", "gnr_grasp_select_fwd: bad filter parameters"},
+        {"gnr_grasp_select_v2_fwd: null pointer", "gnr_grasp_select_v2_fwd: bad B / R / max_n", "gnr_grasp_select_v2_fwd: bad filter parameters"}};
     if (!tsdf || !qual || !rot || !width || !p || !qual_out || !count || !index || !score || !quat || !width_out || !ws)
-        return fail(GNR_ERR_ARG, "gnr_grasp_select_fwd: null pointer");
-    if (B < 1 || R < 2 || R > 256 || max_n < 1) return fail(GNR_ERR_SHAPE, "gnr_grasp_select_fwd: bad B / R / max_n");
+        return fail(GNR_ERR_ARG, text[who][0]);
+    if (B < 1 || R < 2 || R > 256 || max_n < 1) return fail(GNR_ERR_SHAPE, text[who][1]);
     if (p->gauss_radius < 0 || p->gauss_radius > GNR_GAUSS_MAX_RADIUS || p->dilate_iterations < 0 || p->max_filter_size < 1 ||
         p->max_filter_size > 16)
-        return fail(GNR_ERR_ARG, "gnr_grasp_select_fwd: bad filter parameters");
-    if (ws_bytes < gnr_grasp_select_workspace_bytes(B, R)) return fail(GNR_ERR_WORKSPACE, "workspace too small");
+        return fail(GNR_ERR_ARG, text[who][2]);
+    if (order != GNR_SELECT_ORDER_INDEX && order != GNR_SELECT_ORDER_SCORE)
+        return fail(GNR_ERR_ARG, "gnr_grasp_select_v2_fwd: order must be GNR_SELECT_ORDER_INDEX or GNR_SELECT_ORDER_SCORE");
+    if (top_k < 0) return fail(GNR_ERR_ARG, "gnr_grasp_select_v2_fwd: top_k must be >= 0 (0: as many as max_n)");
+    if (order == GNR_SELECT_ORDER_SCORE && R > GNR_SELECT_SCORE_MAX_R)
+        return fail(GNR_ERR_SHAPE, "gnr_grasp_select_v2_fwd: GNR_SELECT_ORDER_SCORE takes R <= 64 (2^18 voxels per scene to rank)");
+    if (ws_bytes < gnr_grasp_select_v2_workspace_bytes(B, R, order)) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)B * R * R * R;
     char* base = (char*)ws;
@@ -152,7 +325,7 @@ extern "C" int gnr_grasp_select_fwd(const float* tsdf, const float* qual, const 
     float* fb = (float*)base;                      base += al256(n * sizeof(float));
     unsigned char* xa = (unsigned char*)base;      base += al256(n);
     unsigned char* xb = (unsigned char*)base;      base += al256(n);
-    unsigned char* mk = (unsigned char*)base;
+    unsigned char* mk = (unsigned char*)base;      base += al256(n);
     const unsigned blocks = (unsigned)((n + 255) / 256);
     GaussW g;
     g.radius = p->gauss_radius;
@@ -162,7 +335,7 @@ extern "C" int gnr_grasp_select_fwd(const float* tsdf, const float* qual, const 
     if (int rc = launch<k_gauss_axis>(nullptr, st, grid, block, 0, qual, fa, R, R * R, g, n)) return rc;
     if (int rc = launch<k_gauss_axis>(nullptr, st, grid, block, 0, fa, fb, R, R, g, n)) return rc;
     if (int rc = launch<k_gauss_axis>(nullptr, st, grid, block, 0, fb, fa, R, 1, g, n)) return rc;
-    if (int rc = launch<k_masks>(nullptr, st, grid, block, 0, tsdf, xa, mk, p->tsdf_thres_high, p->tsdf_thres_low, n)) return rc;
+    if (int rc = launch<k_masks>(nullptr, st, grid, block, 0, tsdf, xa, mk, outside, p->tsdf_thres_high, p->tsdf_thres_low, n)) return rc;
     unsigned char *xin = xa, *xout = xb;
     for (int it = 0; it < p->dilate_iterations; ++it) {
         if (int rc = launch<k_dilate>(nullptr, st, grid, block, 0, xin, mk, xout, R, n)) return rc;
@@ -170,5 +343,55 @@ extern "C" int gnr_grasp_select_fwd(const float* tsdf, const float* qual, const 
     }
     if (int rc = launch<k_finalize>(nullptr, st, grid, block, 0, fa, xin, width, qual_out, fb, p->min_width, p->max_width, p->threshold, n)) return rc;
     if (int rc = launch<k_nms>(nullptr, st, grid, block, 0, fb, xout, R, p->max_filter_size, n)) return rc;
-    return launch<k_compact>(nullptr, st, dim3(B), dim3(1024), 0, xout, fb, rot, width, R, max_n, count, index, score, quat, width_out);
+    const int limit = top_k > 0 && top_k < max_n ? top_k : max_n;
+    if (order == GNR_SELECT_ORDER_INDEX)
+        return launch<k_compact>(nullptr, st, dim3(B), dim3(1024), 0, xout, fb, rot, width, R, max_n, limit, count, index, score, quat, width_out);
+    unsigned* ka = (unsigned*)base;                base += al256(n * 4);
+    unsigned* kb = (unsigned*)base;                base += al256(n * 4);
+    int* ia = (int*)base;                          base += al256(n * 4);
+    int* ib = (int*)base;
+    return launch<k_rank>(nullptr, st, dim3(B), dim3(1024), 0, xout, fb, rot, width, R, max_n, limit, ka, kb, ia, ib, count, index, score,
+                          quat, width_out);
+}
+
+extern "C" int gnr_grasp_select_fwd(const float* tsdf, const float* qual, const float* rot, const float* width, int B, int R,
+                                    const GnrSelectParams* p, float* qual_out, int* count, int* index, float* score, float* quat,
+                                    float* width_out, int max_n, void* ws, size_t ws_bytes, void* stream) {
+    return select_impl(0, tsdf, qual, rot, width, B, R, p, p ? p->tsdf_thres_high : 0.f, GNR_SELECT_ORDER_INDEX, 0, qual_out, count, index,
+                       score, quat, width_out, max_n, ws, ws_bytes, stream);
+}
+
+extern "C" int gnr_grasp_select_v2_fwd(const float* tsdf, const float* qual, const float* rot, const float* width, int B, int R,
+                                       const GnrSelectParamsV2* p, float* qual_out, int* count, int* index, float* score, float* quat,
+                                       float* width_out, int max_n, void* ws, size_t ws_bytes, void* stream) {
+    return select_impl(1, tsdf, qual, rot, width, B, R, p ? &p->select : nullptr, p ? p->tsdf_thres_outside : 0.f, p ? p->order : 0,
+                       p ? p->top_k : 0, qual_out, count, index, score, quat, width_out, max_n, ws, ws_bytes, stream);
+}
+
+extern "C" size_t gnr_surface_points_workspace_bytes(int B, int R) {
+    if (B < 1 || R < 1) return 0;
+    const size_t nc = ((size_t)R * R * R + 1023) / 1024;
+    return al256((size_t)B * nc * sizeof(int));
+}
+
+extern "C" int gnr_surface_points_fwd(const float* vol, int B, int R, const GnrSurfaceParams* p, int* count, int* index, double* points,
+                                      float* colors, int max_n, void* ws, size_t ws_bytes, void* stream) {
+    if (!vol || !p || !count || !index || !points || !colors || !ws) return fail(GNR_ERR_ARG, "gnr_surface_points_fwd: null pointer");
+    if (B < 1 || B > 65535 || R < 1 || R > 256 || max_n < 1) return fail(GNR_ERR_SHAPE, "gnr_surface_points_fwd: bad B / R / max_n (R <= 256)");
+    if (p->color_mode != GNR_SURFACE_COLOR_FIXED && p->color_mode != GNR_SURFACE_COLOR_VALUE)
+        return fail(GNR_ERR_ARG, "gnr_surface_points_fwd: color_mode must be GNR_SURFACE_COLOR_FIXED or GNR_SURFACE_COLOR_VALUE");
+    if (ws_bytes < gnr_surface_points_workspace_bytes(B, R)) return fail(GNR_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)R * R * R;
+    const int nc = (int)((n + 1023) / 1024);
+    int* chunk = (int*)ws;
+    SurfColor col;
+    col.value_map = p->color_mode == GNR_SURFACE_COLOR_VALUE;
+    for (int c = 0; c < 3; ++c) col.rgb[c] = p->color[c];
+    col.a = p->bound_a; col.b = p->bound_b;
+    col.m = (p->bound_a + p->bound_b) / 2.f;
+    const dim3 grid(nc, B), block(1024);
+    if (int rc = launch<k_surf_count>(nullptr, st, grid, block, 0, vol, n, p->lo, p->hi, chunk)) return rc;
+    if (int rc = launch<k_surf_scan>(nullptr, st, dim3(B), block, 0, chunk, nc, count)) return rc;
+    return launch<k_surf_write>(nullptr, st, grid, block, 0, vol, R, n, p->lo, p->hi, col, p->scale, (const int*)chunk, max_n, index, points, colors);
 }

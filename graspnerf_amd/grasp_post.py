@@ -1,6 +1,8 @@
 """Device-side grasp post-processing: the reference planner's `process` + `select` (ref: src/nr/main.py:23-84) as HIP
 kernels (csrc/gnr_post.hip) instead of scipy.ndimage on the host, plus the host-side tail of `GraspNeRFPlanner.__call__`
-(main.py:197-209: seeded permutation, voxel -> metric coordinates)."""
+(main.py:197-209: seeded permutation, voxel -> metric coordinates).  The real-robot route of src/nr/utils/grasp_utils.py and
+draw_utils.py is here too: `process` with its three thresholds (GRASP_UTILS_PROCESS), `sim_grasp`'s ranking by score
+(order='score', top_k), and the surface point cloud of `extract_surface_points_from_volume` (SurfaceExtractor, write_ply)."""
 import ctypes as C
 
 import numpy as np
@@ -20,6 +22,12 @@ def gaussian_weights(sigma, truncate=4.0):
     return r, w[r:]
 
 
+# the defaults and thresholds of grasp_utils.process (grasp_utils.py:40-68): outside tsdf > 0.1, inside -1 < tsdf < -0.1, widths 0..12
+GRASP_UTILS_PROCESS = dict(gaussian_filter_sigma=1.0, min_width=0, max_width=12, tsdf_thres_outside=0.1, tsdf_thres_high=-0.1,
+                           tsdf_thres_low=-1)
+_ORDERS = {'index': _lib.GNR_SELECT_ORDER_INDEX, 'score': _lib.GNR_SELECT_ORDER_SCORE}
+
+
 class GraspSelector:
     """process() + select() for B scenes at once.  Defaults are the reference functions' defaults; the planner passes
     tsdf_thres_high=0, tsdf_thres_low=-0.85 (main.py:93-94,199)."""
@@ -33,10 +41,18 @@ class GraspSelector:
         self._ws = None
 
     def __call__(self, tsdf, qual, rot, width, gaussian_filter_sigma=1.0, min_width=1.33, max_width=9.33,
-                 tsdf_thres_high=0.5, tsdf_thres_low=1e-3, threshold=0.90, max_filter_size=4):
+                 tsdf_thres_high=0.5, tsdf_thres_low=1e-3, threshold=0.90, max_filter_size=4, tsdf_thres_outside=None, order='index',
+                 top_k=None):
         """tsdf, qual, width [B,1,R,R,R] (or [B,R,R,R]); rot [B,4,R,R,R]  ->  dict of device tensors:
         qual [B,R,R,R] processed quality; count [B]; index [B,max,3] int32; score [B,max]; quat [B,max,4]; width [B,max]
-        (entries beyond count[b] are undefined)."""
+        (entries beyond count[b] are undefined).
+        tsdf_thres_outside: the outside threshold when it is not tsdf_thres_high (grasp_utils.py:59-60);  order: 'index' (np.argwhere
+        order) or 'score' (descending score over ALL survivors, ties by ascending voxel index; R <= 64);  top_k: store the first
+        top_k rows only (count still reports every survivor).  The result carries `order` and `top_k` for grasps_from_selection."""
+        if order not in _ORDERS:
+            raise ValueError(f"order must be 'index' or 'score', got {order!r}")
+        if top_k is not None and int(top_k) < 1:
+            raise ValueError(f'top_k must be None or positive, got {top_k!r}')
         d = self.device
         f = lambda a: torch.as_tensor(a, dtype=torch.float32, device=d).contiguous()
         tsdf, qual, rot, width = f(tsdf), f(qual), f(rot), f(width)
@@ -49,27 +65,101 @@ class GraspSelector:
         p.tsdf_thres_high, p.tsdf_thres_low = float(tsdf_thres_high), float(tsdf_thres_low)
         p.min_width, p.max_width, p.threshold = float(min_width), float(max_width), float(threshold)
         p.dilate_iterations, p.max_filter_size = 2, int(max_filter_size)
-        need = self.L.gnr_grasp_select_workspace_bytes(B, R)
+        v2 = tsdf_thres_outside is not None or order != 'index' or top_k is not None
+        if v2:
+            p2 = _lib.GnrSelectParamsV2()
+            p2.select = p
+            p2.tsdf_thres_outside = float(tsdf_thres_high if tsdf_thres_outside is None else tsdf_thres_outside)
+            p2.order, p2.top_k = _ORDERS[order], int(top_k or 0)
+        need = self.L.gnr_grasp_select_v2_workspace_bytes(B, R, _ORDERS[order]) if v2 else self.L.gnr_grasp_select_workspace_bytes(B, R)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=d)
         M = self.max_grasps
         out = {'qual': torch.empty(B, R, R, R, device=d), 'count': torch.empty(B, dtype=torch.int32, device=d),
                'index': torch.empty(B, M, 3, dtype=torch.int32, device=d), 'score': torch.empty(B, M, device=d),
                'quat': torch.empty(B, M, 4, device=d), 'width': torch.empty(B, M, device=d)}
-        rc = self.L.gnr_grasp_select_fwd(tsdf.data_ptr(), qual.data_ptr(), rot.data_ptr(), width.data_ptr(), B, R,
-                                         C.byref(p), out['qual'].data_ptr(), out['count'].data_ptr(),
-                                         out['index'].data_ptr(), out['score'].data_ptr(), out['quat'].data_ptr(),
-                                         out['width'].data_ptr(), M, self._ws.data_ptr(), self._ws.numel(),
-                                         C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
-        _lib.check(rc, 'gnr_grasp_select_fwd')
+        fn, name = (self.L.gnr_grasp_select_v2_fwd, 'gnr_grasp_select_v2_fwd') if v2 else (self.L.gnr_grasp_select_fwd, 'gnr_grasp_select_fwd')
+        rc = fn(tsdf.data_ptr(), qual.data_ptr(), rot.data_ptr(), width.data_ptr(), B, R, C.byref(p2 if v2 else p),
+                out['qual'].data_ptr(), out['count'].data_ptr(), out['index'].data_ptr(), out['score'].data_ptr(),
+                out['quat'].data_ptr(), out['width'].data_ptr(), M, self._ws.data_ptr(), self._ws.numel(),
+                C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+        _lib.check(rc, name)
+        out['order'], out['top_k'] = order, None if top_k is None else int(top_k)
         return out
+
+
+class SurfaceExtractor:
+    """extract_surface_points_from_volume (draw_utils.py:355-377) for B volumes at once, on the device."""
+
+    def __init__(self, device='cuda:0'):
+        self.L = _lib.lib()
+        if not torch.cuda.is_available():
+            raise _lib.GnrError('the HIP surface extraction needs a ROCm GPU; there is no CPU fallback')
+        self.device = torch.device(device)
+        self._ws = None
+
+    def __call__(self, vol, rg=(-0.2, 0.2), bound=(-1, 1), color=(0, 0, 1), scale=0.3 / 40, max_points=None):
+        """vol [B,R,R,R] (or [B,1,R,R,R], or one [R,R,R])  ->  dict of device tensors: count [B] voxels with rg[0] < vol < rg[1];
+        index [B,max,3] int32 in np.nonzero order; points [B,max,3] float64 = index * scale; colors [B,max,3] float32 (`color`, or
+        the value map over `bound` when color is None); entries beyond count[b] are undefined.  max_points=None: R^3, nothing is
+        truncated.  The result carries `scale` and `value_map` for surface_from_extraction."""
+        d = self.device
+        vol = torch.as_tensor(vol, dtype=torch.float32, device=d).contiguous()
+        R = vol.shape[-1]
+        if vol.dim() < 3 or tuple(vol.shape[-3:]) != (R, R, R) or vol.numel() % R ** 3:
+            raise ValueError(f'vol must be [B,R,R,R], got {tuple(vol.shape)}')
+        B = vol.numel() // R ** 3
+        M = R ** 3 if max_points is None else int(max_points)
+        p = _lib.GnrSurfaceParams()
+        p.lo, p.hi, p.scale = float(rg[0]), float(rg[1]), float(scale)
+        p.color_mode = _lib.GNR_SURFACE_COLOR_VALUE if color is None else _lib.GNR_SURFACE_COLOR_FIXED
+        p.color[:] = [float(c) for c in (color or (0, 0, 0))]
+        p.bound_a, p.bound_b = float(bound[0]), float(bound[1])
+        need = self.L.gnr_surface_points_workspace_bytes(B, R)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=d)
+        out = {'count': torch.empty(B, dtype=torch.int32, device=d), 'index': torch.empty(B, M, 3, dtype=torch.int32, device=d),
+               'points': torch.empty(B, M, 3, dtype=torch.float64, device=d), 'colors': torch.empty(B, M, 3, device=d)}
+        rc = self.L.gnr_surface_points_fwd(vol.data_ptr(), B, R, C.byref(p), out['count'].data_ptr(), out['index'].data_ptr(),
+                                           out['points'].data_ptr(), out['colors'].data_ptr(), M, self._ws.data_ptr(),
+                                           self._ws.numel(), C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+        _lib.check(rc, 'gnr_surface_points_fwd')
+        out['scale'], out['value_map'] = float(scale), color is None
+        return out
+
+
+def surface_from_extraction(res, b=0):
+    """Scene b of a SurfaceExtractor result -> numpy dict: `index` [N,3] int64, `points` [N,3] float64 (metres), `colors` [N,3]
+    float64 (what open3d's Vector3dVector holds).  Raises when the buffers held fewer rows than the scene has voxels in range."""
+    n = int(res['count'][b].item())
+    if n > res['index'].shape[1]:
+        raise _lib.GnrError(f'{n} surface voxels but the buffers hold {res["index"].shape[1]}: raise max_points')
+    return {'index': res['index'][b, :n].cpu().numpy().astype(np.int64), 'points': res['points'][b, :n].cpu().numpy(),
+            'colors': res['colors'][b, :n].cpu().numpy().astype(np.float64)}
+
+
+def write_ply(path, points, colors):
+    """A point cloud as an ASCII PLY 1.0 file (draw_utils.py:382 writes open3d's): x y z as float64, colours in [0, 1] as uchar."""
+    points, colors = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(colors, np.float64).reshape(-1, 3)
+    if len(points) != len(colors):
+        raise ValueError(f'{len(points)} points but {len(colors)} colours')
+    rgb = np.clip(np.floor(colors * 255.0 + 0.5), 0, 255).astype(np.uint8)
+    with open(path, 'w') as f:
+        f.write('ply\nformat ascii 1.0\ncomment graspnerf_amd surface cloud\n'
+                f'element vertex {len(points)}\nproperty double x\nproperty double y\nproperty double z\n'
+                'property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
+        for (x, y, z), (r, g, b) in zip(points.tolist(), rgb.tolist()):
+            f.write(f'{x!r} {y!r} {z!r} {r} {g} {b}\n')
 
 
 def grasps_from_selection(sel, b=0, voxel_size=0.3 / 40, seed=None):
     """Scene b of a GraspSelector result -> numpy dict in the reference's conventions (main.py:79-84,201-209):
     `pos` = voxel index * voxel_size (metres, bbox-local), `quat` normalised (x,y,z,w; scipy Rotation.from_quat),
-    `width` in metres, `score`, `index`; permuted with np.random.seed(seed) like the planner when seed is given."""
+    `width` in metres, `score`, `index`; permuted with np.random.seed(seed) like the planner when seed is given.
+    A result made with top_k holds min(count, top_k) rows by request (ranked: sim_grasp's list, grasp_utils.py:105)."""
     n = int(sel['count'][b].item())
+    if sel.get('top_k') is not None:
+        n = min(n, sel['top_k'])
     if n > sel['index'].shape[1]:
         # the reference's select() returns EVERY non-maximum-suppression survivor (main.py:70-84); a truncated list (in
         # index order, before the seeded permutation) would silently be a different result

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from .renderer import GraspNeRF
-from .grasp_post import GraspSelector, grasps_from_selection
+from .grasp_post import GRASP_UTILS_PROCESS, GraspSelector, SurfaceExtractor, grasps_from_selection, surface_from_extraction
 from .ingest import axis_tables
 from .planner_session import PlannerSession
 
@@ -60,15 +60,18 @@ def core(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8),
 
 def plan(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497)),
          seed=None, selector=None, tsdf_thres_high=0.0, tsdf_thres_low=-0.85, voxel_size=0.3 / 40, return_volumes=False,
-         session=None):
+         session=None, tsdf_thres_outside=None, order='index', top_k=None, que_id=0):
     """`GraspNeRFPlanner.__call__` from arrays (main.py:185-209): forward, process + select on the device, seeded
     permutation, voxel -> metric.  -> (grasps dict of numpy arrays: pos, quat, width, score, index; forward seconds).
     session: a PlannerSession of this net -- `images` are then the raw uint8 frames [V,h,w,c] and the whole plan is one replay
-    of the session's captured graph (the thresholds and the voxel size are the session's: they must agree with the arguments)."""
+    of the session's captured graph (the thresholds and the voxel size are the session's: they must agree with the arguments).
+    tsdf_thres_outside, order, top_k: GraspSelector's (the outside threshold of grasp_utils.process, ranking by score, a prefix);
+    que_id: the view the one-pixel query render of the eager forward is taken from (the volume does not depend on it)."""
     if session is not None:
         sp = session.selector_params
-        if session.net is not net or selector is not None or (sp['tsdf_thres_high'], sp['tsdf_thres_low'], session.voxel_size) != \
-                (tsdf_thres_high, tsdf_thres_low, voxel_size):
+        if session.net is not net or selector is not None or \
+                (sp['tsdf_thres_high'], sp['tsdf_thres_low'], session.voxel_size, sp['tsdf_thres_outside'], sp['order'], sp['top_k']) != \
+                (tsdf_thres_high, tsdf_thres_low, voxel_size, tsdf_thres_outside, order, top_k):
             raise ValueError('plan(session=...): the session was built for another net, thresholds or voxel size '
                              '(its GraspSelector is its own: pass no selector)')
         return session.plan(images, extrinsics, intrinsics, depth_range, bbox3d, seed=seed, return_volumes=return_volumes)
@@ -78,8 +81,8 @@ def plan(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-
     ext = np.asarray(extrinsics, np.float32)[:, :3, :]
     dr = np.broadcast_to(np.asarray(depth_range, np.float32), (V, 2)) if np.ndim(depth_range) == 1 else np.asarray(depth_range, np.float32)
     ref = {'imgs': t(images), 'poses': t(ext), 'Ks': t(intrinsics), 'depth_range': t(dr), 'bbox3d': t(bbox3d)}
-    que = {'poses': t(ext[0])[None], 'Ks': t(np.asarray(intrinsics, np.float32)[0])[None],
-           'coords': torch.zeros(1, 1, 2, device=dev), 'depth_range': t(dr[0])[None]}
+    que = {'poses': t(ext[que_id])[None], 'Ks': t(np.asarray(intrinsics, np.float32)[que_id])[None],
+           'coords': torch.zeros(1, 1, 2, device=dev), 'depth_range': t(dr[que_id])[None]}
     data = {'step': 0, 'eval': True, 'full_vol': True, 'ref_imgs_info': ref, 'que_imgs_info': que, 'src_imgs_info': dict(ref)}
     selector = selector or GraspSelector(dev)
     with torch.no_grad():
@@ -87,13 +90,86 @@ def plan(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-
         t0 = time.time()
         out = net(data)
         q, r, wd = out['vgn_pred']
-        sel = selector(out['volume'], q, r, wd, tsdf_thres_high=tsdf_thres_high, tsdf_thres_low=tsdf_thres_low)
+        new = {k: v for k, v in (('tsdf_thres_outside', tsdf_thres_outside), ('top_k', top_k)) if v is not None}
+        if order != 'index':                                                      # (a caller's own selector sees today's call otherwise)
+            new['order'] = order
+        sel = selector(out['volume'], q, r, wd, tsdf_thres_high=tsdf_thres_high, tsdf_thres_low=tsdf_thres_low, **new)
         torch.cuda.synchronize(dev)
         dt = time.time() - t0
     grasps = grasps_from_selection(sel, 0, voxel_size, seed)
     if return_volumes:
         grasps['volumes'] = tuple(x.cpu().numpy() for x in (out['volume'], q, r, wd, sel['qual']))
     return grasps, dt
+
+
+# ---- the real-robot route (ref: src/nr/utils/grasp_utils.py:119-151) ------------------------------------------------------
+REAL_BBOX3D = ((-0.15, -0.15, 0.0), (0.15, 0.15, 0.3))                                                    # grasp_utils.py:123
+REAL_DEPTH_RANGE, REAL_QUE_ID, REAL_VOXEL_SIZE = (0.2, 0.8), 3, 0.3 / 40                                  # grasp_utils.py:122,137,146
+
+
+def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, **kw):
+    """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud."""
+    return PlannerSession(net, n_views, src_hw, img_wh, max_grasps=max_grasps, voxel_size=REAL_VOXEL_SIZE,
+                          surface=dict(rg=tuple(surface_rg)), order='score' if order == 'score' else 'index', top_k=top_k,
+                          **GRASP_UTILS_PROCESS, **kw)
+
+
+def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None):
+    """`run_real` (grasp_utils.py:119-151) without its file output: one plan from camera frames.
+    images: V >= 4 uint8 frames [h,w,3] (list or array); extrinsics: V world->camera [3|4,4]; intrinsic [3,3], the same for every view.
+    run_real's workspace box, depth range (0.2, 0.8) and query view 3; grasp_utils.process's thresholds (GRASP_UTILS_PROCESS),
+    select's defaults.  order='permuted': every survivor, permuted (np.random.seed(seed) first when a seed is given; run_real draws
+    from the global state);  order='score': ranked by descending score, best first -- with top_k=10 sim_grasp's list
+    (grasp_utils.py:105).  session: a real_session of this net for these frames -- the whole plan is then one replay of its graph.
+    -> (grasps dict: pos (metres), quat, width, score, index;  scores;  tsdf_vol [R,R,R];
+        cloud dict: points [N,3] float64, colors [N,3], index [N,3] of the voxels with surface_rg[0] < tsdf < surface_rg[1];  seconds)."""
+    if order not in ('permuted', 'score'):
+        raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
+    ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
+    V = ext.shape[0]
+    if V <= REAL_QUE_ID:
+        raise ValueError(f'run_real renders its query from view {REAL_QUE_ID} (grasp_utils.py:137): it needs at least '
+                         f'{REAL_QUE_ID + 1} views, got {V}')
+    if len(images) != V:
+        raise ValueError(f'{len(images)} images but {V} extrinsics')
+    Ks = np.repeat(np.asarray(intrinsic, np.float32)[None], V, 0)
+    sel_order = 'score' if order == 'score' else 'index'
+    if session is not None:
+        sp, su = session.selector_params, session.surface_params
+        want = dict(GRASP_UTILS_PROCESS, order=sel_order, top_k=top_k)
+        if session.net is not net or su is None or tuple(su['rg']) != tuple(surface_rg) or any(sp[k] != v for k, v in want.items()) \
+                or session.voxel_size != REAL_VOXEL_SIZE:
+            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k or surface range '
+                             '(build it with planner.real_session)')
+        g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
+        tsdf_vol, cloud = g.pop('volumes')[0], session.cloud
+    else:
+        dev = next(net.parameters()).device
+        frames = np.stack([np.asarray(f) for f in images], 0)
+        if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3:
+            raise ValueError(f'images must be uint8 [V,h,w,3] frames, got {frames.dtype} {frames.shape}')
+        imgs = (frames.astype(np.float32) / 255).transpose([0, 3, 1, 2])                                  # color_map_forward, grasp_utils.py:134
+        selector = GraspSelector(dev)
+        call = lambda vol, q, r, w, **kw: selector(vol, q, r, w, **{**kw, **GRASP_UTILS_PROCESS})
+        was = torch.backends.cudnn.deterministic                  # the solvers a PlannerSession records: the same frames, the same bits
+        torch.backends.cudnn.deterministic = True
+        try:
+            g, dt = plan(net, imgs, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, selector=call, voxel_size=REAL_VOXEL_SIZE,
+                         tsdf_thres_high=GRASP_UTILS_PROCESS['tsdf_thres_high'], tsdf_thres_low=GRASP_UTILS_PROCESS['tsdf_thres_low'],
+                         order=sel_order, top_k=top_k, return_volumes=True, que_id=REAL_QUE_ID)
+        finally:
+            torch.backends.cudnn.deterministic = was
+        tsdf_vol = g.pop('volumes')[0]
+        res = SurfaceExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), rg=surface_rg)                 # grasp_utils.py:149
+        cloud = surface_from_extraction(res, 0)
+    tsdf_vol = np.asarray(tsdf_vol).reshape(tsdf_vol.shape[-3:])
+    n = len(g['score'])
+    if order == 'permuted' and n > 0:                                                                     # grasp_utils.py:144-147
+        if seed is not None:
+            np.random.seed(seed)
+        p = np.random.permutation(n)
+        g = {k: v[p] for k, v in g.items()}
+    return g, g['score'], tsdf_vol, cloud, dt
 
 
 # ---- the planner's file I/O (SURVEY.md §8f N4; ref: src/nr/main.py:87-209) -----------------------------------------------

@@ -13,11 +13,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import GraspSelector, grasps_from_selection
+from .grasp_post import GraspSelector, SurfaceExtractor, grasps_from_selection
 from .ingest import DeviceIngest
 
 _SELECTOR_DEFAULTS = {k: p.default for k, p in inspect.signature(GraspSelector.__call__).parameters.items()
                       if p.default is not inspect.Parameter.empty}
+_SURFACE_DEFAULTS = {k: p.default for k, p in inspect.signature(SurfaceExtractor.__call__).parameters.items()
+                     if p.default is not inspect.Parameter.empty}
 _SEG = 64                                                    # floats: every camera block starts on a 256-byte boundary
 
 
@@ -29,10 +31,17 @@ class PlannerSession:
     passes tsdf_thres_high=0.0, tsdf_thres_low=-0.85, main.py:93-94,199);  channels: 3, or 4 for RGBA frames (alpha ignored);
     deterministic: the convolutions of the 2D backbones are recorded with MIOpen's deterministic solvers, so the same frames and
     cameras give the same bits on every replay (its default solvers for some of the strided layers sum in arrival order: an
-    eager forward differs from itself by ~1e-5); False records whatever MIOpen picks."""
+    eager forward differs from itself by ~1e-5); False records whatever MIOpen picks.
+    The real-robot route (planner.plan_real): the selector parameters tsdf_thres_outside / order / top_k, and surface = dict(rg=...,
+    bound=..., color=..., max_points=...) (keyword arguments of SurfaceExtractor.__call__; {} for its defaults) adds the surface
+    point cloud of the volume to the graph; self.cloud then holds the last plan's cloud (index, points, colors as numpy).  The
+    read-back of the cloud is sized by its row count: the counts come with the selection, then ONE copy of the stored index rows
+    (and of the colours in value-map mode; a fixed colour is known on the host); the float64 points stay on the device (the graph's
+    output `surface`) and are recomputed on the host as index * scale, which is the same float64 product.  A session built
+    without any of these records the graph it always recorded."""
 
     def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
-                 **selector_params):
+                 surface=None, **selector_params):
         cfg = net.nr_net.cfg
         if cfg.get('warn_low_valid_ratio', False):
             raise ValueError("graph capture cannot read the valid ratio back on every call: unset cfg['warn_low_valid_ratio']")
@@ -41,6 +50,10 @@ class PlannerSession:
         unknown = sorted(set(selector_params) - set(_SELECTOR_DEFAULTS))
         if unknown:
             raise TypeError(f'unknown selector parameters {unknown}; GraspSelector takes {sorted(_SELECTOR_DEFAULTS)}')
+        if surface is not None:
+            unknown = sorted(set(surface) - set(_SURFACE_DEFAULTS))
+            if unknown:
+                raise TypeError(f'unknown surface parameters {unknown}; SurfaceExtractor takes {sorted(_SURFACE_DEFAULTS)}')
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise _lib.GnrError('PlannerSession needs the model on a ROCm GPU; there is no CPU fallback')
@@ -71,9 +84,18 @@ class PlannerSession:
         self._d = view(self._d_cam)
         self.images = torch.zeros(V, 3, H, W, dtype=torch.float32, device=dev)       # the ingested frames of the last plan
         # the selection, packed for one read-back: count | index [M,3] | score [M] | quat [M,4] | width [M], 4-byte words
-        self._d_out = torch.zeros(1 + 9 * M, dtype=torch.int32, device=dev)
-        self._h_out = torch.zeros(1 + 9 * M, dtype=torch.int32, pin_memory=True)
-        self.selection = None
+        # (+ the cloud's row count, when the session extracts one)
+        self.surface_params = None if surface is None else {**_SURFACE_DEFAULTS, **surface}
+        words = 1 + 9 * M + (0 if surface is None else 1)
+        self._d_out = torch.zeros(words, dtype=torch.int32, device=dev)
+        self._h_out = torch.zeros(words, dtype=torch.int32, pin_memory=True)
+        self.selection = self.cloud = None
+        if surface is not None:
+            R = int(cfg['volume_resolution'])
+            self.surface = SurfaceExtractor(dev)
+            self._surface_rows = R ** 3 if self.surface_params['max_points'] is None else int(self.surface_params['max_points'])
+            self._h_surf_index = torch.zeros(self._surface_rows, 3, dtype=torch.int32, pin_memory=True)
+            self._h_surf_colors = torch.zeros(self._surface_rows, 3, dtype=torch.float32, pin_memory=True)
         self.captures = 0
         self._set_example_cameras()
         self._capture()
@@ -104,7 +126,11 @@ class PlannerSession:
         o[1:1 + 3 * M].copy_(sel['index'].reshape(-1))
         for k, a, b in (('score', 1 + 3 * M, 1 + 4 * M), ('quat', 1 + 4 * M, 1 + 8 * M), ('width', 1 + 8 * M, 1 + 9 * M)):
             o[a:b].copy_(sel[k].reshape(-1).view(torch.int32))
-        return {'volume': vol, 'qual': q, 'rot': r, 'width': w, 'sel_qual': sel['qual']}
+        out = {'volume': vol, 'qual': q, 'rot': r, 'width': w, 'sel_qual': sel['qual']}
+        if self.surface_params is not None:
+            out['surface'] = self.surface(vol, **self.surface_params)
+            o[1 + 9 * M:2 + 9 * M].copy_(out['surface']['count'])
+        return out
 
     def _state(self):
         """What the captured graph depends on besides its static inputs: the parameter versions and addresses (the packed
@@ -160,6 +186,20 @@ class PlannerSession:
             np.copyto(dst, f)
         self._d_frames.copy_(self._h_frames, non_blocking=True)
 
+    def _read_cloud(self, count, st):
+        """The stored rows of the cloud: one sized copy of the index (and of the colours in value-map mode)."""
+        if count > self._surface_rows:
+            raise _lib.GnrError(f'{count} surface voxels but the buffers hold {self._surface_rows}: raise surface max_points')
+        sp, surf = self.surface_params, self._out['surface']
+        self._h_surf_index[:count].copy_(surf['index'][0, :count], non_blocking=True)
+        if sp['color'] is None:
+            self._h_surf_colors[:count].copy_(surf['colors'][0, :count], non_blocking=True)
+        st.synchronize()
+        index = self._h_surf_index[:count].numpy().astype(np.int64)
+        colors = self._h_surf_colors[:count].numpy().astype(np.float64) if sp['color'] is None else \
+            np.array([sp['color']], np.float64).repeat(count, axis=0)
+        return {'count': count, 'index': index, 'points': index.astype(np.float64) * float(sp['scale']), 'colors': colors}
+
     def plan(self, frames_u8, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497)),
              seed=None, return_volumes=False):
         """planner.plan() from raw frames: frames_u8 [V,h,w,c] uint8 (array, list of arrays, or a device tensor);
@@ -186,7 +226,11 @@ class PlannerSession:
         M, h = self.max_grasps, self._h_out.clone()          # the staging buffer is rewritten by the next plan
         f = lambda a, b, *shp: h[a:b].view(torch.float32).view(1, M, *shp)
         self.selection = {'count': h[0:1], 'index': h[1:1 + 3 * M].view(1, M, 3), 'score': f(1 + 3 * M, 1 + 4 * M),
-                          'quat': f(1 + 4 * M, 1 + 8 * M, 4), 'width': f(1 + 8 * M, 1 + 9 * M)}
+                          'quat': f(1 + 4 * M, 1 + 8 * M, 4), 'width': f(1 + 8 * M, 1 + 9 * M),
+                          'order': self.selector_params['order'], 'top_k': self.selector_params['top_k']}
+        if self.surface_params is not None:
+            self.cloud = self._read_cloud(int(h[1 + 9 * M]), st)
+            dt = time.time() - t0
         grasps = grasps_from_selection(self.selection, 0, self.voxel_size, seed)
         if return_volumes:
             grasps['volumes'] = tuple(self._out[k].cpu().numpy() for k in ('volume', 'qual', 'rot', 'width', 'sel_qual'))

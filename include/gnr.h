@@ -564,6 +564,61 @@ int gnr_grasp_select_fwd(const float* tsdf, const float* qual, const float* rot,
                          float* quat, float* width_out, int max_n, void* workspace, size_t workspace_bytes, void* stream);
 const char* gnr_post_last_error(void);       /* alias of gnr_last_error() */
 
+/* ---- the real-robot route (src/nr/utils/grasp_utils.py:40-151, draw_utils.py:355-382) ----
+ * gnr_grasp_select_v2_fwd: gnr_grasp_select_fwd with three more parameters; every argument, output and
+ * layout is that call's, and with tsdf_thres_outside == select.tsdf_thres_high, GNR_SELECT_ORDER_INDEX and
+ * top_k == 0 so is every bit (gnr_grasp_select_fwd is this call with those values).
+ *   tsdf_thres_outside   outside = tsdf > tsdf_thres_outside, while may_change stays
+ *                        !(tsdf_thres_low < tsdf < tsdf_thres_high): the three thresholds of
+ *                        grasp_utils.process (0.1 / -0.1 / -1, grasp_utils.py:59-60)
+ *   order                GNR_SELECT_ORDER_INDEX: np.argwhere order.  GNR_SELECT_ORDER_SCORE: descending
+ *                        score, equal scores by ascending linear voxel index -- sim_grasp's
+ *                        np.argsort(scores)[::-1][:top_k] (grasp_utils.py:105), except that numpy leaves the
+ *                        order of tied scores unspecified (argsort's default sort is not stable, and [::-1]
+ *                        would reverse a stable one): on ties this order is this library's, not numpy's.
+ *                        The ranking is over ALL survivors (non-maximum suppression keeps every voxel of a
+ *                        plateau: up to R^3), never over the first max_n in index order.  R <= 64
+ *                        (GNR_SELECT_SCORE_MAX_R: 2^18 voxels per scene, the limit of the render path's
+ *                        sample order); a larger R is refused.  GNR_SELECT_ORDER_INDEX keeps R <= 256.
+ *   top_k                rows stored per scene = min(count, top_k, max_n); 0: as many as max_n
+ *   count [B]            ALL survivors per scene in either order (may exceed top_k and max_n)            */
+#define GNR_SELECT_ORDER_INDEX 0
+#define GNR_SELECT_ORDER_SCORE 1
+#define GNR_SELECT_SCORE_MAX_R 64
+typedef struct GnrSelectParamsV2 {
+    GnrSelectParams select;
+    float tsdf_thres_outside;
+    int order;                                 /* GNR_SELECT_ORDER_*                                    */
+    int top_k;
+} GnrSelectParamsV2;
+size_t gnr_grasp_select_v2_workspace_bytes(int B, int R, int order);
+int gnr_grasp_select_v2_fwd(const float* tsdf, const float* qual, const float* rot, const float* width, int B, int R,
+                            const GnrSelectParamsV2* params, float* qual_out, int* count, int* index, float* score,
+                            float* quat, float* width_out, int max_n, void* workspace, size_t workspace_bytes, void* stream);
+/* gnr_surface_points_fwd: extract_surface_points_from_volume (draw_utils.py:355-377) for B volumes in one
+ * launch sequence: per scene the voxels with lo < vol < hi in np.nonzero order (ascending linear index).
+ *   vol [B,R,R,R], R <= 256
+ *   count [B]               voxels in range per scene (may exceed max_n: only the first max_n are stored)
+ *   index [B,max_n,3]       (i,j,k) int32
+ *   points [B,max_n,3]      float64, index * scale (open3d's PointCloud.scale about the origin)
+ *   colors [B,max_n,3]      float32: `color` for every point (GNR_SURFACE_COLOR_FIXED), or the value map of the
+ *                           reference's color=None branch (GNR_SURFACE_COLOR_VALUE, draw_utils.py:364-370) in
+ *                           float32, v = vol at the voxel:  m = (a + b) / 2;  r = v <= m ? v - a : -v + b;
+ *                           g = v <= m ? 0 : 1 - r;  b = v <= m ? 1 - r : 0
+ * Entries beyond min(count[b], max_n) are undefined.                                                   */
+#define GNR_SURFACE_COLOR_FIXED 0
+#define GNR_SURFACE_COLOR_VALUE 1
+typedef struct GnrSurfaceParams {
+    float lo, hi;                              /* (-0.2, 0.2) (grasp_utils.py:149)                      */
+    int color_mode;                            /* GNR_SURFACE_COLOR_*                                   */
+    float color[3];                            /* (0, 0, 1) (draw_utils.py:355)                         */
+    float bound_a, bound_b;                    /* (-1, 1) (draw_utils.py:355)                           */
+    double scale;                              /* 0.3 / 40 (draw_utils.py:355)                          */
+} GnrSurfaceParams;
+size_t gnr_surface_points_workspace_bytes(int B, int R);
+int gnr_surface_points_fwd(const float* vol, int B, int R, const GnrSurfaceParams* params, int* count, int* index,
+                           double* points, float* colors, int max_n, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- introspection / measurement -------------------------------------------------------*/
 /* name of the dominant kernel as it appears in rocprofv3 traces, and the calling thread's last error text (see GNR_ERR_*) */
 const char* gnr_dominant_kernel_name(void);

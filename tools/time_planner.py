@@ -5,7 +5,19 @@
   (b) PlannerSession.plan(): pinned upload of the uint8 frames, one captured-graph replay, one read-back.
 Both are timed with a host clock around the whole call (each ends in a device synchronisation), alternating a, b, a, b ...
 after a warm-up, and reported as p50 / p99 with (a)'s spread.  Writes profiles/planner_session.json.
-Usage: python tools/time_planner.py [--calls 60] [--warmup 5] [--out profiles/planner_session.json]"""
+Usage: python tools/time_planner.py [--calls 60] [--warmup 5] [--out profiles/planner_session.json]
+
+--real: the real-robot route instead (planner.plan_real; src/nr/utils/grasp_utils.py:119-151), three legs on one box, alternating:
+  (a) a PlannerSession WITHOUT the new outputs (the selection in index order, no cloud) -- to compare with the commit before the
+      route existed, copy this file into a built checkout of that commit, run it there with --real --only-a (leg (a) uses nothing
+      newer) and hand that run's JSON in with --parent-json: the requirement on (a) is that its p50 lies within the parent's own
+      p10..p90.  Within one process the calls agree to 0.03 ms while two processes of the SAME checkout differ by up to 0.1 ms, so
+      the comparison pools processes: --parent-json and --a-json (further --only-a runs of this checkout) take several files,
+      run alternately, and the percentiles are taken over the pooled calls;
+  (b) planner.real_session: grasp_utils.process's thresholds, the ranked top-10 and the surface cloud inside the graph;
+  (c) the host route to the same result: leg (a)'s replay, the four volumes read back, then scipy / numpy process + select +
+      argsort + extract_surface_points_from_volume as the reference runs them.
+Writes profiles/planner_session_real.json with p10 / p50 / p90 per leg."""
 import argparse
 import json
 import os
@@ -49,18 +61,131 @@ def pct(x, p):
     return float(np.percentile(np.asarray(x) * 1e3, p))
 
 
+def host_real_route(tsdf, qual, rot, width, top_k, rg):
+    """grasp_utils.process + select + sim_grasp's ranking + extract_surface_points_from_volume on the host, as the reference runs
+    them (scipy.ndimage; grasp_utils.py:40-105, draw_utils.py:355-377)."""
+    from scipy import ndimage
+    tsdf, qual, rot, width = tsdf.squeeze(), qual.squeeze(), rot.squeeze(), width.squeeze()
+    qual = ndimage.gaussian_filter(qual, sigma=1.0, mode='nearest')
+    valid = ndimage.binary_dilation(tsdf > 0.1, iterations=2, mask=np.logical_not(np.logical_and(-1 < tsdf, tsdf < -0.1)))
+    qual[valid == False] = 0.0                                               # noqa: E712
+    qual[np.logical_or(width < 0, width > 12)] = 0.0
+    q = qual.copy()
+    q[q < 0.90] = 0.0
+    q = np.where(q == ndimage.maximum_filter(q, size=4), q, 0.0)
+    idx = np.argwhere(q)
+    scores = q[idx[:, 0], idx[:, 1], idx[:, 2]]
+    p = np.argsort(scores)[::-1][:top_k]
+    quat = rot[:, idx[p, 0], idx[p, 1], idx[p, 2]].T
+    ind = np.transpose(((tsdf > rg[0]) & (tsdf < rg[1])).nonzero())
+    return idx[p], scores[p], quat, width[idx[p, 0], idx[p, 1], idx[p, 2]], ind, ind.astype(np.float64) * (0.3 / 40)
+
+
+def main_real(a, net):
+    """The --real legs (see the module docstring)."""
+    V = 6
+    rng = np.random.default_rng(0)
+    frames = rng.integers(0, 256, (V, IMG_WH[1], IMG_WH[0], 3), dtype=np.uint8)     # run_real's frames are the network's size
+    poses = ring_cameras(V)
+    K = np.float32([[357.048, 0, 255.8], [0, 357.048, 143.8], [0, 0, 1]])
+    Ks, top_k = np.repeat(K[None], V, 0), 10
+    hw = (IMG_WH[1], IMG_WH[0])
+    # run_real's box and depth range (grasp_utils.py:122-123) and grasp_utils.process's parameters without the third threshold
+    # (:45-47,60), spelled out: leg (a) must run on a checkout that has no plan_real
+    DR, BOX = (0.2, 0.8), ((-0.15, -0.15, 0.0), (0.15, 0.15, 0.3))
+    kw = dict(gaussian_filter_sigma=1.0, min_width=0, max_width=12, tsdf_thres_high=-0.1, tsdf_thres_low=-1)
+    plain = PlannerSession(net, V, hw, IMG_WH, voxel_size=0.3 / 40, **kw)
+    vol = plain.plan(frames, poses, Ks, DR, BOX, return_volumes=True)[0]['volumes'][0]
+    rg = (float(np.percentile(vol, 40)), float(np.percentile(vol, 60)))              # the synthetic volume has no zero crossing
+
+    def leg_a():
+        t0 = time.perf_counter()
+        g, _ = plain.plan(frames, poses, Ks, DR, BOX)
+        return time.perf_counter() - t0, g
+
+    def leg_b():
+        t0 = time.perf_counter()
+        out = planner.plan_real(net, frames, poses, K, order='score', top_k=top_k, surface_rg=rg, session=real)
+        return time.perf_counter() - t0, out
+
+    def leg_c():
+        t0 = time.perf_counter()
+        g, _ = plain.plan(frames, poses, Ks, DR, BOX, return_volumes=True)
+        out = host_real_route(*g['volumes'][:4], top_k, rg)
+        return time.perf_counter() - t0, out
+
+    def measure(legs):
+        for _ in range(a.warmup):
+            last = {k: f()[1] for k, f in legs.items()}
+        times = {k: [] for k in legs}
+        for _ in range(a.calls):                                             # alternating: the legs see the same machine state
+            for k, f in legs.items():
+                times[k].append(f()[0])
+        return times, last
+
+    # leg (a) on its own, before anything of the new route exists in the process: the procedure of a --only-a run, so that the two
+    # are comparable; then (b) and (c), alternating
+    times, last = measure({'a_session_without_new_outputs': leg_a})
+    have_v2 = not a.only_a
+    if have_v2:
+        real = planner.real_session(net, V, hw, IMG_WH, order='score', top_k=top_k, surface_rg=rg)
+        t2, l2 = measure({'b_session_ranked_top10_and_cloud': leg_b, 'c_host_route_numpy': leg_c})
+        times.update(t2), last.update(l2)
+    res = {'shape': {'views': V, 'frames_hw': hw, 'volume_resolution': 40, 'weights': 'synthetic'}, 'calls': a.calls, 'warmup': a.warmup,
+           'unit': 'ms, host clock around the whole call (ends in a device synchronisation)', 'library': os.path.basename(_lib_path()),
+           'device': torch.cuda.get_device_name(0)}
+    for k, t in times.items():
+        res[k] = {'p10': pct(t, 10), 'p50': pct(t, 50), 'p90': pct(t, 90)}
+    if a.only_a:
+        res['a_calls_ms'] = [round(t * 1e3, 4) for t in times['a_session_without_new_outputs']]
+    if have_v2:
+        b, c = last['b_session_ranked_top10_and_cloud'], last['c_host_route_numpy']
+        res['survivors'], res['cloud_points'] = int(real.selection['count'][0]), int(len(b[3]['index']))
+        res['b_equals_c'] = bool(np.array_equal(b[0]['index'], c[0]) and np.array_equal(b[1], c[1]) and np.array_equal(b[3]['index'], c[4])
+                                 and np.array_equal(b[3]['points'], c[5]))
+        res['b_p50_below_c_p50'] = bool(res['b_session_ranked_top10_and_cloud']['p50'] < res['c_host_route_numpy']['p50'])
+    if a.parent_json:
+        pool = lambda files: np.concatenate([json.load(open(f))['a_calls_ms'] for f in files]) / 1e3
+        par = pool(a.parent_json)
+        own = np.concatenate([pool(a.a_json)] if a.a_json else [] + [np.asarray(times['a_session_without_new_outputs'])])
+        p50s = lambda files: [json.load(open(f))['a_session_without_new_outputs']['p50'] for f in files]
+        res['a_parent_commit'] = {'processes': len(a.parent_json), 'p10': pct(par, 10), 'p50': pct(par, 50), 'p90': pct(par, 90),
+                                  'p50_per_process': p50s(a.parent_json)}
+        res['a_this_commit'] = {'processes': len(a.a_json) or 1, 'p10': pct(own, 10), 'p50': pct(own, 50), 'p90': pct(own, 90),
+                                'p50_per_process': p50s(a.a_json) if a.a_json else [res['a_session_without_new_outputs']['p50']]}
+        res['a_p50_within_parent_p10_p90'] = bool(pct(par, 10) <= pct(own, 50) <= pct(par, 90))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+def _lib_path():
+    from graspnerf_amd import _lib
+    return _lib.LIB_PATH
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--calls', type=int, default=60)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'planner_session.json'))
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--real', action='store_true', help='the real-robot route: profiles/planner_session_real.json')
+    ap.add_argument('--only-a', action='store_true', help='--real: leg (a) alone (a checkout from before the route has no other)')
+    ap.add_argument('--parent-json', nargs='+', default=None, help='--real: JSONs of --real --only-a runs in a checkout of the parent commit')
+    ap.add_argument('--a-json', nargs='*', default=None, help='--real: JSONs of --real --only-a runs of this checkout (pooled instead of this run\'s leg (a))')
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'planner_session_real.json' if a.real else 'planner_session.json')
     if not torch.cuda.is_available():
         sys.exit('time_planner.py measures on a ROCm GPU; there is nothing to time without one')
     shapes = {k: tuple(v.shape) for k, v in GraspNeRF(dict(CFG)).state_dict().items()}
     sd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth_state_dict(shapes).items()}
     sd['vgn_net.conv_qual.bias'] = sd['vgn_net.conv_qual.bias'] + 2.5
+    if a.real:
+        sd['vgn_net.conv_width.bias'] = sd['vgn_net.conv_width.bias'] + 5.0     # inside the 0..12 grasp_utils.process keeps
     net = planner.load_model(dict(CFG), sd)
+    if a.real:
+        return main_real(a, net)
     rng = np.random.default_rng(0)
     frames = rng.integers(0, 256, (V, *SRC_HW, 3), dtype=np.uint8)
     poses = ring_cameras(V)
