@@ -23,6 +23,7 @@ OPTIONS = {'fp32_chain': 0x001, 'feature_grad_fixed': 0x002, 'view1_one_wavefron
            'ray_order_morton': 0x010, 'poison_partials': 0x020, 'direct_scatter': 0x040, 'geo_dual_fp32': 0x080, 'test_lose_partner': 0x100, 'static_tiles': 0x200, 'split_launch': 0x400,
            'sample_order_natural': 0x800}
 GNR_STATUS_LOST_PARTNER = 16
+STATUS_SLOT_VOLUME_GRAD, STATUS_SLOT_VOLUME_GRAD_RAY = 7, 8     # status words of gnr_sample_volume_grad_fwd (include/gnr.h): its chain launch, its per-column kernel
 
 
 class GnrRays(C.Structure):
@@ -109,6 +110,13 @@ def lib():
     L.gnr_sample_volume_fwd.argtypes = [C.POINTER(GnrScene), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.gnr_sample_volume_fwd.restype = C.c_int
+    L.gnr_sample_volume_grad_workspace_bytes.argtypes = [C.POINTER(GnrScene), C.c_int]
+    L.gnr_sample_volume_grad_workspace_bytes.restype = C.c_size_t
+    L.gnr_sample_volume_grad_fwd.argtypes = [C.POINTER(GnrScene), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]
+    L.gnr_sample_volume_grad_fwd.restype = C.c_int
+    L.gnr_surface_gradient_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.gnr_surface_gradient_fwd.restype = C.c_int
     L.gnr_debug_volume_chain.argtypes = [C.POINTER(GnrScene), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]
     L.gnr_debug_volume_chain.restype = C.c_int
@@ -283,7 +291,8 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_debug_fill_lds', 'gnr_img_last_error', 'gnr_instnorm_act', 'gnr_instnorm_act_bwd', 'gnr_reflect_pad2d', 'gnr_reflect_pad2d_bwd', 'gnr_upsample2x_bilinear',
             'gnr_ingest_tables_bytes', 'gnr_ingest_tables_host', 'gnr_ingest_u8', 'gnr_ingest_last_error',
             'gnr_frame_metrics_workspace_bytes', 'gnr_frame_metrics',
-            'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd']
+            'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd',
+            'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd']
 
 
 def check(rc, what):

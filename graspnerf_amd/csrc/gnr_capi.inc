@@ -50,9 +50,10 @@ static Workspace carve(const GnrScene* s, size_t P, size_t rn, void* base) {
 // concern every launch on the prepared scene (0 = a feature, 2 = a weight beyond the fp16-pair range); the launch slots carry bit 1 of
 // their launch; the last words belong to the per-ray kernel's tail, the backward and the fixed-point scatter.
 enum StatusSlot { RS_SCENE = 0, RS_VOLUME = 1, RS_COARSE = 2, RS_FINE = 3, RS_VOLUME_TRAIN = 4, RS_COARSE_TRAIN = 5, RS_DEPTHS_TRAIN = 6,
+                  RS_VOLUME_GRAD = 7 /* gnr_sample_volume_grad_fwd: its chain launch */, RS_VOLUME_GRAD_RAY = 8 /* ... and its per-column kernel's matrix-core tail */,
                   RS_BACKWARD = 61 /* bit 4: GNR_STATUS_LOST_PARTNER */, RS_RAY_WATCH = 62 /* k_ray<true>'s matrix-core tail */,
                   RS_FEAT_FX = 63 /* bit 3: a clamped fixed-point contribution */, RS_WORDS = 64 };
-static_assert(RS_DEPTHS_TRAIN < RS_BACKWARD && RS_FEAT_FX < RS_WORDS, "status slots");
+static_assert(RS_VOLUME_GRAD_RAY < RS_BACKWARD && RS_FEAT_FX < RS_WORDS, "status slots");
 static inline bool opt(const GnrScene* s, unsigned bit) { return (s->options & bit) != 0; }
 
 static int check_scene(const GnrScene* s) {
@@ -166,8 +167,8 @@ static int launch_chain_one(const ChainArgs& a, hipStream_t st, const char* labe
 // and recompute the whole launch on the fp32-input MFMA when a feature or an activation left the fp16-pair range.
 // force_fp32 (GNR_OPT_FP32_CHAIN): the fp32-MFMA instantiation alone, the pair kernel is skipped
 template <int V, bool RENDER, bool SAVE = false, bool USEVIS = false>
-static int launch_chain_t(const ChainArgs& a, hipStream_t st, bool force_fp32) {
-    const char* label = RENDER ? (SAVE ? "k_chain.render.train" : "k_chain.render") : (SAVE ? "k_chain.volume.train" : "k_chain.volume");
+static int launch_chain_t(const ChainArgs& a, hipStream_t st, bool force_fp32, const char* label_as = nullptr, const char* twin_as = nullptr) {
+    const char* label = label_as ? label_as : RENDER ? (SAVE ? "k_chain.render.train" : "k_chain.render") : (SAVE ? "k_chain.volume.train" : "k_chain.volume");
     if constexpr (GNR_SPLIT16 != 0) {
         ChainArgs b = a;
         b.only_if_flagged = 0;
@@ -175,7 +176,7 @@ static int launch_chain_t(const ChainArgs& a, hipStream_t st, bool force_fp32) {
         if (int rc = launch_chain_one<V, RENDER, SAVE, USEVIS, true>(b, st, label)) return rc;
         if (!a.range_flag || !GNR_RANGE_GUARD) return GNR_OK;
         b.only_if_flagged = 1;
-        return launch_chain_one<V, RENDER, SAVE, USEVIS, false>(b, st, RENDER ? "k_chain.render.fp32_twin" : "k_chain.volume.fp32_twin");
+        return launch_chain_one<V, RENDER, SAVE, USEVIS, false>(b, st, twin_as ? twin_as : RENDER ? "k_chain.render.fp32_twin" : "k_chain.volume.fp32_twin");
     } else {
         ChainArgs b = a;
         b.only_if_flagged = 0;
@@ -184,17 +185,19 @@ static int launch_chain_t(const ChainArgs& a, hipStream_t st, bool force_fp32) {
 }
 
 // use_vis (GnrScene.use_vis: the levels' decoders carry the fourth branch, gnr_pack_vis_decoder / gnr_pack_vis_decoder_bwd)
+// label_as / twin_as: timing labels of an entry point that names its launches itself (null: the kernel's own)
 template <bool RENDER, bool SAVE = false>
-static int launch_chain(const GnrScene* s, const ChainArgs& a, hipStream_t st) {
+static int launch_chain(const GnrScene* s, const ChainArgs& a, hipStream_t st, const char* label_as = nullptr, const char* twin_as = nullptr) {
     if (s->use_vis != 0 && s->use_vis != 1) return fail(GNR_ERR_ARG, "GnrScene.use_vis must be 0 or 1");
     const bool f32 = opt(s, GNR_OPT_FP32_CHAIN);
     return with_views(s->V, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        return s->use_vis ? launch_chain_t<V, RENDER, SAVE, true>(a, st, f32) : launch_chain_t<V, RENDER, SAVE, false>(a, st, f32);
+        return s->use_vis ? launch_chain_t<V, RENDER, SAVE, true>(a, st, f32, label_as, twin_as) : launch_chain_t<V, RENDER, SAVE, false>(a, st, f32, label_as, twin_as);
     });
 }
 // The range guard and the tile hand-out of a chain launch: the scene's status words, the watch word of this launch (slot) and, unless
 // GNR_OPT_STATIC_TILES, the tile counters behind them (part: the half of a GNR_OPT_SPLIT_LAUNCH call, each with counters of its own)
+constexpr int TILE_CTR_VOLUME_GRAD = 2;                  // (parts 0 and 1: the halves of a GNR_OPT_SPLIT_LAUNCH call)
 static void wire_chain(ChainArgs& a, const GnrScene* s, const Workspace& w, int slot, int part = 0) {
     a.range_flag = w.range_flag;
     a.range_launch = w.range_flag ? w.range_flag + slot : nullptr;
@@ -362,7 +365,8 @@ static int pack_rays(int ray_floats, int slots, int lds_budget_bytes, int* ray_s
 // (RS_RAY_WATCH: the watch word of k_ray<true>'s matrix-core tail, bit 1.  Sticky until the next gnr_prepare: once tripped, every later
 // k_ray<true> launch on the prepared scene is followed by its fp32 recomputation.)
 // k_ray packs floor(256/slots) rays into a workgroup (slots = lanes per ray); two workgroups share a CU's LDS.
-template <bool RENDER>
+// VOLG: the volume output mode (gnr_sample_volume_grad_fwd)
+template <bool RENDER, bool VOLG = false>
 static int launch_ray(RayArgs& a, hipStream_t st) {
     const int fdn = (RENDER && a.fine_depth) ? a.fdn : 0;
     a.slots = a.dn > fdn ? a.dn : fdn;
@@ -375,11 +379,12 @@ static int launch_ray(RayArgs& a, hipStream_t st) {
     constexpr size_t MAX_LDS = 80 * 1024;
     const size_t lds_bytes = (size_t)rpb * a.ray_stride * sizeof(float);
     const dim3 grid((unsigned)((a.nrays + rpb - 1) / rpb));
-    if (int rc = launch<k_ray<RENDER>, MAX_LDS>(RENDER ? "k_ray.render" : "k_ray.volume", st, grid, dim3(256), lds_bytes, a)) return rc;
+    constexpr bool MM = GNR_RAY_GEO_MFMA != 0;
+    if (int rc = launch<k_ray<RENDER, MM, VOLG>, MAX_LDS>(VOLG ? "k_ray.render@volume_grad" : RENDER ? "k_ray.render" : "k_ray.volume", st, grid, dim3(256), lds_bytes, a)) return rc;
     if (RENDER && GNR_RAY_GEO_MFMA != 0 && a.range_word) {
         // the fp32 twin of the matrix-core tail: returns at once unless that launch flagged a non-finite value (range guard, k_ray)
         a.only_if = a.range_word;
-        return launch<k_ray<RENDER, false>, MAX_LDS>("k_ray.render.fp32_twin", st, grid, dim3(256), lds_bytes, a);
+        return launch<k_ray<RENDER, false, VOLG>, MAX_LDS>(VOLG ? "k_ray.render.fp32_twin@volume_grad" : "k_ray.render.fp32_twin", st, grid, dim3(256), lds_bytes, a);
     }
     return GNR_OK;
 }
@@ -508,6 +513,40 @@ extern "C" int gnr_sample_volume_fwd(const GnrScene* s, const float* bbox_min, i
     if (!bbox_min || !wc || !sdf_out || !ws) return fail(GNR_ERR_ARG, "gnr_sample_volume_fwd: null pointer");
     if (R < 2 || R > MAX_DN) return fail(GNR_ERR_SHAPE, "volume_res must be in 2..64");
     return volume_impl(s, bbox_min, R, wc, sdf_out, vmask_out, ws, ws_bytes, (hipStream_t)stream, true, true, true);
+}
+
+// The SDF gradient volume (ibrnet.py:485-513: the VJP with ones of a column's SDF values w.r.t. its query points, which the reference's volume
+// path computes and drops, aggregate_net.py:133-134): the volume's R^2 columns as rays of R samples through the render-record chain and
+// k_ray<true>'s volume output mode.  Workspace = the region of a render call of R^2 rays x R samples + the chain's colour outputs (not used).
+static size_t volume_grad_colors_bytes(const GnrScene* s, int R) { return al256((size_t)s->B * R * R * R * 3 * sizeof(float)); }
+extern "C" size_t gnr_sample_volume_grad_workspace_bytes(const GnrScene* s, int R) {
+    if (!s || R < 1 || R > MAX_DN) return 0;
+    return carve(s, (size_t)R * R * R, (size_t)R * R, nullptr).total + volume_grad_colors_bytes(s, R);
+}
+extern "C" int gnr_sample_volume_grad_fwd(const GnrScene* s, const float* bbox_min, int R, const float* wc, float* grad_out, float* sdf_out,
+                                          float* grad_error_out, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_scene(s)) return rc;
+    if (!bbox_min || !wc || !grad_out || !ws) return fail(GNR_ERR_ARG, "gnr_sample_volume_grad_fwd: null pointer");
+    if (R < 3 || R > MAX_DN) return fail(GNR_ERR_SHAPE, "gnr_sample_volume_grad_fwd: volume_res must be in 3..64 (the per-column kernel with the VJP takes 3 to 64 samples)");
+    const int P = R * R * R, rn = R * R;
+    if (int rc = check_points(s, (size_t)P)) return rc;
+    Workspace w = carve(s, (size_t)P, (size_t)rn, ws);
+    if (ws_bytes < w.total + volume_grad_colors_bytes(s, R)) return fail(GNR_ERR_WORKSPACE, "workspace too small (gnr_sample_volume_grad_workspace_bytes)");
+    float* colors = (float*)((char*)ws + w.total);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = launch<k_points_volume>("k_points_volume@volume_grad", st, dim3((s->B * P + 255) / 256), dim3(256), 0, bbox_min, w.desc, R, s->B)) return rc;
+    ChainArgs a{wc, w.feat64, s->imgs, w.viewp, w.desc, w.rec, colors, nullptr, nullptr, s->B, P, s->H, s->W, s->fh, s->fw, 0};
+    wire_chain(a, s, w, RS_VOLUME_GRAD, TILE_CTR_VOLUME_GRAD);
+    if (int rc = launch_chain<true>(s, a, st, "k_chain.render@volume_grad", "k_chain.render.fp32_twin@volume_grad")) return rc;
+    RayArgs r;
+    memset(&r, 0, sizeof(r));
+    r.wpk = wc; r.rec = w.rec; r.desc = w.desc; r.nrays = s->B * rn; r.dn = R; r.rays_per_scene = rn;
+    r.grad = grad_out; r.volume = sdf_out; r.gerr_part = grad_error_out ? w.gerr_part : nullptr;
+    r.range_word = w.range_flag ? w.range_flag + RS_VOLUME_GRAD_RAY : nullptr;
+    if (int rc = launch_ray<true, true>(r, st)) return rc;
+    if (grad_error_out)
+        return launch<k_gerr_reduce>("k_gerr_reduce@volume_grad", st, dim3(s->B, 1), dim3(256), 0, w.gerr_part, grad_error_out, rn, R, rn);
+    return GNR_OK;
 }
 
 // bring-up aid: per-point intermediates of k_chain on the volume points, point (column) order.

@@ -1753,7 +1753,7 @@ struct RayArgs {
     float* volume;           // [B][R*R][R] with z flipped back
     unsigned char* vmask_out;
     // render outputs (nullable)
-    float *sdf, *alpha, *hit, *pix, *rdepth, *gerr_part, *grad;
+    float *sdf, *alpha, *hit, *pix, *rdepth, *gerr_part, *grad;     // (VOLG: grad [B][R][R][R][3] and the optional `volume` in voxel order, gerr_part [nrays])
     unsigned char* rmask;
     int view_num, point_num;
     // inverse-CDF resampling (coarse pass only; nullable)
@@ -1851,8 +1851,12 @@ DEV void wave_sync() {
 }
 // MM (RENDER only): the VJP's dense tail on the f16 matrix cores (the product); false: as fp32 FMAs -- the instantiation launched right
 // behind every MM launch, which returns at once unless that launch's range watch tripped (RayArgs::only_if) and otherwise recomputes it
-template <bool RENDER, bool MM = (GNR_RAY_GEO_MFMA != 0)>
+// VOLG (RENDER only): the volume output mode of gnr_sample_volume_grad_fwd -- the "rays" are the volume's columns (k_points_volume's
+// descriptors); behind the VJP the kernel writes the gradient (and the SDF) of sample i into voxel (x, y, R-1-i) and the column's sum of
+// (|grad| - 1)^2, and returns: no depths, no alpha, no compositing, no resampler
+template <bool RENDER, bool MM = (GNR_RAY_GEO_MFMA != 0), bool VOLG = false>
 __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayArgs a) {
+    static_assert(RENDER || !VOLG, "the volume output mode follows the VJP of the render instantiation");
     if constexpr (RENDER && !MM) {
         if (a.only_if && (__builtin_nontemporal_load(a.only_if) & 2u) == 0u) return;
     }
@@ -2337,6 +2341,25 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
             grad[c] = de[c] + c1 * de[3 + c] - s1 * de[6 + c] + 2.f * c2 * de[9 + c] - 2.f * s2 * de[12 + c]
                       + 4.f * c4 * de[15 + c] - 4.f * s4 * de[18 + c];
         }
+        if constexpr (VOLG) {
+            // renderer.py:197-198: column (x, y), sample i is voxel z = R-1-i; the components stay in the world frame.  The column's
+            // eikonal partial is summed in sample order by one lane (the attention scratch is dead once every lane is past the tail)
+            const float gn = sqrtf(grad[0] * grad[0] + grad[1] * grad[1] + grad[2] * grad[2]) - 1.f;
+            __syncthreads();
+            if (act) {
+                sc[i] = gn * gn;
+                const size_t o_idx = (size_t)ray * dn + (dn - 1 - i);
+                a.grad[o_idx * 3] = grad[0]; a.grad[o_idx * 3 + 1] = grad[1]; a.grad[o_idx * 3 + 2] = grad[2];
+                if (a.volume) a.volume[o_idx] = sdf;
+            }
+            __syncthreads();
+            if (rvalid && slot == 0 && a.gerr_part) {
+                float s = 0.f;
+                for (int j = 0; j < dn; ++j) s += sc[j];
+                a.gerr_part[ray] = s;
+            }
+            return;
+        } else {
         // ================= NeuS alpha (aggregate_net.py:105-121), compositing (render_ops.py:72-80)
         const float z = a.depth[opt];
         const float znext = a.depth[opt + ((i + 1 < dn) ? 1 : 0)];
@@ -2441,6 +2464,7 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
                 a.fine_depth[(size_t)oray * fdn + rank] = fd;
                 if (a.fine_inds) a.fine_inds[(size_t)oray * fdn + fs] = inds;
             }
+        }
         }
     }
 }

@@ -281,6 +281,19 @@ __global__ __launch_bounds__(1024) void k_surf_write(const float* __restrict__ v
     colors[o] = r; colors[o + 1] = g; colors[o + 2] = bl;
 }
 
+// rows of a gradient volume at the voxels of a surface cloud: out[b][r] = grad[b][index[b][r]] for r < min(count[b], max_n)
+__global__ __launch_bounds__(256) void k_surf_gradient(const float* __restrict__ grad, const int* __restrict__ index, const int* __restrict__ count,
+                                                       int R, int max_n, float* __restrict__ out) {
+    const int b = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(count[b], max_n);
+    if (r >= n) return;
+    const size_t o = ((size_t)b * max_n + r) * 3;
+    // (an index outside the volume is not gnr_surface_points_fwd's: clamped, never read out of bounds)
+    const int i = min(max(index[o], 0), R - 1), j = min(max(index[o + 1], 0), R - 1), k = min(max(index[o + 2], 0), R - 1);
+    const float* g = grad + (((size_t)b * R + i) * R + j) * (size_t)R * 3 + (size_t)k * 3;
+    out[o] = g[0]; out[o + 1] = g[1]; out[o + 2] = g[2];
+}
+
 }  // namespace gnr_post
 
 using namespace gnr_post;
@@ -394,4 +407,11 @@ extern "C" int gnr_surface_points_fwd(const float* vol, int B, int R, const GnrS
     if (int rc = launch<k_surf_count>(nullptr, st, grid, block, 0, vol, n, p->lo, p->hi, chunk)) return rc;
     if (int rc = launch<k_surf_scan>(nullptr, st, dim3(B), block, 0, chunk, nc, count)) return rc;
     return launch<k_surf_write>(nullptr, st, grid, block, 0, vol, R, n, p->lo, p->hi, col, p->scale, (const int*)chunk, max_n, index, points, colors);
+}
+
+extern "C" int gnr_surface_gradient_fwd(const float* grad, const int* index, const int* count, int B, int R, int max_points, float* out, void* stream) {
+    if (!grad || !index || !count || !out) return fail(GNR_ERR_ARG, "gnr_surface_gradient_fwd: null pointer");
+    if (B < 1 || B > 65535 || R < 1 || R > 256 || max_points < 0) return fail(GNR_ERR_SHAPE, "gnr_surface_gradient_fwd: bad B / R / max_points (1 <= R <= 256, max_points >= 0)");
+    if (max_points == 0) return GNR_OK;
+    return launch<k_surf_gradient>(nullptr, (hipStream_t)stream, dim3((max_points + 255) / 256, B), dim3(256), 0, grad, index, count, R, max_points, out);
 }

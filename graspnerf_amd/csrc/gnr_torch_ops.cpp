@@ -3,6 +3,7 @@
 // outputs / workspaces as tensors on the inputs' device, takes the current HIP stream and calls the same entry points the ctypes
 // route (graspnerf_amd/_lib.py, hotpath.py) calls -- same kernels, same bits.  No arithmetic lives here.
 //   sample_volume        NeuralRayRenderer.sample_volume (renderer.py:164-199)                         -> volume [B,1,R,R,R]
+//   sample_volume_gradient  the SDF gradient volume of the same call (gnr_sample_volume_grad_fwd)      -> grad [B,R,R,R,3]
 //   render_rays          NeuralRayRenderer.render (renderer.py:201-220 + 140-162), both levels         -> 2 x 10 tensors
 //   sample_volume_train  the same forward with the saved states of its backward                         -> (volume, ws, tws)
 //   sample_volume_bwd    its backward twins (csrc/gnr_bwd.inc)                                          -> (d canonical, d ray_feats, d img_feats)
@@ -78,6 +79,21 @@ Tensor sample_volume(const Tensor& imgs, const Tensor& img_feats, const Tensor& 
     Tensor vol = at::empty({sc.s.B, 1, res, res, res}, sc.imgs.options());
     ok(gnr_sample_volume_fwd(&sc.s, fp(bb), (int)res, fp(w), vol.data_ptr<float>(), nullptr, ws.data_ptr(), wsb, st), "gnr_sample_volume_fwd");
     return vol;
+}
+
+Tensor sample_volume_gradient(const Tensor& imgs, const Tensor& img_feats, const Tensor& ray_feats, const Tensor& poses, const Tensor& Ks,
+                              const Tensor& depth_range, const Tensor& bbox_min, const Tensor& weights, int64_t res, bool use_vis) {
+    c10::DeviceGuard guard(imgs.device());
+    Scene sc = make_scene(imgs, img_feats, ray_feats, poses, Ks, depth_range, use_vis);
+    const Tensor bb = arg(bbox_min, "bbox_min [B,3]", sc.imgs, (int64_t)sc.s.B * 3), w = arg(weights, "weights (packed level blob)", sc.imgs, gnr_packed_weights_floats());
+    TORCH_CHECK(res >= 3 && res <= 64, "graspnerf::sample_volume_gradient: res must be in 3..64");
+    const size_t wsb = gnr_sample_volume_grad_workspace_bytes(&sc.s, (int)res);
+    Tensor ws = bytes(wsb, sc.imgs);
+    void* st = cur_stream(sc.imgs);
+    ok(gnr_prepare(&sc.s, ws.data_ptr(), wsb, st), "gnr_prepare");
+    Tensor grad = at::empty({sc.s.B, res, res, res, 3}, sc.imgs.options());
+    ok(gnr_sample_volume_grad_fwd(&sc.s, fp(bb), (int)res, fp(w), grad.data_ptr<float>(), nullptr, nullptr, ws.data_ptr(), wsb, st), "gnr_sample_volume_grad_fwd");
+    return grad;
 }
 
 // outputs of one level, in this order (an undefined pixel_colors_gt when the query images are not given comes back as an empty tensor)
@@ -171,6 +187,8 @@ std::tuple<Tensor, Tensor, Tensor> sample_volume_bwd(const Tensor& imgs, const T
 TORCH_LIBRARY(graspnerf, m) {
     m.def("sample_volume(Tensor imgs, Tensor img_feats, Tensor ray_feats, Tensor poses, Tensor Ks, Tensor depth_range, Tensor bbox_min, "
           "Tensor weights, int res, bool use_vis=False) -> Tensor");
+    m.def("sample_volume_gradient(Tensor imgs, Tensor img_feats, Tensor ray_feats, Tensor poses, Tensor Ks, Tensor depth_range, Tensor bbox_min, "
+          "Tensor weights, int res, bool use_vis=False) -> Tensor");
     m.def("render_rays(Tensor imgs, Tensor img_feats, Tensor ray_feats, Tensor poses, Tensor Ks, Tensor depth_range, Tensor coords, "
           "Tensor que_pose, Tensor que_K, Tensor que_depth_range, Tensor? que_imgs, Tensor weights_coarse, Tensor weights_fine, int dn, "
           "int fdn, int ray_mask_view_num=2, int ray_mask_point_num=8, int ray_batch_num=0, bool fine_depth_use_all=False, "
@@ -183,6 +201,7 @@ TORCH_LIBRARY(graspnerf, m) {
 
 TORCH_LIBRARY_IMPL(graspnerf, CUDA, m) {          // the ROCm build of PyTorch dispatches HIP tensors under the CUDA key
     m.impl("sample_volume", &sample_volume);
+    m.impl("sample_volume_gradient", &sample_volume_gradient);
     m.impl("render_rays", &render_rays);
     m.impl("sample_volume_train", &sample_volume_train);
     m.impl("sample_volume_bwd", &sample_volume_bwd);
@@ -195,6 +214,7 @@ TORCH_LIBRARY_IMPL(graspnerf, CUDA, m) {          // the ROCm build of PyTorch d
 // operator sees is not a differentiable function of anything the dispatcher knows.)
 TORCH_LIBRARY_IMPL(graspnerf, Autograd, m) {
     m.impl("sample_volume", torch::autograd::autogradNotImplementedFallback());
+    m.impl("sample_volume_gradient", torch::autograd::autogradNotImplementedFallback());
     m.impl("render_rays", torch::autograd::autogradNotImplementedFallback());
     m.impl("sample_volume_train", torch::autograd::autogradNotImplementedFallback());
     m.impl("sample_volume_bwd", torch::autograd::autogradNotImplementedFallback());

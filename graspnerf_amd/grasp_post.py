@@ -98,11 +98,13 @@ class SurfaceExtractor:
         self.device = torch.device(device)
         self._ws = None
 
-    def __call__(self, vol, rg=(-0.2, 0.2), bound=(-1, 1), color=(0, 0, 1), scale=0.3 / 40, max_points=None):
+    def __call__(self, vol, rg=(-0.2, 0.2), bound=(-1, 1), color=(0, 0, 1), scale=0.3 / 40, max_points=None, gradient=None):
         """vol [B,R,R,R] (or [B,1,R,R,R], or one [R,R,R])  ->  dict of device tensors: count [B] voxels with rg[0] < vol < rg[1];
         index [B,max,3] int32 in np.nonzero order; points [B,max,3] float64 = index * scale; colors [B,max,3] float32 (`color`, or
         the value map over `bound` when color is None); entries beyond count[b] are undefined.  max_points=None: R^3, nothing is
-        truncated.  The result carries `scale` and `value_map` for surface_from_extraction."""
+        truncated.  The result carries `scale` and `value_map` for surface_from_extraction.
+        gradient [B,R,R,R,3] (HotPath.sample_volume_gradient): adds `gradient` [B,max,3] float32, its rows at the cloud's voxels
+        gathered on the device (gnr_surface_gradient_fwd); rows beyond count[b] are zero."""
         d = self.device
         vol = torch.as_tensor(vol, dtype=torch.float32, device=d).contiguous()
         R = vol.shape[-1]
@@ -124,32 +126,63 @@ class SurfaceExtractor:
                                            out['points'].data_ptr(), out['colors'].data_ptr(), M, self._ws.data_ptr(),
                                            self._ws.numel(), C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
         _lib.check(rc, 'gnr_surface_points_fwd')
+        if gradient is not None:
+            g = torch.as_tensor(gradient, dtype=torch.float32, device=d).contiguous()
+            if tuple(g.shape) != (B, R, R, R, 3):
+                raise ValueError(f'gradient must be [{B},{R},{R},{R},3], got {tuple(g.shape)}')
+            out['gradient'] = torch.zeros(B, M, 3, dtype=torch.float32, device=d)
+            rc = self.L.gnr_surface_gradient_fwd(g.data_ptr(), out['index'].data_ptr(), out['count'].data_ptr(), B, R, M,
+                                                 out['gradient'].data_ptr(), C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+            _lib.check(rc, 'gnr_surface_gradient_fwd')
         out['scale'], out['value_map'] = float(scale), color is None
         return out
 
 
 def surface_from_extraction(res, b=0):
     """Scene b of a SurfaceExtractor result -> numpy dict: `index` [N,3] int64, `points` [N,3] float64 (metres), `colors` [N,3]
-    float64 (what open3d's Vector3dVector holds).  Raises when the buffers held fewer rows than the scene has voxels in range."""
+    float64 (what open3d's Vector3dVector holds).  Raises when the buffers held fewer rows than the scene has voxels in range.
+    A result with `gradient` adds `gradient` [N,3] float32 (the device's rows) and `normals` [N,3] float64 = g / |g| computed here on
+    the host (the convention of `points` = index * scale); a zero row stays zero."""
     n = int(res['count'][b].item())
     if n > res['index'].shape[1]:
         raise _lib.GnrError(f'{n} surface voxels but the buffers hold {res["index"].shape[1]}: raise max_points')
-    return {'index': res['index'][b, :n].cpu().numpy().astype(np.int64), 'points': res['points'][b, :n].cpu().numpy(),
-            'colors': res['colors'][b, :n].cpu().numpy().astype(np.float64)}
+    out = {'index': res['index'][b, :n].cpu().numpy().astype(np.int64), 'points': res['points'][b, :n].cpu().numpy(),
+           'colors': res['colors'][b, :n].cpu().numpy().astype(np.float64)}
+    if 'gradient' in res:
+        out['gradient'] = res['gradient'][b, :n].cpu().numpy()
+        out['normals'] = unit_normals(out['gradient'])
+    return out
 
 
-def write_ply(path, points, colors):
-    """A point cloud as an ASCII PLY 1.0 file (draw_utils.py:382 writes open3d's): x y z as float64, colours in [0, 1] as uchar."""
+def unit_normals(gradient):
+    """[N,3] gradient rows -> float64 g / |g|; a zero row stays zero."""
+    g = np.asarray(gradient, np.float64).reshape(-1, 3)
+    n = np.linalg.norm(g, axis=1, keepdims=True)
+    return np.divide(g, n, out=np.zeros_like(g), where=n > 0)
+
+
+def write_ply(path, points, colors, normals=None):
+    """A point cloud as an ASCII PLY 1.0 file (draw_utils.py:382 writes open3d's): x y z as float64, colours in [0, 1] as uchar;
+    normals [N,3]: nx ny nz as float64 between them (open3d's property order).  Without normals the file is what it was before."""
     points, colors = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(colors, np.float64).reshape(-1, 3)
     if len(points) != len(colors):
         raise ValueError(f'{len(points)} points but {len(colors)} colours')
+    if normals is not None:
+        normals = np.asarray(normals, np.float64).reshape(-1, 3)
+        if len(normals) != len(points):
+            raise ValueError(f'{len(points)} points but {len(normals)} normals')
     rgb = np.clip(np.floor(colors * 255.0 + 0.5), 0, 255).astype(np.uint8)
     with open(path, 'w') as f:
         f.write('ply\nformat ascii 1.0\ncomment graspnerf_amd surface cloud\n'
                 f'element vertex {len(points)}\nproperty double x\nproperty double y\nproperty double z\n'
+                + ('property double nx\nproperty double ny\nproperty double nz\n' if normals is not None else '') +
                 'property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
-        for (x, y, z), (r, g, b) in zip(points.tolist(), rgb.tolist()):
-            f.write(f'{x!r} {y!r} {z!r} {r} {g} {b}\n')
+        if normals is None:
+            for (x, y, z), (r, g, b) in zip(points.tolist(), rgb.tolist()):
+                f.write(f'{x!r} {y!r} {z!r} {r} {g} {b}\n')
+        else:
+            for (x, y, z), (nx, ny, nz), (r, g, b) in zip(points.tolist(), normals.tolist(), rgb.tolist()):
+                f.write(f'{x!r} {y!r} {z!r} {nx!r} {ny!r} {nz!r} {r} {g} {b}\n')
 
 
 def grasps_from_selection(sel, b=0, voxel_size=0.3 / 40, seed=None):

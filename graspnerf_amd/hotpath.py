@@ -79,8 +79,9 @@ class HotPath:
                      t['poses'].data_ptr(), t['Ks'].data_ptr(), t['depth_range'].data_ptr(), 1 if self.use_vis else 0, self.options)
         return s, t
 
-    def _workspace(self, scene, res, rn, dn):
-        need = max(self.L.gnr_workspace_bytes(self._sc(scene), res, rn, dn), 0 if self._ws is None else self._ws.numel())
+    def _workspace(self, scene, res, rn, dn, grad_res=0):
+        need = max(self.L.gnr_workspace_bytes(self._sc(scene), res, rn, dn), 0 if self._ws is None else self._ws.numel(),
+                   self.L.gnr_sample_volume_grad_workspace_bytes(self._sc(scene), grad_res) if grad_res else 0)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
@@ -102,12 +103,13 @@ class HotPath:
             raise _lib.GnrError('HIP backward after the workspaces were re-prepared: run forward and backward of a scene '
                                 '(or of one batch of scenes) before the next training forward')
 
-    def prepare(self, ref, res=40, rn=0, dn=0):
-        """Repack feature maps + per-view projection blocks (timed part of a forward)."""
+    def prepare(self, ref, res=40, rn=0, dn=0, grad_res=0):
+        """Repack feature maps + per-view projection blocks (timed part of a forward).  grad_res: the workspace also serves
+        sample_volume_gradient at that resolution (gnr_sample_volume_grad_workspace_bytes)."""
         self.generation += 1
         self._pass_seq = 0                               # render passes of this forward, counted for their persistent training workspaces
         scene, keep = self._scene(ref)
-        ws = self._workspace(scene, res, rn, dn)
+        ws = self._workspace(scene, res, rn, dn, grad_res)
         _lib.check(self.L.gnr_prepare(self._sc(scene), ws.data_ptr(), ws.numel(), self._stream()), 'gnr_prepare')
         self._prepared = (scene, keep, ws)
         return self._prepared
@@ -149,6 +151,23 @@ class HotPath:
                                                 vol.data_ptr(), vmask.data_ptr() if want_mask else None,
                                                 ws.data_ptr(), ws.numel(), self._stream()), 'gnr_sample_volume_fwd')
         return (vol, vmask) if want_mask else vol
+
+    def sample_volume_gradient(self, ref, res=40, want_sdf=False, want_error=False, prepared=None):
+        """The SDF gradient volume (gnr_sample_volume_grad_fwd, include/gnr.h): grad [B,R,R,R,3] = the reference's summed VJP of a
+        column's SDF values w.r.t. its query points, in the volume's voxel order, world frame (3 <= res <= 64).
+        -> grad, or (grad[, sdf [B,R,R,R]][, error [B] = mean((|grad|-1)^2)]) with want_sdf / want_error.
+        `prepared`: a prepare(..., grad_res=res) of the same scenes."""
+        scene, keep, ws = prepared or self.prepare(ref, res, grad_res=res)
+        B = scene.B
+        bbox_min = _f32(ref['bbox3d'], self.device)[:, 0].contiguous()
+        grad = torch.empty(B, res, res, res, 3, dtype=torch.float32, device=self.device)
+        sdf = torch.empty(B, res, res, res, dtype=torch.float32, device=self.device) if want_sdf else None
+        err = torch.empty(B, dtype=torch.float32, device=self.device) if want_error else None
+        _lib.check(self.L.gnr_sample_volume_grad_fwd(self._sc(scene), bbox_min.data_ptr(), res, self.wc.data_ptr(), grad.data_ptr(),
+                                                     sdf.data_ptr() if want_sdf else None, err.data_ptr() if want_error else None,
+                                                     ws.data_ptr(), ws.numel(), self._stream()), 'gnr_sample_volume_grad_fwd')
+        out = (grad,) + ((sdf,) if want_sdf else ()) + ((err,) if want_error else ())
+        return out if len(out) > 1 else grad
 
     def debug_volume_chain(self, ref, res=40, prepared=None):
         scene, keep, ws = prepared or self.prepare(ref, res)

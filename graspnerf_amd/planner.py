@@ -107,14 +107,18 @@ REAL_BBOX3D = ((-0.15, -0.15, 0.0), (0.15, 0.15, 0.3))                          
 REAL_DEPTH_RANGE, REAL_QUE_ID, REAL_VOXEL_SIZE = (0.2, 0.8), 3, 0.3 / 40                                  # grasp_utils.py:122,137,146
 
 
-def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, **kw):
-    """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud."""
+def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, **kw):
+    """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud
+    (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True))."""
+    if normals:
+        kw = dict(kw, surface_normals=True)
     return PlannerSession(net, n_views, src_hw, img_wh, max_grasps=max_grasps, voxel_size=REAL_VOXEL_SIZE,
                           surface=dict(rg=tuple(surface_rg)), order='score' if order == 'score' else 'index', top_k=top_k,
                           **GRASP_UTILS_PROCESS, **kw)
 
 
-def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None):
+def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None,
+              normals=False):
     """`run_real` (grasp_utils.py:119-151) without its file output: one plan from camera frames.
     images: V >= 4 uint8 frames [h,w,3] (list or array); extrinsics: V world->camera [3|4,4]; intrinsic [3,3], the same for every view.
     run_real's workspace box, depth range (0.2, 0.8) and query view 3; grasp_utils.process's thresholds (GRASP_UTILS_PROCESS),
@@ -122,7 +126,10 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     from the global state);  order='score': ranked by descending score, best first -- with top_k=10 sim_grasp's list
     (grasp_utils.py:105).  session: a real_session of this net for these frames -- the whole plan is then one replay of its graph.
     -> (grasps dict: pos (metres), quat, width, score, index;  scores;  tsdf_vol [R,R,R];
-        cloud dict: points [N,3] float64, colors [N,3], index [N,3] of the voxels with surface_rg[0] < tsdf < surface_rg[1];  seconds)."""
+        cloud dict: points [N,3] float64, colors [N,3], index [N,3] of the voxels with surface_rg[0] < tsdf < surface_rg[1];  seconds).
+    normals=True: the cloud also carries `gradient` [N,3] float32 -- the rows of the SDF gradient volume at its voxels
+    (NeuralRayRenderer.sample_volume_gradient: the reference's summed VJP, world frame) -- and `normals` [N,3] float64 = g / |g|;
+    a session must have been built with real_session(normals=True).  The grasps do not depend on the switch."""
     if order not in ('permuted', 'score'):
         raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
     ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
@@ -138,8 +145,8 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         sp, su = session.selector_params, session.surface_params
         want = dict(GRASP_UTILS_PROCESS, order=sel_order, top_k=top_k)
         if session.net is not net or su is None or tuple(su['rg']) != tuple(surface_rg) or any(sp[k] != v for k, v in want.items()) \
-                or session.voxel_size != REAL_VOXEL_SIZE:
-            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k or surface range '
+                or session.voxel_size != REAL_VOXEL_SIZE or bool(normals) != bool(getattr(session, 'surface_normals', False)):
+            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range or normals '
                              '(build it with planner.real_session)')
         g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
         tsdf_vol, cloud = g.pop('volumes')[0], session.cloud
@@ -160,7 +167,11 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         finally:
             torch.backends.cudnn.deterministic = was
         tsdf_vol = g.pop('volumes')[0]
-        res = SurfaceExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), rg=surface_rg)                 # grasp_utils.py:149
+        grad = None
+        if normals:                                               # the volume's cameras again: the forward keeps no feature maps
+            grad = _volume_gradient(net, imgs, ext, Ks, dev)
+        res = SurfaceExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), rg=surface_rg,                # grasp_utils.py:149
+                                    **({'gradient': grad} if normals else {}))
         cloud = surface_from_extraction(res, 0)
     tsdf_vol = np.asarray(tsdf_vol).reshape(tsdf_vol.shape[-3:])
     n = len(g['score'])
@@ -170,6 +181,25 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         p = np.random.permutation(n)
         g = {k: v[p] for k, v in g.items()}
     return g, g['score'], tsdf_vol, cloud, dt
+
+
+def _volume_gradient(net, imgs, ext, Ks, dev):
+    """The SDF gradient volume [1,R,R,R,3] of run_real's scene from the resized float images (the backbones run again: the eager
+    forward of plan() hands back its outputs, not its feature maps; a session computes both in one graph)."""
+    nr = net.nr_net
+    t = lambda a: torch.as_tensor(np.array(a, np.float32), device=dev)
+    V = imgs.shape[0]
+    ref = {'imgs': t(imgs), 'poses': t(ext[:, :3, :]), 'Ks': t(Ks), 'depth_range': t(np.broadcast_to(np.float32(REAL_DEPTH_RANGE), (V, 2))),
+           'bbox3d': t(REAL_BBOX3D)}
+    was = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        with torch.no_grad():
+            ref['img_feats'] = nr.image_encoder(ref['imgs'])
+            ref['ray_feats'] = nr.vis_encoder(nr.init_net(ref, dict(ref), False), ref['img_feats'])
+            return nr.sample_volume_gradient(ref)
+    finally:
+        torch.backends.cudnn.deterministic = was
 
 
 # ---- the planner's file I/O (SURVEY.md §8f N4; ref: src/nr/main.py:87-209) -----------------------------------------------

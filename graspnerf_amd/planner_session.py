@@ -13,13 +13,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import GraspSelector, SurfaceExtractor, grasps_from_selection
+from .grasp_post import GraspSelector, SurfaceExtractor, grasps_from_selection, unit_normals
 from .ingest import DeviceIngest
 
 _SELECTOR_DEFAULTS = {k: p.default for k, p in inspect.signature(GraspSelector.__call__).parameters.items()
                       if p.default is not inspect.Parameter.empty}
 _SURFACE_DEFAULTS = {k: p.default for k, p in inspect.signature(SurfaceExtractor.__call__).parameters.items()
-                     if p.default is not inspect.Parameter.empty}
+                     if p.default is not inspect.Parameter.empty and k != 'gradient'}      # (the gradient volume is the session's: surface_normals)
 _SEG = 64                                                    # floats: every camera block starts on a 256-byte boundary
 
 
@@ -37,12 +37,17 @@ class PlannerSession:
     point cloud of the volume to the graph; self.cloud then holds the last plan's cloud (index, points, colors as numpy).  The
     read-back of the cloud is sized by its row count: the counts come with the selection, then ONE copy of the stored index rows
     (and of the colours in value-map mode; a fixed colour is known on the host); the float64 points stay on the device (the graph's
-    output `surface`) and are recomputed on the host as index * scale, which is the same float64 product.  A session built
+    output `surface`) and are recomputed on the host as index * scale, which is the same float64 product.
+    surface_normals=True (needs `surface`): the SDF gradient volume (NeuralRayRenderer.sample_volume_gradient) and the gather of its
+    rows at the cloud's voxels are captured in the graph too; the gradient rows are read back in the same sized step as the index
+    rows, and self.cloud gains `gradient` [N,3] float32 and `normals` [N,3] float64 (g / |g| on the host).  A session built
     without any of these records the graph it always recorded."""
 
     def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
-                 surface=None, **selector_params):
+                 surface=None, surface_normals=False, **selector_params):
         cfg = net.nr_net.cfg
+        if surface_normals and surface is None:
+            raise ValueError('surface_normals=True needs the surface cloud: pass surface=dict(...) ({} for its defaults)')
         if cfg.get('warn_low_valid_ratio', False):
             raise ValueError("graph capture cannot read the valid ratio back on every call: unset cfg['warn_low_valid_ratio']")
         if not cfg.get('sample_volume', False):
@@ -86,6 +91,7 @@ class PlannerSession:
         # the selection, packed for one read-back: count | index [M,3] | score [M] | quat [M,4] | width [M], 4-byte words
         # (+ the cloud's row count, when the session extracts one)
         self.surface_params = None if surface is None else {**_SURFACE_DEFAULTS, **surface}
+        self.surface_normals = bool(surface_normals)
         words = 1 + 9 * M + (0 if surface is None else 1)
         self._d_out = torch.zeros(words, dtype=torch.int32, device=dev)
         self._h_out = torch.zeros(words, dtype=torch.int32, pin_memory=True)
@@ -96,6 +102,8 @@ class PlannerSession:
             self._surface_rows = R ** 3 if self.surface_params['max_points'] is None else int(self.surface_params['max_points'])
             self._h_surf_index = torch.zeros(self._surface_rows, 3, dtype=torch.int32, pin_memory=True)
             self._h_surf_colors = torch.zeros(self._surface_rows, 3, dtype=torch.float32, pin_memory=True)
+            if self.surface_normals:
+                self._h_surf_grad = torch.zeros(self._surface_rows, 3, dtype=torch.float32, pin_memory=True)
         self.captures = 0
         self._set_example_cameras()
         self._capture()
@@ -117,7 +125,7 @@ class PlannerSession:
         ref = {'imgs': imgs, **self._d}
         ref['img_feats'] = nr.image_encoder(imgs)
         ref['ray_feats'] = nr.vis_encoder(nr.init_net(ref, None, False), ref['img_feats'])
-        prep = nr._prepare(ref, 0)
+        prep = nr._prepare(ref, 0, volume_gradient=True) if self.surface_normals else nr._prepare(ref, 0)
         vol = nr.sample_volume(ref, _prep=prep)
         q, r, w = self.net.grasp_head(vol)
         sel = self.selector(vol, q, r, w, **self.selector_params)
@@ -128,7 +136,8 @@ class PlannerSession:
             o[a:b].copy_(sel[k].reshape(-1).view(torch.int32))
         out = {'volume': vol, 'qual': q, 'rot': r, 'width': w, 'sel_qual': sel['qual']}
         if self.surface_params is not None:
-            out['surface'] = self.surface(vol, **self.surface_params)
+            grad = nr.sample_volume_gradient(ref, _prep=prep) if self.surface_normals else None
+            out['surface'] = self.surface(vol, **self.surface_params, **({'gradient': grad} if self.surface_normals else {}))
             o[1 + 9 * M:2 + 9 * M].copy_(out['surface']['count'])
         return out
 
@@ -194,11 +203,17 @@ class PlannerSession:
         self._h_surf_index[:count].copy_(surf['index'][0, :count], non_blocking=True)
         if sp['color'] is None:
             self._h_surf_colors[:count].copy_(surf['colors'][0, :count], non_blocking=True)
+        if self.surface_normals:
+            self._h_surf_grad[:count].copy_(surf['gradient'][0, :count], non_blocking=True)
         st.synchronize()
         index = self._h_surf_index[:count].numpy().astype(np.int64)
         colors = self._h_surf_colors[:count].numpy().astype(np.float64) if sp['color'] is None else \
             np.array([sp['color']], np.float64).repeat(count, axis=0)
-        return {'count': count, 'index': index, 'points': index.astype(np.float64) * float(sp['scale']), 'colors': colors}
+        cloud = {'count': count, 'index': index, 'points': index.astype(np.float64) * float(sp['scale']), 'colors': colors}
+        if self.surface_normals:
+            cloud['gradient'] = self._h_surf_grad[:count].numpy().copy()
+            cloud['normals'] = unit_normals(cloud['gradient'])
+        return cloud
 
     def plan(self, frames_u8, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497)),
              seed=None, return_volumes=False):

@@ -458,11 +458,14 @@ class NeuralRayRenderer(nn.Module):
         out['bbox3d'] = (bb if torch.is_tensor(bb) else torch.as_tensor(np.asarray(bb), dtype=torch.float32))[None]
         return out
 
-    def _prepare(self, ref_imgs_info, rn=0):
-        """Feature-map repack + view blocks once per forward; shared by volume / render / depth-mean."""
+    def _prepare(self, ref_imgs_info, rn=0, volume_gradient=None):
+        """Feature-map repack + view blocks once per forward; shared by volume / render / depth-mean (and, with cfg volume_gradient
+        or volume_gradient=True, by the gradient volume: its pass needs a larger workspace)."""
         c = self.cfg
         bref = self._batched_ref(ref_imgs_info)
-        return bref, self.hot().prepare(bref, c.get('volume_resolution', 40), rn, self._dn_max())
+        R = c.get('volume_resolution', 40)
+        grad = c.get('volume_gradient', False) if volume_gradient is None else volume_gradient
+        return bref, self.hot().prepare(bref, R, rn, self._dn_max(), grad_res=R if grad else 0)
 
     @staticmethod
     def _batched_que(que):
@@ -627,6 +630,14 @@ class NeuralRayRenderer(nn.Module):
             print("!! too low ratio", valid_ratio)
         return vol
 
+    def sample_volume_gradient(self, ref_imgs_info, _prep=None, want_error=False):
+        """The gradient volume of sample_volume's SDF, [1,R,R,R,3] in the volume's voxel order, world frame: what agg_impl returns
+        next to the SDF (ibrnet.py:485-513, the VJP with ones of a column's SDF values w.r.t. its query points) and the reference's
+        volume path drops (aggregate_net.py:133-134).  Inference only: there is no backward for it.
+        want_error: -> (gradient, mean((|gradient|-1)^2) [1])."""
+        bref, prep = _prep or self._prepare(ref_imgs_info, volume_gradient=True)
+        return self.hot().sample_volume_gradient(bref, self.cfg['volume_resolution'], want_error=want_error, prepared=prep)
+
     def _out_dict(self, o, suffix, level_net):
         keys = ['sdf_values', 'alpha_values', 'colors_nr', 'hit_prob_nr', 'pixel_colors_nr']
         if self.cfg['use_ray_mask']:                                        # renderer.py:129-132
@@ -729,6 +740,8 @@ class NeuralRayRenderer(nn.Module):
             out = self.render(que, ref, is_train, _prep=prep)
         if self.cfg.get('sample_volume', False):
             out['volume'] = self.sample_volume(ref, _prep=prep, is_train=is_train)
+            if self.cfg.get('volume_gradient', False) and not is_train:      # eval only (no backward); `volume` itself never comes from this pass
+                out['volume_gradient'], out['volume_gradient_error'] = self.sample_volume_gradient(ref, _prep=prep, want_error=True)
         if (self.cfg.get('use_depth_loss', False) and 'true_depth' in ref) or (not is_train):
             out.update(self.predict_mean_for_depth_loss(ref, _prep=prep, is_train=is_train))
         return out

@@ -9,7 +9,7 @@ import torch
 from . import _lib
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'libgnr_torch.so')
-OPS = ('sample_volume', 'render_rays', 'sample_volume_train', 'sample_volume_bwd')
+OPS = ('sample_volume', 'sample_volume_gradient', 'render_rays', 'sample_volume_train', 'sample_volume_bwd')
 RENDER_KEYS = ('depth', 'sdf_values', 'alpha_values', 'colors_nr', 'hit_prob_nr', 'pixel_colors_nr', 'pixel_colors_gt', 'render_depth',
                'ray_mask', 'sdf_gradient_error')           # order of the ten tensors render_rays returns per level (coarse, then fine)
 _loaded = False

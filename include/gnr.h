@@ -224,6 +224,28 @@ int gnr_sample_volume_fwd(const GnrScene* scene, const float* bbox_min /*[B,3]*/
                           unsigned char* view_mask_out, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* The SDF gradient volume: what the reference's network returns next to the SDF on every sample_volume call and its volume path drops
+ * (ibrnet.py:485-513, aggregate_net.py:133-134).  The volume is evaluated as res^2 columns (x, y) of res samples, top -> down
+ * (renderer.py:167-179), query direction (0,0,1);  grad_out[b,x,y,z,:] = sum over the samples i of voxel (x,y,z)'s column of
+ * d sdf_i / d p_(x,y,z) -- the VJP with ones through embedder, geometry_fc, positional table, the column's attention, LayerNorm,
+ * out_geometry_fc, clip and fill, with the cross-view statistics held constant: the SUMMED VJP of the reference, NOT the per-point
+ * Jacobian diagonal.  Components are in the world frame.  The same arithmetic as GnrRenderOut.sdf_gradient of a render pass.
+ *   volume_res     3..64 (the per-column kernel with the VJP takes 3 to 64 samples)
+ *   grad_out       [B,res,res,res,3]
+ *   sdf_out        optional [B,res,res,res]: the SDF of this pass (through the render-record chain; measured bitwise equal to the volume
+ *                  entry point's on the 3-view 16^3 test scene, which is not a promise: callers take the volume from that entry point)
+ *   grad_error_out optional [B]: mean((|grad| - 1)^2) over the scene's res^3 voxels (the eikonal term, aggregate_net.py:139)
+ *   workspace      the prepared scene's, of at least the sizing function below (it exceeds the workspace of the other forwards for the same res)
+ * Runs on a prepared scene like the other forwards, before or after them: neither changes the other's bits.  It re-uses the per-call part
+ * of the workspace, so it must NOT run between a training forward and its backward.  Range guard: status slot 7 (the chain launch) and
+ * 8 (the per-column kernel's matrix-core tail), tile counters of its own; a tripped watch makes the fp32 twins behind the launches
+ * recompute them, as for the other slots.  Capture-safe: the caller's stream only, no allocation, no host wait. */
+size_t gnr_sample_volume_grad_workspace_bytes(const GnrScene* scene, int volume_res);
+int gnr_sample_volume_grad_fwd(const GnrScene* scene, const float* bbox_min /*[B,3]*/, int volume_res,
+                               const float* packed_coarse /*device*/, float* grad_out /*[B,res,res,res,3]*/,
+                               float* sdf_out /*optional [B,res,res,res]*/, float* grad_error_out /*optional [B]*/,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* render_by_depth (renderer.py:110-138): one pass over given sample depths [B,rn,dn]
  * (ascending along each ray).  `level_weights` = packed coarse or fine blob (device). */
 int gnr_render_by_depth_fwd(const GnrScene* scene, const GnrRays* rays, const float* depth, int dn,
@@ -618,6 +640,12 @@ typedef struct GnrSurfaceParams {
 size_t gnr_surface_points_workspace_bytes(int B, int R);
 int gnr_surface_points_fwd(const float* vol, int B, int R, const GnrSurfaceParams* params, int* count, int* index,
                            double* points, float* colors, int max_n, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Rows of a gradient volume (the entry point above the render passes) at the voxels of a surface cloud:
+ *   out[b,r,:] = grad[b, index[b,r]]  for r < min(count[b], max_points);  grad [B,R,R,R,3], index / count as the surface-point call
+ *   wrote them for the same max_points, out [B,max_points,3] float32.  Rows beyond that are left untouched.  1 <= R <= 256. */
+int gnr_surface_gradient_fwd(const float* grad, const int* index, const int* count, int B, int R, int max_points,
+                             float* out /*[B,max_points,3]*/, void* stream);
 
 /* ---- introspection / measurement -------------------------------------------------------*/
 /* name of the dominant kernel as it appears in rocprofv3 traces, and the calling thread's last error text (see GNR_ERR_*) */

@@ -17,7 +17,10 @@ Usage: python tools/time_planner.py [--calls 60] [--warmup 5] [--out profiles/pl
   (b) planner.real_session: grasp_utils.process's thresholds, the ranked top-10 and the surface cloud inside the graph;
   (c) the host route to the same result: leg (a)'s replay, the four volumes read back, then scipy / numpy process + select +
       argsort + extract_surface_points_from_volume as the reference runs them.
-Writes profiles/planner_session_real.json with p10 / p50 / p90 per leg."""
+Writes profiles/planner_session_real.json with p10 / p50 / p90 per leg.
+--real --normals: a fourth leg in the same alternation,
+  (d) planner.real_session(normals=True): leg (b) plus the SDF gradient volume and the gather of its rows at the cloud's voxels in
+      the graph, the rows read back with the index rows, unit normals on the host."""
 import argparse
 import json
 import os
@@ -114,6 +117,11 @@ def main_real(a, net):
         out = host_real_route(*g['volumes'][:4], top_k, rg)
         return time.perf_counter() - t0, out
 
+    def leg_d():
+        t0 = time.perf_counter()
+        out = planner.plan_real(net, frames, poses, K, order='score', top_k=top_k, surface_rg=rg, session=real_n, normals=True)
+        return time.perf_counter() - t0, out
+
     def measure(legs):
         for _ in range(a.warmup):
             last = {k: f()[1] for k, f in legs.items()}
@@ -129,7 +137,11 @@ def main_real(a, net):
     have_v2 = not a.only_a
     if have_v2:
         real = planner.real_session(net, V, hw, IMG_WH, order='score', top_k=top_k, surface_rg=rg)
-        t2, l2 = measure({'b_session_ranked_top10_and_cloud': leg_b, 'c_host_route_numpy': leg_c})
+        legs = {'b_session_ranked_top10_and_cloud': leg_b, 'c_host_route_numpy': leg_c}
+        if a.normals:
+            real_n = planner.real_session(net, V, hw, IMG_WH, order='score', top_k=top_k, surface_rg=rg, normals=True)
+            legs['d_session_with_surface_normals'] = leg_d
+        t2, l2 = measure(legs)
         times.update(t2), last.update(l2)
     res = {'shape': {'views': V, 'frames_hw': hw, 'volume_resolution': 40, 'weights': 'synthetic'}, 'calls': a.calls, 'warmup': a.warmup,
            'unit': 'ms, host clock around the whole call (ends in a device synchronisation)', 'library': os.path.basename(_lib_path()),
@@ -143,6 +155,10 @@ def main_real(a, net):
         res['survivors'], res['cloud_points'] = int(real.selection['count'][0]), int(len(b[3]['index']))
         res['b_equals_c'] = bool(np.array_equal(b[0]['index'], c[0]) and np.array_equal(b[1], c[1]) and np.array_equal(b[3]['index'], c[4])
                                  and np.array_equal(b[3]['points'], c[5]))
+        if a.normals:
+            d = last['d_session_with_surface_normals']
+            res['d_same_grasps_and_cloud_as_b'] = bool(np.array_equal(d[0]['index'], b[0]['index']) and np.array_equal(d[3]['index'], b[3]['index']))
+            res['d_minus_b_p50'] = res['d_session_with_surface_normals']['p50'] - res['b_session_ranked_top10_and_cloud']['p50']
         res['b_p50_below_c_p50'] = bool(res['b_session_ranked_top10_and_cloud']['p50'] < res['c_host_route_numpy']['p50'])
     if a.parent_json:
         pool = lambda files: np.concatenate([json.load(open(f))['a_calls_ms'] for f in files]) / 1e3
@@ -171,6 +187,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--out', default=None)
     ap.add_argument('--real', action='store_true', help='the real-robot route: profiles/planner_session_real.json')
+    ap.add_argument('--normals', action='store_true', help='--real: leg (d), the session with the surface normals')
     ap.add_argument('--only-a', action='store_true', help='--real: leg (a) alone (a checkout from before the route has no other)')
     ap.add_argument('--parent-json', nargs='+', default=None, help='--real: JSONs of --real --only-a runs in a checkout of the parent commit')
     ap.add_argument('--a-json', nargs='*', default=None, help='--real: JSONs of --real --only-a runs of this checkout (pooled instead of this run\'s leg (a))')
