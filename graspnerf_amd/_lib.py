@@ -65,6 +65,15 @@ class GnrSurfaceParams(C.Structure):
                 ('bound_a', C.c_float), ('bound_b', C.c_float), ('scale', C.c_double)]
 
 
+GNR_DEPTH_F32, GNR_DEPTH_U16 = 0, 1
+GNR_TSDF_GRID, GNR_TSDF_SDF_LABEL = 0, 1
+
+
+class GnrTsdfParams(C.Structure):
+    _fields_ = [('B', C.c_int), ('V', C.c_int), ('h', C.c_int), ('w', C.c_int), ('R', C.c_int), ('depth_dtype', C.c_int),
+                ('voxel_size', C.c_double), ('sdf_trunc', C.c_double), ('depth_scale', C.c_double), ('depth_trunc', C.c_double)]
+
+
 class GnrError(RuntimeError):
     pass
 
@@ -236,6 +245,12 @@ def lib():
     L.gnr_surface_points_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(GnrSurfaceParams)] + [C.c_void_p] * 4 + \
                                         [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.gnr_surface_points_fwd.restype = C.c_int
+    L.gnr_tsdf_reset.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gnr_tsdf_reset.restype = C.c_int
+    L.gnr_tsdf_integrate.argtypes = [C.POINTER(GnrTsdfParams)] + [C.c_void_p] * 7
+    L.gnr_tsdf_integrate.restype = C.c_int
+    L.gnr_tsdf_grid.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.gnr_tsdf_grid.restype = C.c_int
     L.gnr_time_chain_kernel.argtypes = [C.POINTER(GnrScene), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                         c_float_p, C.c_void_p]
     L.gnr_time_chain_kernel.restype = C.c_int
@@ -292,7 +307,8 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_ingest_tables_bytes', 'gnr_ingest_tables_host', 'gnr_ingest_u8', 'gnr_ingest_last_error',
             'gnr_frame_metrics_workspace_bytes', 'gnr_frame_metrics',
             'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd',
-            'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd']
+            'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd',
+            'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid']
 
 
 def check(rc, what):

@@ -15,6 +15,7 @@ from .renderer import GraspNeRF
 from .grasp_post import GRASP_UTILS_PROCESS, GraspSelector, SurfaceExtractor, grasps_from_selection, surface_from_extraction
 from .ingest import axis_tables
 from .planner_session import PlannerSession
+from .tsdf import create_tsdf
 
 
 def load_model(cfg, checkpoint=None, device='cuda:0', depth_coords_rng='device'):
@@ -200,6 +201,27 @@ def _volume_gradient(net, imgs, ext, Ks, dev):
             return nr.sample_volume_gradient(ref)
     finally:
         torch.backends.cudnn.deterministic = was
+
+
+# ---- the depth route (ref: src/gd/detection.py:13-40, the VGN baseline) ------------------------------------------------------
+def plan_depth(head, depth_imgs, intrinsic, extrinsics, size=0.3, resolution=40, seed=None):
+    """`VGN.__call__` (detection.py:13-40) from the depth images of `acquire_tsdf` (gd/simulation.py:341-367): TSDF fusion
+    (tsdf.create_tsdf) -> grid -> grasp head -> process + select with detection.py's defaults (GraspSelector's own) -> seeded
+    permutation, voxel -> metric, all on the device.  head: a grasp_head.GraspHead;  depth_imgs [V,h,w] float32 metres (or uint16);
+    intrinsic: 3x3 or an object with fx, fy, cx, cy;  extrinsics: V world->camera transforms, 7-lists [qx,qy,qz,qw,tx,ty,tz] or
+    matrices;  resolution: 40, the head's output grid (detection.py:44).
+    -> (grasps dict: pos (metres), quat, width, score, index;  scores;  seconds)."""
+    dev = head.device
+    with torch.no_grad():
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        grid = create_tsdf(size, resolution, depth_imgs, intrinsic, extrinsics, device=dev).get_grid()
+        q, r, wd = head(grid)
+        sel = GraspSelector(dev)(grid, q, r, wd)
+        torch.cuda.synchronize(dev)
+        dt = time.time() - t0
+    grasps = grasps_from_selection(sel, 0, size / resolution, seed)
+    return grasps, grasps['score'], dt
 
 
 # ---- the planner's file I/O (SURVEY.md §8f N4; ref: src/nr/main.py:87-209) -----------------------------------------------

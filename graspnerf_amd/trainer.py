@@ -50,8 +50,12 @@ def exp_decay_lr(step, lr_init=1e-4, decay_step=100000, decay_rate=0.5, lr_min=1
 
 
 class Trainer:
-    def __init__(self, net, lr_cfg=None, batched=True, log_every=1, flat_exchange='auto', reproducible_feature_grads=False):
-        """reproducible_feature_grads: the path's feature-map gradients (the gradients it hands the 2D backbones) through 64-bit
+    def __init__(self, net, lr_cfg=None, batched=True, log_every=1, flat_exchange='auto', reproducible_feature_grads=False,
+                 sdf_gt_from_depth=False):
+        """sdf_gt_from_depth: a scene of step() or validate() whose `ref_imgs_info` has no `sdf_gt` gets it from its depth images
+        before the losses (tsdf.sdf_gt_from_depth: true_depth fused over the workspace cube on the device at the net's
+        volume_resolution).  Off, such a scene raises a KeyError as it always did; a scene that has the key is never touched.
+        reproducible_feature_grads: the path's feature-map gradients (the gradients it hands the 2D backbones) through 64-bit
         fixed-point adds instead of float sums in arrival order (include/gnr.h GNR_OPT_FEATURE_GRAD_FIXED): with it every gradient the HIP
         path produces is the same bits from run to run, as on the reference's CPU path.  A per-call option of THIS net's calls (set either
         way here: another Trainer in the process is not affected, and a later Trainer with False is not left in the fixed-point mode).
@@ -66,6 +70,7 @@ class Trainer:
         of the latest step stay on the device until last_log() asks for them."""
         self.net = net
         self.batched = batched
+        self.sdf_gt_from_depth = bool(sdf_gt_from_depth)
         nr = getattr(net, 'nr_net', None)
         if hasattr(nr, 'set_hot_option'):
             nr.set_hot_option('feature_grad_fixed', bool(reproducible_feature_grads))
@@ -94,6 +99,20 @@ class Trainer:
                 if isinstance(getattr(nr, n, None), torch.nn.Module):
                     ms.append(getattr(nr, n))
         return ms
+
+    def _with_sdf_gt(self, scenes):
+        """sdf_gt_from_depth: the scenes, those without `sdf_gt` as shallow copies that carry the fused label."""
+        if not self.sdf_gt_from_depth:
+            return scenes
+        from .tsdf import sdf_gt_from_depth
+        R = int(self.net.cfg['volume_resolution'])
+        out = []
+        for d in scenes:
+            if 'sdf_gt' not in d['ref_imgs_info']:
+                with torch.no_grad():
+                    d = dict(d, ref_imgs_info=dict(d['ref_imgs_info'], sdf_gt=sdf_gt_from_depth(d['ref_imgs_info'], R)))
+            out.append(d)
+        return out
 
     def _note_backward_status(self):
         """After a backward: OR the lost-partner bit of the HIP path's status words into the step's flag -- on the device, nothing waits."""
@@ -159,7 +178,7 @@ class Trainer:
         for g in self.optimizer.param_groups:
             g['lr'] = lr
         self.optimizer.zero_grad(set_to_none=True)
-        datas = [dict(d, step=self.step_id) for d in scenes]
+        datas = [dict(d, step=self.step_id) for d in self._with_sdf_gt(scenes)]
         outs = st = None
         if self.batched and hasattr(self.net, 'forward_scenes') and len(datas) > 1:
             # all scenes of the rank in one forward (None: cannot batch): first choice scene-major stacks and ONE set of
@@ -229,7 +248,7 @@ class Trainer:
         """scenes: the global sequence of held-out `data` dicts whose query view is the full frame (planner.full_frame_coords) with
         `que_imgs_info['true_depth']`; every rank passes the same sequence and evaluates its shard.  The net runs in eval() under
         no_grad and comes back in the mode it had.  -> (results, key_metric_value), validation.Validator."""
-        return self.validator(self.net, scenes, self.step_id if step is None else step)
+        return self.validator(self.net, self._with_sdf_gt(scenes), self.step_id if step is None else step)
 
     def save_checkpoint(self, path, best_para):
         """The reference's file (trainer.py:211-218), which its plain torch.optim.Adam and planner.load_model read: the optimiser

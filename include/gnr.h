@@ -647,6 +647,37 @@ int gnr_surface_points_fwd(const float* vol, int B, int R, const GnrSurfaceParam
 int gnr_surface_gradient_fwd(const float* grad, const int* index, const int* count, int B, int R, int max_points,
                              float* out /*[B,max_points,3]*/, void* stream);
 
+/* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
+ * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
+ * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
+ *   p = origin + (idx + 0.5) * voxel_size;  pc = R_wc p + t  (poses: world->camera, OpenCV axes);  skip the view if pc.z <= 0
+ *   u_f = pc.x * fx / pc.z + cx + 0.5, v_f likewise;  skip unless 1e-4 <= u_f < w - 1e-4 and 1e-4 <= v_f < h - 1e-4;  u = (int)u_f, v = (int)v_f
+ *   d = depth[v,u] / depth_scale;  d >= depth_trunc -> d = 0;  skip if d <= 0
+ *   sdf = (d - pc.z) * sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1)
+ *   if sdf > -sdf_trunc:  t = min(1, sdf / sdf_trunc);  tsdf = (tsdf * weight + t) / (weight + 1);  weight += 1
+ * Everything up to t is float64 (single correctly rounded operations in this order, never contracted), t is rounded once to
+ * float32, the update is float32: V views in one call and V calls of one view give the same bits, and the result equals the
+ * float64 statement of tests/tsdf_reference.py bit for bit.
+ *   depth [B,V,h,w] float32 (GNR_DEPTH_F32) or uint16 (GNR_DEPTH_U16);  poses [B,V,3,4];  Ks [B,V,3,3];  origin [B,3]
+ *   1 <= B <= 65535, V >= 1, h, w >= 1, 2 <= R <= 256;  voxel_size, sdf_trunc, depth_scale, depth_trunc > 0
+ * gnr_tsdf_grid: GNR_TSDF_GRID       out = (tsdf + 1) / 2 where weight != 0 and -0.98 <= tsdf < 0.98, else 0   (get_grid)
+ *                GNR_TSDF_SDF_LABEL  out = grid * 2 - 1: the trainer's sdf_gt, -1 = no label   (dataset/database.py:207-209)
+ * All three are asynchronous on `stream`, allocate nothing and do not synchronise (they can be captured in a graph); a refused
+ * call (GNR_ERR_ARG / GNR_ERR_SHAPE) has launched nothing.                                                               */
+#define GNR_DEPTH_F32 0
+#define GNR_DEPTH_U16 1
+#define GNR_TSDF_GRID 0
+#define GNR_TSDF_SDF_LABEL 1
+typedef struct GnrTsdfParams {
+    int B, V, h, w, R, depth_dtype;            /* GNR_DEPTH_*                                           */
+    double voxel_size, sdf_trunc, depth_scale, depth_trunc;
+} GnrTsdfParams;
+int gnr_tsdf_reset(int B, int R, float* tsdf, float* weight, void* stream);
+int gnr_tsdf_integrate(const GnrTsdfParams* params, const void* depth /*[B,V,h,w]*/, const float* poses /*[B,V,3,4]*/,
+                       const float* Ks /*[B,V,3,3]*/, const float* origin /*[B,3]*/, float* tsdf, float* weight /*[B,R,R,R] in/out*/,
+                       void* stream);
+int gnr_tsdf_grid(int B, int R, const float* tsdf, const float* weight, int mode /*GNR_TSDF_GRID | GNR_TSDF_SDF_LABEL*/, float* out /*[B,R,R,R]*/, void* stream);
+
 /* ---- introspection / measurement -------------------------------------------------------*/
 /* name of the dominant kernel as it appears in rocprofv3 traces, and the calling thread's last error text (see GNR_ERR_*) */
 const char* gnr_dominant_kernel_name(void);
