@@ -42,8 +42,14 @@ class HotPath:
             raise _lib.GnrError('use_vis must be the same for both levels (the reference evaluates the fine level with the coarse '
                                 "decoder's compute_prob, renderer.py:70-72)")
         self.options = HotPath.default_options   # per-call options of this HotPath's calls (set_option; include/gnr.h GNR_OPT_*)
-        self._ws = None
-        self._keep = []
+        self.generation = 0                      # prepare() calls so far (check_generation)
+        self._pass_seq = 0                       # render passes of the current forward, counted for their persistent training workspaces
+        self._ws = None                          # the prepared workspace (_workspace)
+        self._prepared = None                    # (scene, keep, ws) of the last prepare()
+        self._train_ctx = None                   # (scene, keep, ws, res, tws) of the last sample_volume_train()
+        self.wb = {'coarse': None, 'fine': None}  # packed weights of the backward twins (set_bwd_weights)
+        self.can_dev = None                      # level -> canonical blob on the device (set by the owner of the weights)
+        self._bufs = {}                          # grow-only training workspaces and backward scratch (_buf)
 
     # ---- plumbing ------------------------------------------------------------------------
     def _stream(self):
@@ -62,7 +68,9 @@ class HotPath:
     def set_option(self, name, on=True):
         """Switch one of the per-call options (_lib.OPTIONS: fp32_chain, feature_grad_fixed, view1_one_wavefront, view2_one_wavefront,
         ray_order_morton, poison_partials, direct_scatter, geo_dual_fp32, test_lose_partner, static_tiles, split_launch,
-        sample_order_natural) for the calls of THIS HotPath; -> previous."""
+        sample_order_natural) for the calls of THIS HotPath; -> previous.  It holds for the life of this object: a renderer that owns
+        it changes a bit only in its own set_hot_option(), and the HotPath it builds after `.to()` / load_state_dict starts again from
+        default_options plus what that set_hot_option() was asked."""
         bit = _lib.OPTIONS[name]
         prev = bool(self.options & bit)
         self.options = (self.options | bit) if on else (self.options & ~bit)
@@ -86,15 +94,35 @@ class HotPath:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _scratch(self, name, nbytes):
-        """Persistent per-purpose scratch of the backward twins (the partial sums of their deterministic parameter-gradient
-        reductions; stream-ordered, so one buffer per purpose serves every call)."""
-        bufs = self.__dict__.setdefault('_scratch_bufs', {})
-        if name not in bufs or bufs[name].numel() < nbytes:
-            bufs[name] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
-        return bufs[name]
+    def _buf(self, key, nbytes):
+        """The grow-only device buffer `key` with at least nbytes: the volume's training workspace, the per-pass training
+        workspaces and the scratch of the backward twins (the partial sums of their deterministic parameter-gradient reductions;
+        stream-ordered, so one buffer per purpose serves every call).  Re-used while it is large enough; a smaller one is dropped
+        before its replacement is allocated."""
+        b = self._bufs.get(key)
+        if b is None or b.numel() < nbytes:
+            self._bufs[key] = b = None
+            b = self._bufs[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
+        return b
 
-    generation = 0
+    def _w(self, level):
+        w = self.wf if level == 'fine' else self.wc
+        if w is None:
+            raise _lib.GnrError(f"this HotPath has no packed weights of the '{level}' level")
+        return w
+
+    def _bbox_min(self, ref):
+        return _f32(ref['bbox3d'], self.device)[:, 0].contiguous()
+
+    def _dcan(self, with_vis=False):
+        """A zeroed gradient blob of one level in state-dict order (with_vis: followed by the vis_decoder's entries under use_vis)."""
+        n = self.L.gnr_canonical_weights_floats() + (self.L.gnr_canonical_vis_floats() if with_vis and self.use_vis else 0)
+        return torch.zeros(n, dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def _bool_mask(o):
+        o['ray_mask'] = o['ray_mask'].view(torch.bool)       # the kernels write 0 / 1 bytes: a view, not a conversion kernel
+        return o
 
     def check_generation(self, gen):
         """The backward twins recompute from the prepared feature maps and the saved states in this object's workspaces:
@@ -107,7 +135,7 @@ class HotPath:
         """Repack feature maps + per-view projection blocks (timed part of a forward).  grad_res: the workspace also serves
         sample_volume_gradient at that resolution (gnr_sample_volume_grad_workspace_bytes)."""
         self.generation += 1
-        self._pass_seq = 0                               # render passes of this forward, counted for their persistent training workspaces
+        self._pass_seq = 0
         scene, keep = self._scene(ref)
         ws = self._workspace(scene, res, rn, dn, grad_res)
         _lib.check(self.L.gnr_prepare(self._sc(scene), ws.data_ptr(), ws.numel(), self._stream()), 'gnr_prepare')
@@ -144,7 +172,7 @@ class HotPath:
     def sample_volume(self, ref, res=40, want_mask=False, prepared=None):
         scene, keep, ws = prepared or self.prepare(ref, res)
         B = scene.B
-        bbox_min = _f32(ref['bbox3d'], self.device)[:, 0].contiguous()
+        bbox_min = self._bbox_min(ref)
         vol = torch.empty(B, 1, res, res, res, dtype=torch.float32, device=self.device)
         vmask = torch.empty(B, res, res, res, dtype=torch.uint8, device=self.device) if want_mask else None
         _lib.check(self.L.gnr_sample_volume_fwd(self._sc(scene), bbox_min.data_ptr(), res, self.wc.data_ptr(),
@@ -159,7 +187,7 @@ class HotPath:
         `prepared`: a prepare(..., grad_res=res) of the same scenes."""
         scene, keep, ws = prepared or self.prepare(ref, res, grad_res=res)
         B = scene.B
-        bbox_min = _f32(ref['bbox3d'], self.device)[:, 0].contiguous()
+        bbox_min = self._bbox_min(ref)
         grad = torch.empty(B, res, res, res, 3, dtype=torch.float32, device=self.device)
         sdf = torch.empty(B, res, res, res, dtype=torch.float32, device=self.device) if want_sdf else None
         err = torch.empty(B, dtype=torch.float32, device=self.device) if want_error else None
@@ -171,7 +199,7 @@ class HotPath:
 
     def debug_volume_chain(self, ref, res=40, prepared=None):
         scene, keep, ws = prepared or self.prepare(ref, res)
-        bbox_min = _f32(ref['bbox3d'], self.device)[:, 0].contiguous()
+        bbox_min = self._bbox_min(ref)
         dbg = torch.zeros(scene.B, res ** 3, 32, dtype=torch.float32, device=self.device)
         _lib.check(self.L.gnr_debug_volume_chain(self._sc(scene), bbox_min.data_ptr(), res, self.wc.data_ptr(),
                                                  dbg.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
@@ -220,35 +248,26 @@ class HotPath:
         (renderer.py:153-162): the coarse pass only, fine dict = None."""
         cfg = cfg or {}
         dn, fdn = cfg.get('depth_sample_num', 40), cfg.get('fine_depth_sample_num', 40)
-        if not cfg.get('use_hierarchical_sampling', True):
-            if fine_depth_in is not None or debug:
-                raise _lib.GnrError('render(): fine depths / resampling indices need use_hierarchical_sampling')
-            B, rn = que['coords'].shape[:2]
-            scene, keep, ws = prepared or self.prepare(ref, 1, rn, dn)
-            rays, rkeep = self._rays(que, dn, fdn, cfg, scene.H, scene.W)
-            co_s, co = self._alloc_out(B, rn, dn, 'imgs' in que, False, rays.ray_batch_num)
-            _lib.check(self.L.gnr_render_rays_fwd(self._sc(scene), C.byref(rays), self.wc.data_ptr(), None, C.byref(co_s), None, None, None,
-                                                  ws.data_ptr(), ws.numel(), self._stream()), 'gnr_render_rays_fwd')
-            co['ray_mask'] = co['ray_mask'].view(torch.bool)
-            return co, None
-        if self.wf is None:
-            raise _lib.GnrError('render() needs the fine-level weights')
+        hier = bool(cfg.get('use_hierarchical_sampling', True))
+        if not hier and (fine_depth_in is not None or debug):
+            raise _lib.GnrError('render(): fine depths / resampling indices need use_hierarchical_sampling')
+        wf = self._w('fine') if hier else None
         B, rn = que['coords'].shape[:2]
         # fine_depth_use_all (renderer.py:145-146): the fine pass renders the coarse and the resampled depths together
-        fine_dn = dn + fdn if cfg.get('fine_depth_use_all', False) else fdn
+        fine_dn = (dn + fdn if cfg.get('fine_depth_use_all', False) else fdn) if hier else 0
         scene, keep, ws = prepared or self.prepare(ref, 1, rn, max(dn, fine_dn))
         rays, rkeep = self._rays(que, dn, fdn, cfg, scene.H, scene.W)
         co_s, co = self._alloc_out(B, rn, dn, 'imgs' in que, debug, rays.ray_batch_num)
-        fi_s, fi = self._alloc_out(B, rn, fine_dn, 'imgs' in que, debug, rays.ray_batch_num)
+        fi_s, fi = self._alloc_out(B, rn, fine_dn, 'imgs' in que, debug, rays.ray_batch_num) if hier else (None, None)
         fd_in = _f32(fine_depth_in, self.device) if fine_depth_in is not None else None
         inds = torch.empty(B, rn, fdn, dtype=torch.int32, device=self.device) if debug else None
-        _lib.check(self.L.gnr_render_rays_fwd(self._sc(scene), C.byref(rays), self.wc.data_ptr(), self.wf.data_ptr(),
-                                              C.byref(co_s), C.byref(fi_s),
-                                              fd_in.data_ptr() if fd_in is not None else None,
-                                              inds.data_ptr() if debug else None,
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.L.gnr_render_rays_fwd(self._sc(scene), C.byref(rays), self.wc.data_ptr(), ptr(wf), C.byref(co_s),
+                                              C.byref(fi_s) if hier else None, ptr(fd_in), ptr(inds),
                                               ws.data_ptr(), ws.numel(), self._stream()), 'gnr_render_rays_fwd')
-        for o in (co, fi):
-            o['ray_mask'] = o['ray_mask'].view(torch.bool)       # the kernels write 0 / 1 bytes: a view, not a conversion kernel
+        self._bool_mask(co)
+        if hier:
+            self._bool_mask(fi)
         return (co, fi, inds) if debug else (co, fi)
 
     def render_by_depth(self, ref, que, depth, level='coarse', cfg=None, debug=False, prepared=None, _sample_perm=None):
@@ -258,7 +277,7 @@ class HotPath:
         scene, keep, ws = prepared or self.prepare(ref, 1, rn, dn)
         rays, rkeep = self._rays(que, dn, dn, cfg, scene.H, scene.W)
         o_s, o = self._alloc_out(B, rn, dn, 'imgs' in que, debug, rays.ray_batch_num)
-        w = self.wc if level == 'coarse' else self.wf
+        w = self._w(level)
         if _sample_perm is not None:                     # debug_render_by_depth_perm
             sp = _sample_perm.to(device=self.device, dtype=torch.int32).contiguous()
             assert sp.shape == (B, rn * dn)
@@ -269,8 +288,7 @@ class HotPath:
             _lib.check(self.L.gnr_render_by_depth_fwd(self._sc(scene), C.byref(rays), depth.data_ptr(), dn, w.data_ptr(),
                                                       C.byref(o_s), ws.data_ptr(), ws.numel(), self._stream()),
                        'gnr_render_by_depth_fwd')
-        o['ray_mask'] = o['ray_mask'].view(torch.bool)       # the kernels write 0 / 1 bytes: a view, not a conversion kernel
-        return o
+        return self._bool_mask(o)
 
     def debug_render_by_depth_perm(self, ref, que, depth, sample_perm, level='coarse', cfg=None, debug=False, prepared=None):
         """Test tooling: render_by_depth with a caller-given order in which the chain kernel visits a scene's samples -- sample_perm
@@ -311,7 +329,7 @@ class HotPath:
         coords = _f32(coords, self.device)
         B, pn, _ = coords.shape
         out = torch.empty(B, scene.V, pn, 2, dtype=torch.float32, device=self.device)
-        w = self.wc if level == 'coarse' else self.wf
+        w = self._w(level)
         _lib.check(self.L.gnr_depth_mean_fwd(self._sc(scene), coords.data_ptr(), pn, w.data_ptr(), out.data_ptr(),
                                              ws.data_ptr(), ws.numel(), self._stream()), 'gnr_depth_mean_fwd')
         return out
@@ -320,53 +338,50 @@ class HotPath:
         """Backward of depth_mean: dmean [B,V,pn,2] -> (d_canonical [36958] gradient blob of the level in state-dict
         order (mean_decoder entries), d_ray_feats [B,V,32,fh,fw] or None).  Packed weights must be current
         (`set_bwd_weights`)."""
-        if getattr(self, 'wb', None) is None or self.wb.get(level) is None:
+        if self.wb[level] is None:
             raise _lib.GnrError('depth_mean_bwd: call set_bwd_weights() first')
         scene, keep, ws = prepared or self.prepare(ref, 1)
-        need = self.L.gnr_depth_mean_bwd_workspace_bytes(self._sc(scene))
-        if getattr(self, '_dm_scratch', None) is None or self._dm_scratch.numel() < need:
-            self._dm_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        scr = self._buf('depth_mean_bwd', self.L.gnr_depth_mean_bwd_workspace_bytes(self._sc(scene)))
         coords = _f32(coords, self.device)
         dmean = _f32(dmean, self.device)
         B, pn, _ = coords.shape
         assert dmean.shape == (B, scene.V, pn, 2)
-        dcan = torch.zeros(self.L.gnr_canonical_weights_floats(), dtype=torch.float32, device=self.device)
+        dcan = self._dcan()
         dray = torch.empty(B, scene.V, 32, scene.fh, scene.fw, dtype=torch.float32, device=self.device) if want_feat_grad else None
-        w = self.wc if level == 'coarse' else self.wf
+        w = self._w(level)
         _lib.check(self.L.gnr_depth_mean_bwd(self._sc(scene), coords.data_ptr(), pn, w.data_ptr(), self.wb[level].data_ptr(),
                                              dmean.data_ptr(), dcan.data_ptr(), dray.data_ptr() if want_feat_grad else None,
-                                             ws.data_ptr(), ws.numel(), self._dm_scratch.data_ptr(), self._dm_scratch.numel(),
+                                             ws.data_ptr(), ws.numel(), scr.data_ptr(), scr.numel(),
                                              self._stream()), 'gnr_depth_mean_bwd')
         return dcan, dray
 
     # ---- sample_volume for training: forward with saved states + staged backward (csrc/gnr_bwd.inc) --------------
     def sample_volume_train(self, ref, res=40, prepared=None):
         scene, keep, ws = prepared or self.prepare(ref, res)
-        need = self.L.gnr_sample_volume_train_workspace_bytes(self._sc(scene), res)
-        if getattr(self, '_tws', None) is None or self._tws.numel() < need:
-            self._tws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        bbox_min = _f32(ref['bbox3d'], self.device)[:, 0].contiguous()
+        tws = self._buf('volume', self.L.gnr_sample_volume_train_workspace_bytes(self._sc(scene), res))
+        bbox_min = self._bbox_min(ref)
         vol = torch.empty(scene.B, 1, res, res, res, dtype=torch.float32, device=self.device)
         _lib.check(self.L.gnr_sample_volume_fwd_train(self._sc(scene), bbox_min.data_ptr(), res, self.wc.data_ptr(), vol.data_ptr(),
-                                                      ws.data_ptr(), ws.numel(), self._tws.data_ptr(), self._tws.numel(),
+                                                      ws.data_ptr(), ws.numel(), tws.data_ptr(), tws.numel(),
                                                       self._stream()), 'gnr_sample_volume_fwd_train')
-        self._train_ctx = (scene, keep, ws, res, self._tws)     # the saved states travel with the context: a release_training_workspaces()
+        self._train_ctx = (scene, keep, ws, res, tws)           # the saved states travel with the context: a release_training_workspaces()
         return vol                                               # (net.eval()) between this forward and its backward cannot take them away
 
     def train_ws_section(self, name, scene, res):
-        """Float view of one section of the training workspace (tests): save1 save2 saveG dg16 dS2 dG dS1 dfeat64 dtail."""
+        """Float view of one section of the last sample_volume_train()'s workspace (tests): save1 save2 saveG dg16 dS2 dG dS1 dfeat64 dtail."""
         names = ['save1', 'save2', 'saveG', 'dg16', 'dS2', 'dG', 'dS1', 'dfeat64', 'dtail']
         off = (C.c_size_t * 9)()
         _lib.check(self.L.gnr_train_workspace_layout(self._sc(scene), res, off), 'gnr_train_workspace_layout')
         i = names.index(name)
-        end = off[i + 1] if i + 1 < 9 else self._tws.numel()
-        return self._tws[off[i]:end].view(torch.float32)
+        tws = self._train_ctx[4]
+        end = off[i + 1] if i + 1 < 9 else tws.numel()
+        return tws[off[i]:end].view(torch.float32)
 
     def sample_volume_bwd(self, dvol, canonical_dev, stages=0x1f, want_feat_grads=True):
         """Backward of the last sample_volume_train: dvol [B,1,R,R,R] -> (d_canonical [36958], d_ray_feats, d_img_feats)."""
         scene, keep, ws, res, tws = self._train_ctx
         dvol = _f32(dvol, self.device)
-        dcan = torch.zeros(self.L.gnr_canonical_weights_floats() + (self.L.gnr_canonical_vis_floats() if self.use_vis else 0), dtype=torch.float32, device=self.device)
+        dcan = self._dcan(with_vis=True)
         shp = (scene.B, scene.V, 32, scene.fh, scene.fw)
         dray = torch.zeros(shp, dtype=torch.float32, device=self.device) if want_feat_grads else None
         dimg = torch.zeros(shp, dtype=torch.float32, device=self.device) if want_feat_grads else None
@@ -400,20 +415,14 @@ class HotPath:
         # activations left the caching allocator re-carving its pool, which showed up as occasional 50-80 ms host stalls inside the
         # forward.  Keyed by the pass's position in its forward (every ray chunk's passes are alive until the backward) and its
         # shape; safe to re-use across forwards: a training forward before the previous one's backward is refused (check_generation).
-        need_t = self.L.gnr_render_chain_train_workspace_bytes(self._sc(scene), rn, dn)
-        pool = self.__dict__.setdefault('_pass_tws', {})
-        seq = self._pass_seq = getattr(self, '_pass_seq', 0) + 1
-        key = (seq, level)                               # one buffer per pass position, grown in place when a shape needs more
-        if key not in pool or pool[key].numel() < need_t:
-            pool[key] = None                             # drop the smaller buffer before allocating its replacement
-            pool[key] = torch.empty(need_t, dtype=torch.uint8, device=self.device)
-        tws = pool[key]
+        self._pass_seq += 1                              # one buffer per pass position, grown in place when a shape needs more
+        tws = self._buf((self._pass_seq, level), self.L.gnr_render_chain_train_workspace_bytes(self._sc(scene), rn, dn))
         stats = torch.empty(B, rn * dn, 66, dtype=torch.float32, device=self.device)
         colors = torch.empty(B, rn * dn, 3, dtype=torch.float32, device=self.device)
         geo = {'depth': torch.empty(B, rn, dn, dtype=torch.float32, device=self.device) if depth is None else depth,
                'pts': torch.empty(B * rn * dn, 3, dtype=torch.float32, device=self.device),
                'qdir': torch.empty(B * rn, 3, dtype=torch.float32, device=self.device)}
-        w = self.wc if level == 'coarse' else self.wf
+        w = self._w(level)
         _lib.check(self.L.gnr_render_chain_fwd_train(self._sc(scene), C.byref(rays), None if depth is None else depth.data_ptr(), dn,
                                                      w.data_ptr(), stats.data_ptr(), colors.data_ptr(),
                                                      geo['depth'].data_ptr() if depth is None else None, geo['pts'].data_ptr(),
@@ -427,11 +436,11 @@ class HotPath:
         dstats = _f32(dstats, self.device)
         dcolors = _f32(dcolors, self.device)
         assert dstats.shape[-1] == 65 and dcolors.shape[-1] == 3
-        dcan = torch.zeros(self.L.gnr_canonical_weights_floats() + (self.L.gnr_canonical_vis_floats() if self.use_vis else 0), dtype=torch.float32, device=self.device)
+        dcan = self._dcan(with_vis=True)
         shp = (scene.B, scene.V, 32, scene.fh, scene.fw)
         dray = torch.empty(shp, dtype=torch.float32, device=self.device)
         dimg = torch.empty(shp, dtype=torch.float32, device=self.device)
-        w = self.wc if level == 'coarse' else self.wf
+        w = self._w(level)
         _lib.check(self.L.gnr_render_chain_bwd(self._sc(scene), rn, dn, w.data_ptr(), self.wb[level].data_ptr(), dstats.data_ptr(),
                                                dcolors.data_ptr(), dcan.data_ptr(), dray.data_ptr(), dimg.data_ptr(), ws.data_ptr(),
                                                ws.numel(), tws.data_ptr(), tws.numel(), self._stream()), 'gnr_render_chain_bwd')
@@ -452,11 +461,11 @@ class HotPath:
         o_s.depth = None
         o_s.view_mask = None
         fd = torch.empty(scene.B, rn, rays.fdn, dtype=torch.float32, device=self.device) if want_fine_depth else None
-        w = self.wc if level == 'coarse' else self.wf
+        w = self._w(level)
         _lib.check(self.L.gnr_render_tail_fwd_train(self._sc(scene), C.byref(rays), depth.data_ptr(), dn, w.data_ptr(), C.byref(o_s),
                                                     fd.data_ptr() if want_fine_depth else None, ws.data_ptr(), ws.numel(),
                                                     tws.data_ptr(), tws.numel(), self._stream()), 'gnr_render_tail_fwd_train')
-        o['ray_mask'] = o['ray_mask'].view(torch.bool)       # the kernels write 0 / 1 bytes: a view, not a conversion kernel
+        self._bool_mask(o)
         o.pop('depth'), o.pop('view_mask')
         if want_fine_depth:
             o['fine_depth'] = fd
@@ -470,11 +479,9 @@ class HotPath:
         assert stats.shape == (P, 66) and pts.shape == (P, 3) and gamma.shape == (P, 3)
         g = torch.empty(P, 16, dtype=torch.float32, device=self.device)
         gd = torch.empty_like(g)
-        need = self.L.gnr_geo_dual_fwd_workspace_bytes()
-        if getattr(self, '_gdf_scratch', None) is None or self._gdf_scratch.numel() < need:
-            self._gdf_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        scr = self._buf('geo_dual_fwd', self.L.gnr_geo_dual_fwd_workspace_bytes())
         _lib.check(self.L.gnr_geo_dual_fwd(canon.data_ptr(), stats.data_ptr(), pts.data_ptr(), gamma.data_ptr(), g.data_ptr(),
-                                           gd.data_ptr(), P, self._gdf_scratch.data_ptr(), self._gdf_scratch.numel(), self.options,
+                                           gd.data_ptr(), P, scr.data_ptr(), scr.numel(), self.options,
                                            self._stream()), 'gnr_geo_dual_fwd')
         return g, gd
 
@@ -483,13 +490,11 @@ class HotPath:
         stats, pts, gamma, gbar, gdbar = (_f32(x, self.device) for x in (stats, pts, gamma, gbar, gdbar))
         P = stats.shape[0]
         dstats = torch.empty(P, 66, dtype=torch.float32, device=self.device)
-        dcan = torch.zeros(self.L.gnr_canonical_weights_floats(), dtype=torch.float32, device=self.device)
-        need = self.L.gnr_geo_dual_bwd_workspace_bytes(P)
-        if getattr(self, '_gd_scratch', None) is None or self._gd_scratch.numel() < need:
-            self._gd_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        dcan = self._dcan()
+        scr = self._buf('geo_dual_bwd', self.L.gnr_geo_dual_bwd_workspace_bytes(P))
         _lib.check(self.L.gnr_geo_dual_bwd(canon.data_ptr(), stats.data_ptr(), pts.data_ptr(), gamma.data_ptr(), gbar.data_ptr(),
-                                           gdbar.data_ptr(), dstats.data_ptr(), dcan.data_ptr(), P, self._gd_scratch.data_ptr(),
-                                           self._gd_scratch.numel(), self.options, self._stream()), 'gnr_geo_dual_bwd')
+                                           gdbar.data_ptr(), dstats.data_ptr(), dcan.data_ptr(), P, scr.data_ptr(),
+                                           scr.numel(), self.options, self._stream()), 'gnr_geo_dual_bwd')
         return dstats, dcan
 
     def composite_bwd(self, level, sdf, grad, col, depth, qdir, dpix, ddepth=None, wgerr=None, dalpha=None, dhit=None):
@@ -503,8 +508,8 @@ class HotPath:
         a, gamma, dcol = torch.empty_like(sdf), torch.empty_like(grad), torch.empty_like(col)
         dvar = torch.empty(1, dtype=torch.float32, device=self.device)
         ptr = lambda x: None if x is None else x.data_ptr()
-        w = self.wc if level == 'coarse' else self.wf
-        scr = self._scratch('comp', self.L.gnr_composite_bwd_workspace_bytes(R))
+        w = self._w(level)
+        scr = self._buf('composite_bwd', self.L.gnr_composite_bwd_workspace_bytes(R))
         _lib.check(self.L.gnr_composite_bwd(w.data_ptr(), sdf.data_ptr(), grad.data_ptr(), col.data_ptr(), depth.data_ptr(),
                                             qdir.data_ptr(), dpix.data_ptr(), ptr(ddepth), ptr(wgerr), ptr(dalpha), ptr(dhit),
                                             a.data_ptr(), gamma.data_ptr(), dcol.data_ptr(), dvar.data_ptr(), R, dn,
@@ -518,8 +523,8 @@ class HotPath:
         R, dn, _ = g.shape
         gbar, gdbar = torch.empty_like(g), torch.empty_like(g)
         dtail = torch.empty(self.L.gnr_ray_tail_grad_floats(), dtype=torch.float32, device=self.device)
-        w = self.wc if level == 'coarse' else self.wf
-        scr = self._scratch('tail', self.L.gnr_ray_tail_dual_bwd_workspace_bytes())
+        w = self._w(level)
+        scr = self._buf('ray_tail_dual_bwd', self.L.gnr_ray_tail_dual_bwd_workspace_bytes())
         _lib.check(self.L.gnr_ray_tail_dual_bwd(w.data_ptr(), g.data_ptr(), gd.data_ptr(), a.data_ptr(), nvalid.data_ptr(),
                                                 gbar.data_ptr(), gdbar.data_ptr(), dtail.data_ptr(), R, dn, scr.data_ptr(), scr.numel(),
                                                 self.options, self._stream()), 'gnr_ray_tail_dual_bwd')
@@ -528,10 +533,7 @@ class HotPath:
     def release_training_workspaces(self):
         """Give the per-pass training workspaces (about 1 GB each at 8 scenes x 512 rays x 40 samples), the volume's training
         workspace and the backward scratch buffers back to the allocator (after training, before a long evaluation)."""
-        self.__dict__.pop('_pass_tws', None)
-        self.__dict__.pop('_scratch_bufs', None)
-        self._tws = None
-        self._dm_scratch = self._gd_scratch = None
+        self._bufs = {}
 
     def set_bwd_weights(self, packed_bwd_coarse, packed_bwd_fine=None):
         t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(self.device)

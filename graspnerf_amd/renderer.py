@@ -304,7 +304,11 @@ class NeuralRayRenderer(nn.Module):
             self.fine_dist_decoder = _DistDecoderParams(self.use_vis)
             self.fine_agg_net = _AggNetParams(c['fine_agg_net_cfg'])
         self.use_sdf = True
-        self._hot = None
+        self._hot = None                                   # the HotPath of the current parameters (_sync_hot; _drop_hot forgets it)
+        self._hot_ver = self._bwd_ver = None               # _hot_versions() the forward / the backward blobs were packed at
+        self._hot_params = self._param_dict = None         # caches of _hot_versions() / _params()
+        self._hot_options = {}                             # what set_hot_option was asked: name -> on / off
+        self._stage_bufs = {}                              # pinned staging buffers of _upload
 
     def train(self, mode=True):
         if not mode and self._hot is not None:             # leaving training: the gigabyte-sized per-pass workspaces go back to the allocator
@@ -312,33 +316,35 @@ class NeuralRayRenderer(nn.Module):
         return super().train(mode)
 
     # ---- HIP hot path handle (re-packed when parameters change device or values) -----------------
+    def _drop_hot(self):
+        """Forget the HotPath (packed weights, workspaces, options set on it) and the parameter caches: the next hot() /
+        hot_for_training() builds them from the current parameters."""
+        self._hot = self._hot_ver = self._bwd_ver = self._hot_params = self._param_dict = None
+
     def _apply(self, fn, *a, **k):
-        self._hot = None
+        self._drop_hot()
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
-        self._hot = None
+        self._drop_hot()
         return super().load_state_dict(*a, **k)
 
     def _hot_versions(self):
         """Autograd version counters of the hot-path parameters: every in-place update (optimizer.step, copy_, load_state_dict)
         bumps them, so a change means the packed copies in the HotPath are stale."""
-        ps = getattr(self, '_hot_params', None)
-        if ps is None or self._hot is None:                  # (re)collected whenever the HotPath is rebuilt (_apply / load_state_dict)
+        if self._hot_params is None:                         # (re)collected whenever the HotPath is rebuilt (_drop_hot)
             P = self._params()
-            ps = self._hot_params = [P[k] for lvl in self.levels for k, _ in _w.level_keys(lvl)]
+            self._hot_params = [P[k] for lvl in self.levels for k, _ in _w.level_keys(lvl)]
             if self.use_vis:
-                ps += [P[_w.LEVELS[lvl][0] + k] for lvl in self.levels for k, _ in _w.VIS_KEYS]
+                self._hot_params += [P[_w.LEVELS[lvl][0] + k] for lvl in self.levels for k, _ in _w.VIS_KEYS]
         # (version, storage address): optimizer.step / copy_ / load_state_dict bump the version, `p.data = tensor` moves the
         # storage.  A write through `p.data.copy_()` / `p.data.mul_()` changes neither: call invalidate_packed() after such surgery.
-        return tuple((p._version, p.data_ptr()) for p in ps)
+        return tuple((p._version, p.data_ptr()) for p in self._hot_params)
 
     def invalidate_packed(self):
-        """Forget the packed HIP copies of the hot-path weights: the next forward re-packs from the current parameter values.
+        """Forget the packed HIP copies of the hot-path weights: the next forward packs the current parameter values again.
         Needed only after in-place writes that bypass autograd's version counters (p.data.copy_, EMA swaps through .data)."""
-        self._hot_ver = None
-        self._bwd_ver = None
-        self.__dict__.pop('_param_dict', None)
+        self._drop_hot()
 
     def _vis_dev(self, sd, lvl):
         """The vis_decoder's six tensors of a level (use_vis) as one flat device tensor, state-dict order."""
@@ -359,8 +365,7 @@ class NeuralRayRenderer(nn.Module):
             if vis[lvl] is not None:
                 _lib.check(L.gnr_pack_vis_decoder_device(vis[lvl].data_ptr(), blob.data_ptr(), st), 'gnr_pack_vis_decoder_device')
         if with_bwd:
-            wb = getattr(hot, 'wb', None)
-            if wb is None or wb.get(self.levels[-1]) is None:
+            if hot.wb[self.levels[-1]] is None:
                 # first training forward: the backward blobs are created from host packs once (their structural zeros stay; the
                 # device packer rewrites the rest every step)
                 host = {lvl: t.cpu().numpy() for lvl, t in can_dev.items()}
@@ -368,45 +373,62 @@ class NeuralRayRenderer(nn.Module):
                 hot.set_bwd_weights(*[_w.pack_bwd(host[lvl], hv[lvl]) for lvl in self.levels])
             else:
                 for lvl in self.levels:
-                    _lib.check(L.gnr_pack_weights_bwd_device(can_dev[lvl].data_ptr(), wb[lvl].data_ptr(), st), 'gnr_pack_weights_bwd_device')
+                    _lib.check(L.gnr_pack_weights_bwd_device(can_dev[lvl].data_ptr(), hot.wb[lvl].data_ptr(), st), 'gnr_pack_weights_bwd_device')
                     if vis[lvl] is not None:
-                        _lib.check(L.gnr_pack_vis_decoder_bwd_device(vis[lvl].data_ptr(), wb[lvl].data_ptr(), st), 'gnr_pack_vis_decoder_bwd_device')
+                        _lib.check(L.gnr_pack_vis_decoder_bwd_device(vis[lvl].data_ptr(), hot.wb[lvl].data_ptr(), st), 'gnr_pack_vis_decoder_bwd_device')
             hot.can_dev = can_dev
 
-    def hot(self):
-        """The HIP path with weights packed from the CURRENT parameter values: re-packed (on the device) whenever a parameter was
-        updated in place since the last packing (an eval forward after optimizer.step() must not run on the previous weights)."""
+    def _sync_hot(self, with_bwd):
+        """The HIP path with weights packed from the CURRENT parameter values: built when there is none, re-packed (on the device,
+        stream-ordered, without a host wait) whenever a parameter was updated in place since the last packing -- an eval forward after
+        optimizer.step() must not run on the previous weights.  with_bwd: also the transposed fragments of the backward twins and
+        the canonical blobs (can_dev)."""
         ver = self._hot_versions()
         if self._hot is None:
             sd = self.state_dict()
-            dev = next(self.parameters()).device
-            self._hot = HotPath(*[_w.pack_state_dict(sd, lvl) for lvl in self.levels], device=dev)
+            self._hot = HotPath(*[_w.pack_state_dict(sd, lvl) for lvl in self.levels], device=next(self.parameters()).device)
+            self._merge_hot_options(self._hot)
             self._hot_ver = ver
-        elif getattr(self, '_hot_ver', None) != ver:
-            self._repack_on_device(with_bwd=False)
+        hot = self._hot
+        # (the first backward re-pack creates the backward blobs from a host pack and sets can_dev)
+        stale_bwd = with_bwd and (self._bwd_ver != ver or hot.wb[self.levels[-1]] is None or hot.can_dev is None)
+        if self._hot_ver != ver or stale_bwd:
+            self._repack_on_device(with_bwd)
             self._hot_ver = ver
-        if self.__dict__.get('_hot_option_bits') is not None:
-            self._hot.options = self._hot_option_bits
-        return self._hot
+            if with_bwd:
+                self._bwd_ver = ver
+        return hot
+
+    def hot(self):
+        """The HIP path with the current weights (_sync_hot)."""
+        return self._sync_hot(with_bwd=False)
+
+    def hot_for_training(self):
+        """The HIP path with the current weights, the backward twins' included (_sync_hot)."""
+        return self._sync_hot(with_bwd=True)
+
+    def _merge_hot_options(self, hot):
+        """What set_hot_option was asked, into hot.options: those bits set or cleared, every other bit left alone."""
+        for name, on in self._hot_options.items():
+            HotPath.set_option(hot, name, on)              # (touches `options` alone)
 
     def set_hot_option(self, name, on=True):
-        """A per-call option of the HIP path (include/gnr.h GNR_OPT_*; hotpath.HotPath.set_option) for every call THIS module makes --
-        kept here because the HotPath is rebuilt whenever the parameters move (`.to()`, load_state_dict); -> previous setting."""
-        from . import _lib
-        bit = _lib.OPTIONS[name]
-        bits = self.__dict__.get('_hot_option_bits')
-        if bits is None:
-            bits = self._hot.options if self._hot is not None else HotPath.default_options
-        self.__dict__['_hot_option_bits'] = (bits | bit) if on else (bits & ~bit)
+        """A per-call option of the HIP path (include/gnr.h GNR_OPT_*; hotpath.HotPath.set_option) for every call THIS module makes;
+        -> previous setting.  The request is kept here (the HotPath is rebuilt whenever the parameters move: `.to()`,
+        load_state_dict) and reaches a HotPath at two moments only: now, when there is one, and when one is built, on top of
+        HotPath.default_options.  Bits switched on the HotPath itself stay as they are for the life of that HotPath."""
         if self._hot is not None:
-            self._hot.options = self._hot_option_bits
-        return bool(bits & bit)
+            prev = self._hot.set_option(name, on)
+        else:
+            prev = self._hot_options.get(name, bool(HotPath.default_options & _lib.OPTIONS[name]))
+        self._hot_options[name] = bool(on)
+        return prev
 
     def _upload(self, name, host_tensor, dev):
         """Host tensor -> device through a persistent pinned staging buffer (one per name): `x.pin_memory()` every step
         goes through the caching host allocator, whose occasional fresh hipHostMalloc showed up as 30-60 ms outlier steps
         (1 in 20).  The buffer is rewritten only after the previous copy out of it has completed."""
-        bufs = self.__dict__.setdefault('_stage_bufs', {})
+        bufs = self._stage_bufs
         ent = bufs.get(name)
         if ent is None or ent[0].shape != host_tensor.shape or ent[0].dtype != host_tensor.dtype:
             ent = [torch.empty(host_tensor.shape, dtype=host_tensor.dtype, pin_memory=True), None]
@@ -418,29 +440,6 @@ class NeuralRayRenderer(nn.Module):
         ent[1] = torch.cuda.Event()
         ent[1].record()
         return out
-
-    def repack_begin(self):
-        """Kept for callers of the round-2..4 interface (the re-pack used to start its device-to-host copies here, ahead of the 2D
-        backbones, and finish on the host in hot_for_training()).  The packer runs on the device now: nothing to start early."""
-        return None
-
-    def hot_for_training(self):
-        """The HIP path with weights re-packed from the CURRENT parameter values (they move every optimiser step), plus
-        the transposed fragments of the backward twins -- all on the device, stream-ordered, without a host wait."""
-        ver = self._hot_versions()
-        if self._hot is None:
-            sd = self.state_dict()
-            dev = next(self.parameters()).device
-            self._hot = HotPath(*[_w.pack_state_dict(sd, lvl) for lvl in self.levels], device=dev)
-            ver = self._hot_versions()
-            self._repack_on_device(with_bwd=True)            # creates the backward blobs (host pack, once) and can_dev
-        elif getattr(self, '_hot_ver', None) != ver or getattr(self._hot, 'wb', None) is None or self._hot.wb.get(self.levels[-1]) is None \
-                or getattr(self._hot, 'can_dev', None) is None or getattr(self, '_bwd_ver', None) != ver:
-            self._repack_on_device(with_bwd=True)
-        self._hot_ver = self._bwd_ver = ver
-        if self.__dict__.get('_hot_option_bits') is not None:
-            self._hot.options = self._hot_option_bits
-        return self._hot
 
     def _train_prep(self, ref_imgs_info, rn=0):
         """Once per training forward on the GPU: re-packed weights and the prepared (channel-last) feature maps shared
@@ -465,7 +464,8 @@ class NeuralRayRenderer(nn.Module):
         bref = self._batched_ref(ref_imgs_info)
         R = c.get('volume_resolution', 40)
         grad = c.get('volume_gradient', False) if volume_gradient is None else volume_gradient
-        return bref, self.hot().prepare(bref, R, rn, self._dn_max(), grad_res=R if grad else 0)
+        hot = self.hot()
+        return hot, bref, hot.prepare(bref, R, rn, self._dn_max(), grad_res=R if grad else 0)
 
     @staticmethod
     def _batched_que(que):
@@ -504,10 +504,9 @@ class NeuralRayRenderer(nn.Module):
         """name -> Parameter of this module tree.  Cached (named_parameters() walks ~1 000 modules, several times per training step:
         2 ms of a step's host time); the Parameter OBJECTS are stable across optimizer steps, and whatever replaces them -- _apply
         (device / dtype moves), load_state_dict, invalidate_packed() -- drops the cache together with the packed weights."""
-        d = self.__dict__.get('_param_dict')
-        if d is None or self._hot is None:
-            d = self.__dict__['_param_dict'] = dict(self.named_parameters())
-        return d
+        if self._param_dict is None or self._hot is None:
+            self._param_dict = dict(self.named_parameters())
+        return self._param_dict
 
     def _train_pass(self, hot, prep, que_b, depth, level, want_fine_depth, ray_feats, img_feats, P):
         """One render pass (renderer.py:90-138) of B scenes in training mode: per-view chain -> per-ray tail -> NeuS alpha /
@@ -581,26 +580,27 @@ class NeuralRayRenderer(nn.Module):
             st.pop('ray_mask', None), st.pop('ray_mask_fine', None)
         return st
 
-    def _render_autograd(self, que, ref, _prep=None):
-        """One scene in training mode (the reference's API): the is_train inverse-CDF samples are drawn exactly as the
-        reference draws them (one torch.rand([1,chunk_rn,fdn]) on the CPU generator per ray chunk, render_ops.py:204-205),
-        the NeuS step counters advance once per chunk (aggregate_net.py:135-137)."""
-        self._need_gpu(ref['imgs'])
-        hot, bref, prep = _prep if _prep is not None and len(_prep) == 3 else self._train_prep(ref, que['coords'].shape[1])
-        rn, chunk, fdn = que['coords'].shape[1], self.cfg['ray_batch_num'], self.cfg['fine_depth_sample_num']
-        us = []
-        hier = bool(self.cfg['use_hierarchical_sampling'])                  # without it the reference neither draws (sample_fine_depth is
-        for r0 in range(0, rn, chunk):                                      # not called) nor runs the fine aggregation net (its step stays)
-            if hier:
-                us.append(torch.rand([1, min(chunk, rn - r0), fdn]))
+    def _train_draws(self, rn):
+        """The random draws and the bookkeeping of ONE scene's training render of rn rays, exactly the reference's: per ray chunk
+        the NeuS step counters advance once (aggregate_net.py:135-137) and draw_fine_u draws the is_train inverse-CDF samples.
+        Without hierarchical sampling the reference neither draws (sample_fine_depth is not called) nor runs the fine aggregation
+        net (its step stays).  -> fine_u [1,rn,fdn] on the host, or None."""
+        c = self.cfg
+        hier = bool(c['use_hierarchical_sampling'])
+        for _ in range(0, rn, c['ray_batch_num']):
             for net in ((self.agg_net, self.fine_agg_net) if hier else (self.agg_net,)):
                 net.train_step_bookkeeping()
-        dev = ref['imgs'].device
-        fine_u = self._upload('fine_u1', torch.cat(us, 1), dev) if hier else None
-        bq = {'coords': que['coords'], 'pose': que['poses'], 'K': que['Ks'], 'depth_range': que['depth_range']}
-        if 'imgs' in que:
-            bq['imgs'] = que['imgs']
-        return self._render_train(hot, prep, bq, fine_u, ref['ray_feats'][None], ref['img_feats'][None])    # B = 1: the stacks ARE the reference's shapes
+        return self.draw_fine_u(rn, c['fine_depth_sample_num'], c['ray_batch_num']) if hier else None
+
+    def _render_autograd(self, que, ref, _prep=None):
+        """One scene in training mode (the reference's API), random draws and step counters as the reference's (_train_draws)."""
+        self._need_gpu(ref['imgs'])
+        rn = que['coords'].shape[1]
+        hot, bref, prep = _prep or self._train_prep(ref, rn)
+        fine_u = self._train_draws(rn)
+        if fine_u is not None:
+            fine_u = self._upload('fine_u1', fine_u, ref['imgs'].device)
+        return self._render_train(hot, prep, self._batched_que(que), fine_u, ref['ray_feats'][None], ref['img_feats'][None])    # B = 1: the stacks ARE the reference's shapes
 
     @staticmethod
     def draw_fine_u(rn, fdn, chunk):
@@ -612,17 +612,17 @@ class NeuralRayRenderer(nn.Module):
     def sample_volume(self, ref_imgs_info, _prep=None, is_train=False):     # renderer.py:164-199
         if self._use_autograd(is_train):
             self._need_gpu(ref_imgs_info['imgs'])
-            hot, bref, prep = _prep if _prep is not None and len(_prep) == 3 else self._train_prep(ref_imgs_info)
+            hot, bref, prep = _prep or self._train_prep(ref_imgs_info)
             P = self._params()
             return _SampleVolumeFn.apply(hot, bref, prep, self.cfg['volume_resolution'], ref_imgs_info['ray_feats'][None],
                                          ref_imgs_info['img_feats'][None], *[P[k] for k, _ in _w.level_keys('coarse', use_vis=self.use_vis)])
-        bref, prep = _prep or self._prepare(ref_imgs_info)
+        hot, bref, prep = _prep or self._prepare(ref_imgs_info)
         if not self.cfg.get('warn_low_valid_ratio', False):
-            return self.hot().sample_volume(bref, self.cfg['volume_resolution'], prepared=prep)
+            return hot.sample_volume(bref, self.cfg['volume_resolution'], prepared=prep)
         # renderer.py:174-176: the reference reads the share of (view, voxel) pairs that project into their image back to the
         # host on every call and prints when it is below one half.  Opt-in here (cfg warn_low_valid_ratio): the read is a
         # host synchronisation (and not capturable in a hipGraph); the in-image bits come out of the chain kernel anyway.
-        vol, vmask = self.hot().sample_volume(bref, self.cfg['volume_resolution'], want_mask=True, prepared=prep)
+        vol, vmask = hot.sample_volume(bref, self.cfg['volume_resolution'], want_mask=True, prepared=prep)
         V = bref['imgs'].shape[1]
         bits = sum(((vmask >> v) & 1).float() for v in range(V))
         valid_ratio = bits.reshape(vmask.shape[0], -1).sum(1) / float(V * vmask[0].numel())
@@ -635,8 +635,8 @@ class NeuralRayRenderer(nn.Module):
         next to the SDF (ibrnet.py:485-513, the VJP with ones of a column's SDF values w.r.t. its query points) and the reference's
         volume path drops (aggregate_net.py:133-134).  Inference only: there is no backward for it.
         want_error: -> (gradient, mean((|gradient|-1)^2) [1])."""
-        bref, prep = _prep or self._prepare(ref_imgs_info, volume_gradient=True)
-        return self.hot().sample_volume_gradient(bref, self.cfg['volume_resolution'], want_error=want_error, prepared=prep)
+        hot, bref, prep = _prep or self._prepare(ref_imgs_info, volume_gradient=True)
+        return hot.sample_volume_gradient(bref, self.cfg['volume_resolution'], want_error=want_error, prepared=prep)
 
     def _out_dict(self, o, suffix, level_net):
         keys = ['sdf_values', 'alpha_values', 'colors_nr', 'hit_prob_nr', 'pixel_colors_nr']
@@ -658,20 +658,16 @@ class NeuralRayRenderer(nn.Module):
         rn = que_imgs_info['coords'].shape[1]
         if self._use_autograd(is_train):
             return self._render_autograd(que_imgs_info, ref_imgs_info, _prep)
-        bref, prep = _prep or self._prepare(ref_imgs_info, rn)
+        hot, bref, prep = _prep or self._prepare(ref_imgs_info, rn)
         bque = self._batched_que(que_imgs_info)
         hier = bool(self.cfg['use_hierarchical_sampling'])
         if is_train:
-            # forward values only (no autograd through the HIP path).  The reference draws the
-            # inverse-CDF samples per chunk with torch.rand on the CPU generator (render_ops.py:204-208): same
-            # draws, same order, so a seeded run samples the same fine depths.
-            fdn, chunk = self.cfg['fine_depth_sample_num'], self.cfg['ray_batch_num']
+            # forward values only (no autograd through the HIP path): the reference's draws in the reference's order
+            # (_train_draws), so a seeded run samples the same fine depths
+            fine_u = self._train_draws(rn)
             if hier:
-                bque['fine_u'] = self.draw_fine_u(rn, fdn, chunk)
-            for net in ((self.agg_net, self.fine_agg_net) if hier else (self.agg_net,)):          # aggregate_net.py:135-137 bookkeeping
-                for _ in range((rn + chunk - 1) // chunk):
-                    net.train_step_bookkeeping()
-        co, fi = self.hot().render(bref, bque, self._render_cfg(), prepared=prep)
+                bque['fine_u'] = fine_u
+        co, fi = hot.render(bref, bque, self._render_cfg(), prepared=prep)
         out = self._out_dict(co, '', self.agg_net)
         if hier:                                                            # renderer.py:157-161
             out.update(self._out_dict(fi, '_fine', self.fine_agg_net))
@@ -698,35 +694,32 @@ class NeuralRayRenderer(nn.Module):
         h, w = ref_imgs_info['imgs'].shape[-2:]
         rfn = ref_imgs_info['imgs'].shape[0]
         coords = self.gen_depth_loss_coords(h, w, ref_imgs_info['imgs'].device)
+        xy = coords.to(torch.float32)[None]                                 # the reference feeds (row, col) where (x, y) is expected; kept
         if self._use_autograd(is_train):
-            P = self._params()
             self._need_gpu(ref_imgs_info['imgs'])
             # HIP forward + HIP backward behind an autograd.Function (csrc/gnr_bwd.inc)
-            hot, bref, prep = _prep if _prep is not None and len(_prep) == 3 else self._train_prep(ref_imgs_info)
-            xy = coords.to(torch.float32)[None]
+            hot, bref, prep = _prep or self._train_prep(ref_imgs_info)
+            P = self._params()
             ms = [_DepthMeanFn.apply(hot, bref, prep, xy, lvl, ref_imgs_info['ray_feats'][None],
                                      *[P[_w.LEVELS[lvl][0] + 'mean_decoder.' + n] for n in _DM_PARAMS])[0] for lvl in self.levels]
-            out = {'depth_mean': ms[0][..., 0], 'depth_coords': coords[None].repeat(rfn, 1, 1), 'depth_mean_2': ms[0][..., 1]}
-            if len(ms) > 1:                                                 # renderer.py:247-251,259-264: the fine means only with hierarchical sampling
-                out.update({'depth_mean_fine': ms[1][..., 0], 'depth_mean_fine_2': ms[1][..., 1]})
-            return out
-        # the reference feeds (row, col) where (x, y) is expected; kept
-        xy = coords.to(torch.float32)[None]
-        bref, prep = _prep or self._prepare(ref_imgs_info)
-        hot = self.hot()
-        mc = hot.depth_mean(bref, xy, 'coarse', prepared=prep)[0]
-        out = {'depth_mean': mc[..., 0], 'depth_coords': coords[None].repeat(rfn, 1, 1), 'depth_mean_2': mc[..., 1]}
-        if len(self.levels) > 1:
-            mf = hot.depth_mean(bref, xy, 'fine', prepared=prep)[0]
-            out.update({'depth_mean_fine': mf[..., 0], 'depth_mean_fine_2': mf[..., 1]})
+        else:
+            hot, bref, prep = _prep or self._prepare(ref_imgs_info)
+            ms = [hot.depth_mean(bref, xy, lvl, prepared=prep)[0] for lvl in self.levels]
+        return self._depth_mean_dict(ms, coords[None].repeat(rfn, 1, 1))
+
+    @staticmethod
+    def _depth_mean_dict(ms, coords):
+        """predict_mean_for_depth_loss's output keys from the levels' means (renderer.py:247-251,259-264: the fine ones only with
+        hierarchical sampling)."""
+        out = {'depth_mean': ms[0][..., 0], 'depth_coords': coords, 'depth_mean_2': ms[0][..., 1]}
+        if len(ms) > 1:
+            out.update({'depth_mean_fine': ms[1][..., 0], 'depth_mean_fine_2': ms[1][..., 1]})
         return out
 
     def forward(self, data):                                                # renderer.py:268-291
         ref = dict(data['ref_imgs_info'])
         que = dict(data['que_imgs_info'])
         is_train = 'eval' not in data
-        if self._use_autograd(is_train) and ref['imgs'].is_cuda:
-            self.repack_begin()                                             # finished in _train_prep, behind the backbones
         ref['img_feats'] = self.image_encoder(ref['imgs'])
         ref['ray_feats'] = self.init_net(ref, data.get('src_imgs_info'), is_train)
         ref['ray_feats'] = self.vis_encoder(ref['ray_feats'], ref['img_feats'])
@@ -746,7 +739,6 @@ class NeuralRayRenderer(nn.Module):
             out.update(self.predict_mean_for_depth_loss(ref, _prep=prep, is_train=is_train))
         return out
 
-
     def forward_scenes(self, datas, stacked=False):
         """Training forward of several scenes in ONE pass (trainer-internal; the reference's API is one scene per forward):
         batched backbones, one weight re-pack, batched HIP twin pairs, one per-ray tail over the rays of all scenes.  Same
@@ -764,7 +756,7 @@ class NeuralRayRenderer(nn.Module):
             return None
         B, V = len(datas), refs[0]['imgs'].shape[0]
         h, w = refs[0]['imgs'].shape[-2:]
-        rn, fdn, R = ques[0]['coords'].shape[1], c['fine_depth_sample_num'], c['volume_resolution']
+        rn, R = ques[0]['coords'].shape[1], c['volume_resolution']
         dev = refs[0]['imgs'].device
         # The backbones are queued first; the weights are re-packed on the device behind them (hot_for_training: stream-ordered
         # kernels, nothing waits), and the reference's CPU random draws reach the device in one pinned copy each.
@@ -775,15 +767,11 @@ class NeuralRayRenderer(nn.Module):
         hot = self.hot_for_training()
         want_depth = c.get('use_depth_loss', False) and 'true_depth' in refs[0]
         us, coords = [], []
-        hier = bool(c['use_hierarchical_sampling'])
         for _ in range(B):                                                  # the per-scene draw order of forward()
-            if hier:
-                us.append(torch.rand([1, rn, fdn]))
-            for net in ((self.agg_net, self.fine_agg_net) if hier else (self.agg_net,)):
-                net.train_step_bookkeeping()
+            us.append(self._train_draws(rn))
             if want_depth:
                 coords.append(self.gen_depth_loss_coords(h, w, dev, keep_on_host=True))
-        fine_u = self._upload('fine_u', torch.cat(us), dev) if hier else None
+        fine_u = self._upload('fine_u', torch.cat(us), dev) if c['use_hierarchical_sampling'] else None
         if want_depth:
             coords = torch.stack(coords)                                    # [B,8192,2]
             coords = coords if coords.is_cuda else self._upload('depth_coords', coords, dev)
@@ -793,19 +781,14 @@ class NeuralRayRenderer(nn.Module):
                 'bbox3d': stack('bbox3d', refs)}
         prep = hot.prepare(bref, R, rn, self._dn_max())
         P = self._params()
-        que_b = {'coords': torch.cat([q['coords'] for q in ques]), 'pose': torch.cat([q['poses'] for q in ques]),
-                 'K': torch.cat([q['Ks'] for q in ques]), 'depth_range': torch.cat([q['depth_range'] for q in ques])}
-        if 'imgs' in ques[0]:
-            que_b['imgs'] = torch.cat([q['imgs'] for q in ques])
+        que_b = self._batched_que({k: torch.cat([q[k] for q in ques]) for k in ('coords', 'poses', 'Ks', 'depth_range', 'imgs') if k in ques[0]})
         st = self._render_train(hot, prep, que_b, fine_u, ray_feats, img_feats)
         st['volume'] = _SampleVolumeFn.apply(hot, bref, prep, R, ray_feats, img_feats, *[P[k] for k, _ in _w.level_keys('coarse', use_vis=self.use_vis)])
         if want_depth:
             xy = coords.to(torch.float32)
             ms = [_DepthMeanFn.apply(hot, bref, prep, xy, lvl, ray_feats, *[P[_w.LEVELS[lvl][0] + 'mean_decoder.' + n] for n in _DM_PARAMS])
                   for lvl in self.levels]
-            st.update({'depth_mean': ms[0][..., 0], 'depth_coords': coords[:, None].expand(B, V, *coords.shape[1:]), 'depth_mean_2': ms[0][..., 1]})
-            if len(ms) > 1:
-                st.update({'depth_mean_fine': ms[1][..., 0], 'depth_mean_fine_2': ms[1][..., 1]})
+            st.update(self._depth_mean_dict(ms, coords[:, None].expand(B, V, *coords.shape[1:])))
         return st if stacked else self.unstack(st, B)
 
 

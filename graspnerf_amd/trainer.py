@@ -116,9 +116,10 @@ class Trainer:
 
     def _note_backward_status(self):
         """After a backward: OR the lost-partner bit of the HIP path's status words into the step's flag -- on the device, nothing waits."""
-        hot = getattr(getattr(self.net, 'nr_net', None), '_hot', None)
-        if hot is None or getattr(hot, '_prepared', None) is None:
+        nr = getattr(self.net, 'nr_net', None)             # (a net without the volumetric path has no HIP status words)
+        if nr is None or nr._hot is None or nr._hot._prepared is None:
             return
+        hot = nr._hot
         bad = (hot.status_words() & 16).ne(0).any()
         self._bad = bad if self._bad is None else (self._bad | bad)
 
