@@ -207,6 +207,13 @@ def lib():
     L.gnr_render_chain_bwd.argtypes = [C.POINTER(GnrScene), C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p, C.c_size_t,
                                        C.c_void_p, C.c_size_t, C.c_void_p]
     L.gnr_render_chain_bwd.restype = C.c_int
+    L.gnr_scatter_workspace_layout.argtypes = [C.POINTER(GnrScene), C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    L.gnr_scatter_workspace_layout.restype = C.c_int
+    L.gnr_debug_feature_scatter_bytes.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_size_t)]
+    L.gnr_debug_feature_scatter_bytes.restype = C.c_size_t
+    L.gnr_debug_feature_scatter.argtypes = [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.gnr_debug_feature_scatter.restype = C.c_int
     L.gnr_render_tail_fwd_train.argtypes = [C.POINTER(GnrScene), C.POINTER(GnrRays), C.c_void_p, C.c_int, C.c_void_p,
                                             C.POINTER(GnrRenderOut), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                             C.c_void_p]
@@ -308,7 +315,8 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_frame_metrics_workspace_bytes', 'gnr_frame_metrics',
             'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd',
             'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd',
-            'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid']
+            'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid',
+            'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 
 def check(rc, what):

@@ -1126,7 +1126,7 @@ __global__ __launch_bounds__(256, 1) void k_view2_bwd(View2BwdArgs a) {
                 if (__ballot(m != 0.f) == 0ull) {
                     float* o1 = a.dS1 + ((size_t)tile * V + v) * DS1 * 64 + lane;
 #pragma unroll
-                    for (int j = 0; j < 17; ++j) o1[j * 64] = 0.f;
+                    for (int j = 0; j < 17; ++j) o1[j * 64] = 0.f;              // (entry 17, d gate, is k_hoist_bwd's: it stores it for every pair)
                     continue;
                 }
             }

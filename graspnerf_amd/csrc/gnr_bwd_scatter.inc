@@ -20,6 +20,9 @@
 //                                        or 4 x 64 atomic dwords per (bin, chunk)
 //
 // Atomic dwords per volume launch: 786 M -> ~40 M.  The rows cross HBM once each way (0.79 GB written, read once).
+// Range guard: on a flagged pass the view kernel returns before it parks anything -- key / wts / rows then hold whatever the workspace
+// held -- so the four kernels below take its BwdGuard and return at the same place: nothing is placed, nothing is gathered.
+// Tests: tests/test_feature_scatter.py runs the stage alone (gnr_debug_feature_scatter) against a float64 and an integer model.
 // Float mode: the order inside a bin follows the cursor atomics, so the low bits vary from run to run exactly as the direct float
 // scatter's did.  Bit-reproducible mode (GNR_OPT_FEATURE_GRAD_FIXED): the same rows, summed as 64-bit integers (k_scatter_gather<true>).
 namespace gnr {
@@ -37,8 +40,9 @@ struct ScatterBins {             // device buffers of one launch (carved from th
 };
 
 // one workgroup per scene-view: cursor[bin] = seg * cap + (rows in the bins before it)
-__global__ __launch_bounds__(1024) void k_scatter_scan(const int* __restrict__ cnt, int* __restrict__ cursor, int* __restrict__ nseg, int npix, int cap) {
+__global__ __launch_bounds__(1024) void k_scatter_scan(const int* __restrict__ cnt, int* __restrict__ cursor, int* __restrict__ nseg, int npix, int cap, BwdGuard guard) {
     __shared__ int wsum[16];
+    if (bwd_guard_skip(guard)) return;
     const int seg = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int per = (npix + 1023) / 1024;
     const int lo = min(t * per, npix), hi = min(lo + per, npix);
@@ -62,7 +66,8 @@ __global__ __launch_bounds__(1024) void k_scatter_scan(const int* __restrict__ c
 // whose cursors do not fit the LDS: returning atomics on one address serialise at the memory side (~0.5 us each across XCDs), and a
 // pixel that collects a few hundred rows holds the whole launch up (0.166 ms per 8-scene volume launch, whatever the aggregation
 // inside a wavefront).
-__global__ __launch_bounds__(256) void k_scatter_fill(const int* __restrict__ key, int* __restrict__ cursor, int* __restrict__ list, int n) {
+__global__ __launch_bounds__(256) void k_scatter_fill(const int* __restrict__ key, int* __restrict__ cursor, int* __restrict__ list, int n, BwdGuard guard) {
+    if (bwd_guard_skip(guard)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int k = key[i];
@@ -73,9 +78,10 @@ __global__ __launch_bounds__(256) void k_scatter_fill(const int* __restrict__ ke
 // takes its place with an LDS atomic (ds_add_rtn: no trip to the memory side, no cross-XCD serialisation).  The rows of scene b,
 // view v are the 16-row groups (tile * V + v) of the scene's tiles.  Dynamic LDS: npix ints.
 __global__ __launch_bounds__(1024) void k_scatter_place(const int* __restrict__ cnt, const int* __restrict__ key, int* __restrict__ list, int* __restrict__ nseg,
-                                                        int npix, int cap, int V) {
+                                                        int npix, int cap, int V, BwdGuard guard) {
     extern __shared__ int cur[];
     __shared__ int wsum[16];
+    if (bwd_guard_skip(guard)) return;
     const int seg = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int per = (npix + 1023) / 1024;
     const int lo = min(t * per, npix), hi = min(lo + per, npix);
@@ -111,11 +117,29 @@ __global__ __launch_bounds__(1024) void k_scatter_place(const int* __restrict__ 
     }
 }
 
+// Test tooling (gnr_debug_feature_scatter): what the view kernel does for the bins of caller-given rows.  key_in -> key with every
+// key outside its own row's scene-view range [seg * npix, (seg + 1) * npix) turned into -1 (counted in *neutralised: nothing behind
+// this kernel can then leave cnt / cursor / list / the LDS cursors), the live rows counted into their bins, and the bits of the
+// upstream maximum put where the fixed-point kernels look for them.  Row i = ((b * tps + tile) * V + v) * 16 + point.
+__global__ __launch_bounds__(256) void k_scatter_debug_keys(const int* __restrict__ key_in, int* __restrict__ key, int* __restrict__ cnt,
+                                                            unsigned* __restrict__ neutralised, unsigned* __restrict__ upmax, unsigned upmax_bits,
+                                                            int n, int V, int tps, int npix) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0 && upmax) upmax[0] = upmax_bits;
+    if (i >= n) return;
+    const int pair = i >> 4, v = pair % V, b = (pair / V) / tps, seg = b * V + v;
+    int k = key_in[i];
+    if (k != -1 && (k < seg * npix || k >= (seg + 1) * npix)) { k = -1; atomicAdd(neutralised, 1u); }
+    key[i] = k;
+    if (k >= 0) atomicAdd(&cnt[k], 1);
+}
+
 struct ScatterGatherArgs {
     ScatterBins sc;
     float* dfeat64;              // [B * V][npix][64]  (FX: 64-bit entries)
     int nsegs, cap, npix, fh, fw;
     FeatFx fx;                   // FX instantiation only
+    BwdGuard guard;              // the guard of the view kernel that parked the rows
 };
 
 // position of a value in a parked row -> channel of the channel-last feature-map gradient: the compute wavefront's lane (point r, group g)
@@ -165,6 +189,7 @@ DEV void scatter_flush(float* __restrict__ dfeat, int key, int seg, int npix, in
 template <bool FX>
 __global__ __launch_bounds__(256) void k_scatter_gather(ScatterGatherArgs a) {
     using T = std::conditional_t<FX, double, float>;
+    if (bwd_guard_skip(a.guard)) return;
     const int lane = threadIdx.x & 63;
     const int chunk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     const int cps = (a.cap + 63) >> 6;

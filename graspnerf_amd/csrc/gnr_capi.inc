@@ -295,18 +295,23 @@ static ScatterBins scatter_bins(const GnrScene* s, size_t T, char* base) {
     return ScatterBins{(float*)(base + c.rows), (f4*)(base + c.wts), (int*)(base + c.key), (int*)(base + c.cnt), (int*)(base + c.cursor),
                        (int*)(base + c.list), (int*)(base + c.nseg)};
 }
-// the launches behind k_view1_bwd_pw when it parked its rows: places of the bins, row ids into them, sums per pixel
-static int launch_scatter_bins(const GnrScene* s, const ScatterBins& sc, float* dfeat64, int ntiles, const BwdEntry& e, bool fixed, const FeatFx& fx, hipStream_t st) {
+// the launches behind k_view1_bwd_pw when it parked its rows: places of the bins, row ids into them, sums per pixel.
+// guard: the view kernel's -- on a range-flagged pass that kernel parked nothing (no key, no weight, no row), and these return at once too.
+// path: SCATTER_PATH_AUTO = by the feature map's size; the other two are gnr_debug_feature_scatter's (a 3 x 3 map through scan + fill).
+constexpr size_t PLACE_LDS = 150 * 1024;                       // k_scatter_place counts a scene-view's pixels in LDS
+enum { SCATTER_PATH_AUTO = 0, SCATTER_PATH_PLACE = 1, SCATTER_PATH_SCAN_FILL = 2 };
+static int launch_scatter_bins(const GnrScene* s, const ScatterBins& sc, float* dfeat64, int ntiles, const BwdEntry& e, bool fixed, const FeatFx& fx,
+                               const BwdGuard& guard, hipStream_t st, int path = SCATTER_PATH_AUTO) {
     const int BV = s->B * s->V, npix = s->fh * s->fw, cap = (ntiles / s->B) * 16, N = ntiles * s->V * 16;
-    constexpr size_t PLACE_LDS = 150 * 1024;                   // k_scatter_place counts a scene-view's pixels in LDS
-    if ((size_t)npix * sizeof(int) <= PLACE_LDS) {
+    if (path == SCATTER_PATH_AUTO) path = (size_t)npix * sizeof(int) <= PLACE_LDS ? SCATTER_PATH_PLACE : SCATTER_PATH_SCAN_FILL;
+    if (path == SCATTER_PATH_PLACE) {
         if (int rc = launch<k_scatter_place, PLACE_LDS>(e.scatter_place, st, dim3(BV), dim3(1024), (size_t)npix * sizeof(int), (const int*)sc.cnt,
-                                                        (const int*)sc.key, sc.list, sc.nseg, npix, cap, s->V)) return rc;
+                                                        (const int*)sc.key, sc.list, sc.nseg, npix, cap, s->V, guard)) return rc;
     } else {
-        if (int rc = launch<k_scatter_scan>(e.scatter_scan, st, dim3(BV), dim3(1024), 0, (const int*)sc.cnt, sc.cursor, sc.nseg, npix, cap)) return rc;
-        if (int rc = launch<k_scatter_fill>(e.scatter_fill, st, dim3((N + 255) / 256), dim3(256), 0, (const int*)sc.key, sc.cursor, sc.list, N)) return rc;
+        if (int rc = launch<k_scatter_scan>(e.scatter_scan, st, dim3(BV), dim3(1024), 0, (const int*)sc.cnt, sc.cursor, sc.nseg, npix, cap, guard)) return rc;
+        if (int rc = launch<k_scatter_fill>(e.scatter_fill, st, dim3((N + 255) / 256), dim3(256), 0, (const int*)sc.key, sc.cursor, sc.list, N, guard)) return rc;
     }
-    ScatterGatherArgs g{sc, dfeat64, BV, cap, npix, s->fh, s->fw, fx};
+    ScatterGatherArgs g{sc, dfeat64, BV, cap, npix, s->fh, s->fw, fx, guard};
     const int chunks = BV * ((cap + 63) / 64);
     return fixed ? launch<k_scatter_gather<true>>(e.scatter_gather, st, dim3((chunks + 3) / 4), dim3(256), 0, g)
                  : launch<k_scatter_gather<false>>(e.scatter_gather, st, dim3((chunks + 3) / 4), dim3(256), 0, g);
@@ -343,8 +348,9 @@ static int launch_view1_bwd(const GnrScene* s, const Workspace& w, const BwdEntr
         else if (s->use_vis) rc = launch_view1_single<true, true>(e.view1, a, fixed, blocks, st);
         else rc = launch_view1_single<false, true>(e.view1, a, fixed, blocks, st);
         if (rc) return rc;
-        if (bins)                                               // (a flagged pass parked nothing: the bins are empty, the twin below scatters directly)
-            if (int rc2 = launch_scatter_bins(s, a.sc, a.dfeat64, ntiles, e, fixed, a.fx, st)) return rc2;
+        if (bins)                                               // (a flagged pass parked nothing -- cnt is cleared, key / wts / rows hold whatever was there:
+                                                                //  the scatter kernels return under the same guard, the twin below scatters directly)
+            if (int rc2 = launch_scatter_bins(s, a.sc, a.dfeat64, ntiles, e, fixed, a.fx, a.guard, st)) return rc2;
         a.sc = ScatterBins{};
     }
     a.guard = bwd_guard(s, w, e, f32 ? 0 : 2);
@@ -1128,6 +1134,91 @@ extern "C" int gnr_render_chain_bwd(const GnrScene* s, int rn, int dn, const flo
         })) return rc;
     const BwdWs b{sec(t.desc), sec(t.save1), sec(t.saveG), sec(t.dS2), sec(t.dG), sec(t.dS1), sec(t.dpart), tb + t.dfeat64, tb + t.scatter};
     return chain_bwd(s, w, BWD_RENDER, b, wl, wb, P, 15, d_canonical, d_ray_feats, d_img_feats, st);
+}
+
+// ---- test tooling of the binned scatter (include/gnr.h) -----------------------------------------------------
+// byte offsets of {rows, wts, key, cnt, cursor, list, nseg} of the binned scatter inside a training workspace + the number of rows:
+// dn == 0: the volume's (gnr_sample_volume_train_workspace_bytes(scene, n)), else a render pass's (rn = n rays x dn samples)
+extern "C" int gnr_scatter_workspace_layout(const GnrScene* s, int n, int dn, size_t* out8) {
+    if (int rc = check_scene(s)) return rc;
+    if (!out8) return fail(GNR_ERR_ARG, "gnr_scatter_workspace_layout: null pointer");
+    size_t base, T;
+    if (dn == 0) {
+        if (n < 2 || n > MAX_DN) return fail(GNR_ERR_SHAPE, "volume_res must be in 2..64");
+        base = carve_train(s, n).scatter;
+        T = (size_t)s->B * (((size_t)n * n * n + 15) / 16);
+    } else {
+        if (n < 1 || dn < 3 || dn > MAX_DN_FWD) return fail(GNR_ERR_SHAPE, "gnr_scatter_workspace_layout: rn >= 1, dn in 3..128");
+        base = carve_render_train(s, n, dn).scatter;
+        T = (size_t)s->B * (((size_t)n * dn + 15) / 16);
+    }
+    const ScatterWs c = carve_scatter(s, T);
+    const size_t v[8] = {base + c.rows, base + c.wts, base + c.key, base + c.cnt, base + c.cursor, base + c.list, base + c.nseg, T * s->V * 16};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    return GNR_OK;
+}
+
+// the stage alone on caller-given rows: its scratch = the sanitised keys, cnt, cursor, list, nseg
+struct DebugScatterWs { size_t key, cnt, cursor, list, nseg, total; };
+static bool debug_scatter_shape_ok(int B, int V, int fh, int fw, int tps) {
+    if (B < 1 || V < 1 || fh < 1 || fw < 1 || tps < 1) return false;
+    const unsigned long long bins = (unsigned long long)B * V * fh * fw, rows = (unsigned long long)B * tps * V * 16;
+    return bins < (1ull << 26) && rows < (1ull << 26) && (unsigned long long)fh * fw < (1ull << 24);      // (keys, row ids and 64 x either as ints / size_t)
+}
+static DebugScatterWs carve_debug_scatter(int B, int V, int fh, int fw, int tps) {
+    DebugScatterWs c;
+    const size_t N = (size_t)B * tps * V * 16, bins = (size_t)B * V * fh * fw;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
+    c.key = take(N * sizeof(int));
+    c.cnt = take(bins * sizeof(int));
+    c.cursor = take(bins * sizeof(int));
+    c.list = take(N * sizeof(int));
+    c.nseg = take((size_t)B * V * sizeof(int));
+    c.total = off;
+    return c;
+}
+extern "C" size_t gnr_debug_feature_scatter_bytes(int B, int V, int fh, int fw, int tiles_per_scene, size_t* raw_bytes) {
+    if (!debug_scatter_shape_ok(B, V, fh, fw, tiles_per_scene)) return 0;
+    if (raw_bytes) *raw_bytes = al256((size_t)B * V * fh * fw * 64 * 8) + 256;
+    return carve_debug_scatter(B, V, fh, fw, tiles_per_scene).total;
+}
+static const BwdEntry BWD_DEBUG_SCATTER = {
+    false, 0, -1, {}, nullptr, nullptr, nullptr, nullptr,
+    "k_scatter_place@gnr_debug_feature_scatter", "k_scatter_scan@gnr_debug_feature_scatter", "k_scatter_fill@gnr_debug_feature_scatter",
+    "k_scatter_gather@gnr_debug_feature_scatter", "k_unpack_feat_grad@gnr_debug_feature_scatter", nullptr};
+extern "C" int gnr_debug_feature_scatter(int B, int V, int fh, int fw, int tiles_per_scene, const float* rows, const float* wts, const int* key,
+                                         unsigned upmax_bits, int fixed, int path, float* d_ray_feats, float* d_img_feats, void* raw,
+                                         size_t raw_bytes, void* scratch, size_t scratch_bytes, unsigned* status_out2, void* stream) {
+    if (!rows || !wts || !key || !raw || !scratch || !status_out2) return fail(GNR_ERR_ARG, "gnr_debug_feature_scatter: null pointer");
+    if (!debug_scatter_shape_ok(B, V, fh, fw, tiles_per_scene)) return fail(GNR_ERR_SHAPE, "gnr_debug_feature_scatter: B, V, fh, fw, tiles >= 1; B*V*fh*fw and the rows below 2^26");
+    if (path != SCATTER_PATH_AUTO && path != SCATTER_PATH_PLACE && path != SCATTER_PATH_SCAN_FILL) return fail(GNR_ERR_ARG, "gnr_debug_feature_scatter: path is 0 (by size), 1 (LDS placement) or 2 (scan + fill)");
+    const size_t npix = (size_t)fh * fw;
+    if (path == SCATTER_PATH_PLACE && npix * sizeof(int) > PLACE_LDS) return fail(GNR_ERR_SHAPE, "gnr_debug_feature_scatter: the LDS placement holds at most 38400 pixels");
+    const DebugScatterWs c = carve_debug_scatter(B, V, fh, fw, tiles_per_scene);
+    const size_t need_raw = al256((size_t)B * V * npix * 64 * 8) + 256;
+    if (scratch_bytes < c.total || raw_bytes < need_raw) return fail(GNR_ERR_WORKSPACE, "gnr_debug_feature_scatter: scratch or raw buffer too small");
+    hipStream_t st = (hipStream_t)stream;
+    GnrScene s;
+    memset(&s, 0, sizeof(s));
+    s.B = B; s.V = V; s.fh = fh; s.fw = fw;
+    char* sb = (char*)scratch;
+    unsigned* status = status_out2;                               // device: [0] bit 3 (a clamped contribution), [1] keys neutralised
+    unsigned* upmax = (unsigned*)((char*)raw + al256((size_t)B * V * npix * 64 * 8));
+    const int ntiles = B * tiles_per_scene, N = ntiles * V * 16;
+    ScatterBins sc{const_cast<float*>(rows), reinterpret_cast<f4*>(const_cast<float*>(wts)), (int*)(sb + c.key), (int*)(sb + c.cnt),
+                   (int*)(sb + c.cursor), (int*)(sb + c.list), (int*)(sb + c.nseg), fixed ? upmax : nullptr};
+    GNR_HIP(hipMemsetAsync(sc.cnt, 0, (size_t)B * V * npix * sizeof(int), st));
+    GNR_HIP(hipMemsetAsync(status, 0, 2 * sizeof(unsigned), st));
+    GNR_HIP(hipMemsetAsync(raw, 0, fixed ? need_raw : (size_t)B * V * npix * 64 * sizeof(float), st));      // (as feat_grad_begin clears it)
+    if (int rc = launch<k_scatter_debug_keys>("k_scatter_debug_keys@gnr_debug_feature_scatter", st, dim3((N + 255) / 256), dim3(256), 0, key, sc.key, sc.cnt,
+                                              status + 1, fixed ? upmax : (unsigned*)nullptr, upmax_bits, N, V, tiles_per_scene, (int)npix)) return rc;
+    const FeatGradBuf fg{(float*)raw, FeatFx{upmax, status}, fixed != 0};
+    const BwdGuard always{nullptr, nullptr, nullptr, 0, nullptr, 0};
+    if (int rc = launch_scatter_bins(&s, sc, fg.buf, ntiles, BWD_DEBUG_SCATTER, fg.fixed, fg.fx, always, st, path)) return rc;
+    if (d_ray_feats || d_img_feats)
+        if (int rc = feat_grad_unpack(&s, fg, d_ray_feats, d_img_feats, BWD_DEBUG_SCATTER.unpack, st)) return rc;
+    return GNR_OK;
 }
 
 // Forward of the per-ray tail + NeuS alpha + compositing of a training render pass: k_ray<true> on the records the chain of

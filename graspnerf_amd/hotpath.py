@@ -313,6 +313,53 @@ class HotPath:
         _lib.check(self.L.gnr_debug_sample_order(keys.data_ptr(), B, P, perm.data_ptr(), self._stream()), 'gnr_debug_sample_order')
         return perm
 
+    SCATTER_SECTIONS = ('rows', 'wts', 'key', 'cnt', 'cursor', 'list', 'nseg')
+
+    def scatter_ws_sections(self, scene, tws, n, dn=0):
+        """The binned scatter's buffers inside the training workspace `tws` (tests; gnr_scatter_workspace_layout): dn == 0 the volume's
+        at resolution n, else a render pass's of n rays x dn samples -> {rows [N, 64] float32, wts [N, 4] float32, key [N] int32,
+        cnt / cursor [B*V*fh*fw] int32, list [N] int32, nseg [B*V] int32} as device views."""
+        off = (C.c_size_t * 8)()
+        _lib.check(self.L.gnr_scatter_workspace_layout(self._sc(scene), n, dn, off), 'gnr_scatter_workspace_layout')
+        N, BV = int(off[7]), scene.B * scene.V
+        bins = BV * scene.fh * scene.fw
+        count = {'rows': N * 64, 'wts': N * 4, 'key': N, 'cnt': bins, 'cursor': bins, 'list': N, 'nseg': BV}
+        out = {}
+        for i, name in enumerate(self.SCATTER_SECTIONS):
+            sec = tws[off[i]:off[i] + 4 * count[name]]
+            out[name] = sec.view(torch.float32 if name in ('rows', 'wts') else torch.int32)
+        out['rows'], out['wts'] = out['rows'].view(N, 64), out['wts'].view(N, 4)
+        return out
+
+    def debug_feature_scatter(self, B, V, fh, fw, tiles_per_scene, rows, wts, key, upmax=0.0, fixed=False, path=0):
+        """The binned scatter stage alone (gnr_debug_feature_scatter): rows [N, 64], wts [N, 4] float32, key [N] int32 with
+        N = B * tiles_per_scene * V * 16; path 0 = as a backward would choose, 1 = LDS placement, 2 = scan + fill; fixed: the fixed-point
+        mode with the upstream maximum `upmax` -> (d_ray_feats, d_img_feats [B, V, 32, fh, fw], raw channel-last buffer [B*V, fh*fw, 64]
+        float32 or int64, status bits, number of keys the entry took as -1).  Synchronises (it reads the status words)."""
+        N = B * tiles_per_scene * V * 16
+        rows = rows.to(device=self.device, dtype=torch.float32).contiguous()
+        wts = wts.to(device=self.device, dtype=torch.float32).contiguous()
+        key = key.to(device=self.device, dtype=torch.int32).contiguous()
+        assert rows.shape == (N, 64) and wts.shape == (N, 4) and key.shape == (N,)
+        raw_bytes = C.c_size_t(0)
+        need = self.L.gnr_debug_feature_scatter_bytes(B, V, fh, fw, tiles_per_scene, C.byref(raw_bytes))
+        if need == 0:
+            raise _lib.GnrError('gnr_debug_feature_scatter_bytes: shape refused')
+        scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        raw = torch.empty(raw_bytes.value, dtype=torch.uint8, device=self.device)
+        status = torch.empty(2, dtype=torch.int32, device=self.device)
+        dray = torch.empty(B, V, 32, fh, fw, dtype=torch.float32, device=self.device)
+        dimg = torch.empty(B, V, 32, fh, fw, dtype=torch.float32, device=self.device)
+        bits = int(np.float32(upmax).view(np.uint32))
+        _lib.check(self.L.gnr_debug_feature_scatter(B, V, fh, fw, tiles_per_scene, rows.data_ptr(), wts.data_ptr(), key.data_ptr(), bits,
+                                                    1 if fixed else 0, path, dray.data_ptr(), dimg.data_ptr(), raw.data_ptr(), raw.numel(),
+                                                    scratch.data_ptr(), scratch.numel(), status.data_ptr(), self._stream()),
+                   'gnr_debug_feature_scatter')
+        nfeat = B * V * fh * fw * 64
+        chan_last = raw[:nfeat * 8].view(torch.int64) if fixed else raw[:nfeat * 4].view(torch.float32)
+        st = status.cpu()
+        return dray, dimg, chan_last.view(B * V, fh * fw, 64), int(st[0]), int(st[1])
+
     def merge_depths(self, a, b):
         """sort(cat([a, b], -1), -1) of two per-ray ascending depth lists [..., na], [..., nb] on the device (gnr_merge_depths;
         renderer.py:145-146, fine_depth_use_all under training)."""

@@ -478,6 +478,30 @@ int gnr_sample_volume_bwd(const GnrScene* scene, int volume_res, const float* le
                           float* d_img_feats, void* workspace, size_t workspace_bytes, void* train_workspace,
                           size_t train_workspace_bytes, int stages, void* stream);
 
+/* Test tooling of the binned scatter (csrc/gnr_bwd_scatter.inc), in the style of gnr_debug_sample_order.
+ * gnr_scatter_workspace_layout: byte offsets of the stage's buffers {rows, wts, key, cnt, cursor, list, nseg} inside a training
+ *   workspace and, as the eighth entry, its number of rows N -- dn == 0: the volume's workspace at volume_res = n
+ *   (gnr_sample_volume_train_workspace_bytes), else the workspace of a render pass of n rays x dn samples
+ *   (gnr_render_chain_train_workspace_bytes).
+ * gnr_debug_feature_scatter: the stage alone on caller-given device arrays rows [N][64], wts [N][4] (w00 w01 w10 w11), key [N]
+ *   (N = B * tiles_per_scene * V * 16, row id = ((b * tiles_per_scene + tile) * V + v) * 16 + point; key = (b * V + v) * fh * fw +
+ *   top-left tap pixel, or -1 for a dead row).  It clears the bin counts, counts the live keys (what the view kernel's atomics do
+ *   in a backward), clears `raw` and then makes exactly a backward's launches: placement, k_scatter_gather, k_unpack_feat_grad.
+ *   fixed != 0: the fixed-point mode with upmax_bits = the bits of the launch's largest upstream gradient.  path: 0 = the
+ *   placement a backward takes at this feature-map size, 1 = the LDS placement (at most 38 400 pixels), 2 = k_scatter_scan +
+ *   k_scatter_fill.  A key outside its own row's scene-view range [(b * V + v) * fh * fw, + fh * fw) is taken as -1 before
+ *   anything consumes it, so no input indexes out of range; the taps of a row in the last column / row are the caller's to zero
+ *   (the stage skips them there whatever their weight).
+ *   Outputs: d_ray_feats / d_img_feats [B,V,32,fh,fw] (each nullable); raw = the channel-last buffer [B*V][fh*fw][64] (floats, or
+ *   64-bit multiples of the quantum) of raw_bytes; status_out2 (device, two words): [0] = status bits (bit 3: a clamped
+ *   contribution), [1] = the number of keys taken as -1.  gnr_debug_feature_scatter_bytes -> the bytes of `scratch` (and of `raw`);
+ *   0 for a refused shape. */
+int gnr_scatter_workspace_layout(const GnrScene* scene, int n, int dn, size_t* offsets_out8);
+size_t gnr_debug_feature_scatter_bytes(int B, int V, int fh, int fw, int tiles_per_scene, size_t* raw_bytes);
+int gnr_debug_feature_scatter(int B, int V, int fh, int fw, int tiles_per_scene, const float* rows, const float* wts, const int* key,
+                              unsigned upmax_bits, int fixed, int path, float* d_ray_feats, float* d_img_feats, void* raw, size_t raw_bytes,
+                              void* scratch, size_t scratch_bytes, unsigned* status_out2, void* stream);
+
 /* Render path for training: the per-view chain of one render pass in both directions; the per-ray tail (renderer.py:90-108,
  * ibrnet.py:485-504) and NeuS alpha / compositing have their own twin pairs below; the ray geometry (S1-S3), the inverse-CDF
  * resampling and the sort (F1/F2) run in the forward kernels.  PyTorch autograd only connects the pairs with the losses.

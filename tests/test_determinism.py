@@ -318,7 +318,10 @@ def _fill_allocations(monkeypatch, byte):
 def test_nothing_reads_memory_it_did_not_write(weights_np, monkeypatch):
     """The forward (volume + both render passes with their debug outputs) and a training render pass with its backward on freshly
     allocated workspaces / outputs / scratch filled with 0x00 and with 0xff bytes (NaNs): the same bits, everything finite -- no kernel
-    reads a workspace region, a partial slot or an output array before something wrote it."""
+    reads a workspace region, a partial slot or an output array before something wrote it.  Then a render pass's backward on a scene
+    with a view that sees nothing (skipped (tile, view) pairs), fills 0x00 / 0xff / 0x71, under the binned, the direct, the one-wavefront
+    and the fp32 scatter paths: the same bits per path whatever the fill (the fixed-point quantum depends on nothing unwritten), binned,
+    direct and one-wavefront the same bits, the fp32 chain (other arithmetic) within 2e-3 of the binned one."""
     from graspnerf_amd.hotpath import HotPath, batch_scenes
     prev = HotPath.default_options
     HotPath.default_options = prev | _lib.OPTIONS['feature_grad_fixed']
@@ -356,5 +359,54 @@ def test_nothing_reads_memory_it_did_not_write(weights_np, monkeypatch):
             if v.dtype.is_floating_point:
                 assert bool(torch.isfinite(v).all()), k
             assert torch.equal(v, b[k]), k
+
+        # A second scene whose fourth view sees nothing (its principal point lies 10 000 pixels outside the image): on the ray points
+        # every (tile, view) pair of that view is skipped by the render pass's backward kernels (GNR_BWD_SKIP_MASKED).  Every path but
+        # the binned one takes the fixed-point quantum from a maximum over the WHOLE dS1 buffer, skipped pairs included: with the
+        # allocations filled with 0x71 bytes (floats of 1.19e30) an entry nobody stored would move the quantum by a hundred binades.
+        scenes4 = [make_scene(80 + i, dict(CONFIGS['cfg1'], V=4, rn=rn)) for i in range(B)]
+        for ref4, _ in scenes4:
+            ref4['Ks'][3, 0, 2] = ref4['Ks'][3, 1, 2] = -1.0e4
+        bref4, bque4 = batch_scenes(scenes4)
+        options = (None, 'direct_scatter', 'view1_one_wavefront', 'fp32_chain')
+
+        def run4(byte):
+            _fill_allocations(monkeypatch, byte)
+            out = {}
+            for o in options:
+                hp = _hot(weights_np)                                  # its own, freshly allocated workspaces
+                if o:
+                    hp.set_option(o, True)
+                prep = hp.prepare(bref4, 1, rn, dn)
+                bq = {k: torch.from_numpy(v).cuda() for k, v in bque4.items() if k != 'imgs'}
+                depth = torch.from_numpy(depth_np).cuda()
+                _, _, _, ctx = hp.render_chain_train(bq, depth, 'fine', cfg, prep)
+                _, dray, dimg = hp.render_chain_bwd(ctx, torch.from_numpy(up['ds']).cuda(), torch.from_numpy(up['dc']).cuda())
+                torch.cuda.synchronize()
+                assert hp.range_status(prep) & 15 == 0
+                out[o] = (dray.clone(), dimg.clone())
+                if o is None:
+                    vm = hp.render_by_depth(bref4, bque4, depth, 'fine', cfg, debug=True, prepared=prep)['view_mask']
+                    assert int((vm >> 3).max()) == 0 and int(vm.max()) > 0      # the fourth view's mask bit is never set on the ray points
+            return out
+        runs = {byte: run4(byte) for byte in (0x00, 0xff, 0x71)}
+        for o in options:
+            for i, name in enumerate(('d_ray_feats', 'd_img_feats')):
+                v = runs[0x00][o][i]
+                assert bool(torch.isfinite(v).all()) and float(v.abs().max()) > 0, (o, name)
+                for byte in (0xff, 0x71):
+                    assert torch.equal(v, runs[byte][o][i]), (o, name, hex(byte), float((v - runs[byte][o][i]).abs().max()), float(v.abs().max()))
+                base = runs[0x00][None][i]
+                print(f'{o} {name}: max|d| to the binned scatter {float((v - base).abs().max()):.3e} of {float(base.abs().max()):.3e}')
+                if o in ('direct_scatter', 'view1_one_wavefront'):
+                    # the same rows -- out of the same kernel, or out of k_view1_bwd, whose dX chain the partner kernel's compute
+                    # wavefront runs instruction for instruction (gnr_bwd_view1_pw.inc) -- rounded once each to the same quantum and
+                    # summed as integers: the same bits, whether the maximum was taken over the visited pairs or over all of dS1
+                    assert torch.equal(v, base), (o, name, float((v - base).abs().max()))
+                elif o:
+                    # the fp32 chain computes the rows with other arithmetic and cannot agree bitwise with the fp16 pairs
+                    # (tests/test_backward_guard.py asserts that it does not): within that test's own 2e-3 of the maximum.
+                    # A quantum moved by a stale 1.19e30 would round every contribution to zero.
+                    assert float((v - base).abs().max()) <= 2e-3 * float(base.abs().max()) + 1e-9, (o, name)
     finally:
         HotPath.default_options = prev
