@@ -719,9 +719,6 @@ struct GeoBwdArgs {
 constexpr int TS2 = 112;      // LDS tile row stride for up to 96 columns (4 k-groups on disjoint banks)
 // inter-stage gradient record of a (tile, view) between stages 3 / 2 / 1: d X[9] (stage 3: per-view columns of base_fc.0; stage 2
 // adds the part through the cross-view statistics), d e[8] (stage 3), d gate (stage 2)
-#ifndef GNR_BWD_SKIP_MASKED
-#define GNR_BWD_SKIP_MASKED 1
-#endif
 constexpr int DS1 = 18;
 
 // acc[bi * NBJ + bj] += dY-block bi (x) X-block bj over the tile's 16 points
@@ -1019,9 +1016,7 @@ struct View2BwdArgs {
     BwdGuard guard;
 };
 
-#ifndef GNR_BWD_PAIRS
-#define GNR_BWD_PAIRS 1       // forward recompute + dX chains of k_view2_bwd / k_view1_bwd on the f16 matrix cores (fp16 pairs); 0: fp32-input MFMA (rounds 1-4)
-#endif
+// BP (k_view2_bwd / k_view1_bwd): forward recompute + dX chains on the f16 matrix cores (fp16 pairs); false: fp32-input MFMA (rounds 1-4)
 namespace l3 {                // LDS image of k_view2_bwd (floats)
 constexpr int FW = 0, BASE1 = 0, BASE2 = frag_floats(17, 4), VIS1 = BASE2 + frag_floats(16, 2), VIS2 = VIS1 + 1024, VISB1 = VIS2 + 1024;
 constexpr int BI = VISB1 + 1024, TB = BI + 128, SC = TB + 64, BW = SC + 4;
@@ -1043,7 +1038,7 @@ constexpr int TOTAL_RENDER = T_RGB0V + 16;
 // fallback for both passes, GNR_OPT_FP32_CHAIN).  Pairs on the volume points only: the render instantiation (colour head: 4 more
 // accumulator blocks, a second projection) sits at the 256-arch-register limit in the fp32 form already (32 B of scratch); with the
 // pair operands it spills 576 B and runs 1.70 -> 3.22 ms per step (measured, profiles/r05_d_*), so it keeps the fp32-input MFMA.
-template <bool RENDER, bool BP = (GNR_BWD_PAIRS != 0 && !RENDER)>
+template <bool RENDER, bool BP = !RENDER>
 __global__ __launch_bounds__(256, 1) void k_view2_bwd(View2BwdArgs a) {
     static_assert(!(RENDER && BP), "k_view2_bwd<true> runs on the fp32-input MFMA");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1121,7 +1116,6 @@ __global__ __launch_bounds__(256, 1) void k_view2_bwd(View2BwdArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) E1[j] = s1[(9 + j) * 64];
             const float m = s1[18 * 64];
-#if GNR_BWD_SKIP_MASKED
             if constexpr (RENDER) {                                             // see k_view1_bwd: nothing flows through a view that no sample of the tile sees
                 if (__ballot(m != 0.f) == 0ull) {
                     float* o1 = a.dS1 + ((size_t)tile * V + v) * DS1 * 64 + lane;
@@ -1130,7 +1124,6 @@ __global__ __launch_bounds__(256, 1) void k_view2_bwd(View2BwdArgs a) {
                     continue;
                 }
             }
-#endif
             constexpr int D2W = RENDER ? 10 : 9;
             const float* d2 = a.dS2 + ((size_t)tile * V + v) * D2W * 64 + lane;
 #pragma unroll
@@ -1581,7 +1574,7 @@ constexpr int BW = SC + 4;                                                // bac
 constexpr int DEC2T = BW, DEC1T = DEC2T + 3072, PE2F = DEC1T + 3072, B_PE2 = PE2F + 1024, PE2T = B_PE2 + 32,
               PE0T = PE2T + 1024, T_PE0HV = PE0T + 1024, NR0T = T_PE0HV + 64, RDF2T = NR0T + frag_floats(4, 2);
 constexpr int TILES = RDF2T + frag_floats(9, 1);
-// GNR_BWD_PAIRS: [DEC2T, T_PE0HV) is the blob's pair section pkb::P1_BEGIN .. P1_END (same order, same sizes); T_PE0HV, NR0T, RDF2T
+// BP: [DEC2T, T_PE0HV) is the blob's pair section pkb::P1_BEGIN .. P1_END (same order, same sizes); T_PE0HV, NR0T, RDF2T
 // (short layers: fp32) come from the fp32 section as before
 static_assert(T_PE0HV - BW == pkb::P1_END - pkb::P1_BEGIN && PE2F - BW == pkb::P1_PE2F - pkb::P1_BEGIN && PE0T - BW == pkb::P1_PE0T - pkb::P1_BEGIN, "LDS image = the blob's pair section");
 constexpr int TOTAL = TILES + 4 * 2 * 16 * TS2;
@@ -1593,7 +1586,7 @@ constexpr int TOTAL_VIS = V_DEC1T + 1024;
 static_assert(pk::DEC1 == 0 && pk::B_PE1 == pk::B_DEC1 + 192 && pk::B_NR1 == pk::B_DEC1 + 288 && pk::T_NR2 == pk::T_DEC3 + 168, "layout");
 }
 
-template <bool USEVIS, bool FX = false, bool BP = (GNR_BWD_PAIRS != 0)>      // BP: fp16 pairs / fp32-input MFMA, as for k_view2_bwd
+template <bool USEVIS, bool FX = false, bool BP = true>      // BP: fp16 pairs / fp32-input MFMA, as for k_view2_bwd
 __global__ __launch_bounds__(256, 1) void k_view1_bwd(View1BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (bwd_guard_skip(a.guard)) return;
@@ -1683,12 +1676,10 @@ __global__ __launch_bounds__(256, 1) void k_view1_bwd(View1BwdArgs a) {
             ViewGeom vg;
             project_view<true>(vp, p, qd, a.H, a.W, vg);
             const float m = vg.m;
-#if GNR_BWD_SKIP_MASKED
             // every quantity this view hands to the reductions carries the weight m = 0 (ibrnet.py:466-484; hit, vis, the rgb taps and the
             // bilinear taps are products with m): with no valid sample in the tile all of its gradients are exact zeros -- parameters,
             // feature maps (the scatter skips zero weights anyway) and points alike.  The forward's render instantiations skip the same pairs.
             if (a.skip_masked && __ballot(m != 0.f) == 0ull) continue;
-#endif
             const Taps t = make_taps(vg.u, vg.v, fsx, fsy, -0.5f, a.fh, a.fw);
             const float w00 = t.w00 * m, w01 = t.w01 * m, w10 = t.w10 * m, w11 = t.w11 * m;
             float FR[8];

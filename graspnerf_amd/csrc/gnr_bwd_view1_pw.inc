@@ -20,15 +20,10 @@
 // use_vis levels keep k_view1_bwd<true> (its 59 accumulator blocks do not fit the partner's 256 registers).
 namespace gnr {
 
-#ifndef GNR_PW_ABLATE_D1
-#define GNR_PW_ABLATE_D1 0
-#endif
-#ifndef GNR_PW_OUTER_UNROLL
-#define GNR_PW_OUTER_UNROLL 2      // 4 (every k-step of a stage in flight): 176 - 244 bytes of scratch on the partner; 1 or 2: none, 230 registers
-#endif
 namespace l1p {
 constexpr int NSLOT = 3;                            // ring depth per pair
-constexpr int OUTER_UNROLL = GNR_PW_OUTER_UNROLL;   // k-steps of an outer product in flight (pw_outer)
+constexpr int OUTER_UNROLL = 2;                     // k-steps of an outer product in flight (pw_outer); 4 (every k-step of a stage): 176 - 244 bytes
+                                                    // of scratch on the partner; 1 or 2: none, 230 registers
 constexpr int TSP = 48;                             // tile row stride: the 4 k-groups of an MFMA operand read disjoint banks (48 mod 64)
 constexpr int SLOT = 2 * 16 * TSP;                  // dY tile | X tile (the scatter stage: 16 rows x 64 values | 16 x 8 tap records)
 constexpr int RING = l1::TILES;                     // behind k_view1_bwd's weight image
@@ -129,11 +124,8 @@ enum { PW_STAGE = 0, PW_SKIP = 1 };
 constexpr int W3_ROW0 = 8, NR2_ROW = 13;
 enum { ST1_STAGE = 0, ST1_END = 1 };      // slot kinds: a stage of the pair in flight (the partner knows the order) / the compute wavefront is done
 
-#ifndef GNR_PW_PROBE
-#define GNR_PW_PROBE 0      // register probes (compile only): 1 = the partner role alone, 2 = the compute role alone, at 512 registers
-#endif
 template <bool FX = false, bool BINS = false>      // BINS: the scatter rows are parked for k_scatter_gather (gnr_bwd_scatter.inc; float mode only)
-__global__ __launch_bounds__(512, GNR_PW_PROBE ? 1 : 2) void k_view1_bwd_pw(View1BwdArgs a) {
+__global__ __launch_bounds__(512, 2) void k_view1_bwd_pw(View1BwdArgs a) {
     static_assert(!(FX && BINS), "the binned scatter is the float mode's");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (bwd_guard_skip(a.guard)) return;
@@ -159,8 +151,6 @@ __global__ __launch_bounds__(512, GNR_PW_PROBE ? 1 : 2) void k_view1_bwd_pw(View
     const int V = a.V, tps = (a.P + 15) >> 4;
     if (partner && a.guard.lose_partner) return;                   // GNR_OPT_TEST_LOSE_PARTNER: the compute wavefronts' waits must give up and say so
 
-    if (GNR_PW_PROBE == 2 && partner) return;
-    if (GNR_PW_PROBE == 1 && !partner) return;
     if (partner) {
         // =========================== partner wavefront: weight gradients, bias sums, scatter ===========================
         f4 gWr2[3], gWr1[1], gWnr0[2], gWpe2[4], gWpe0[6], gWd2[3][4], gWd1[3][4];
@@ -197,11 +187,7 @@ __global__ __launch_bounds__(512, GNR_PW_PROBE ? 1 : 2) void k_view1_bwd_pw(View
             for (int br = 0; br < 3; ++br) {
                 s = ring.acquire_full(k); pw_outer<1, 2>(s, lane, gWnr0, bNR0); ring.release();                             // last-layer rows W3_ROW0 + 2 br
                 s = ring.acquire_full(k); pw_outer<2, 2>(s, lane, gWd2[br], bD2[br]); ring.release();
-#if GNR_PW_ABLATE_D1
-                s = ring.acquire_full(k); ring.release();                 // measurement build (wrong gradients): decoder .0 weight gradients dropped
-#else
                 s = ring.acquire_full(k); pw_outer<2, 2>(s, lane, gWd1[br], bD1[br]); ring.release();
-#endif
             }
             // ---- scatter: rows [16][64] = d(ray channels | image-feature channels) of the 16 points, tap records [16][8] = 4 weights
             // (0 where the point is dead) + 4 pixel offsets, the scene-view index behind them; one wavefront instruction adds the 64
@@ -275,12 +261,10 @@ __global__ __launch_bounds__(512, GNR_PW_PROBE ? 1 : 2) void k_view1_bwd_pw(View
             ViewGeom vg;
             project_view<true>(vp, p, qd, a.H, a.W, vg);
             const float m = vg.m;
-#if GNR_BWD_SKIP_MASKED
             if (a.skip_masked && __ballot(m != 0.f) == 0ull) {          // see k_view1_bwd: nothing flows through this (tile, view)
                 if constexpr (BINS) a.sc.key[((size_t)tile * V + v) * 16 + r] = -1;      // binned scatter: 16 dead rows
                 continue;                                                // (nothing is published: the partner follows stage ids, not pairs)
             }
-#endif
             const Taps t = make_taps(vg.u, vg.v, fsx, fsy, -0.5f, a.fh, a.fw);
             const float w00 = t.w00 * m, w01 = t.w01 * m, w10 = t.w10 * m, w11 = t.w11 * m;
             float FR[8];

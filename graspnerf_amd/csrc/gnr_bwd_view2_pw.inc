@@ -9,9 +9,6 @@
 // the single-wavefront kernel lacked (k_view2_bwd<true> spilled 576 B with pair operands and stays on the fp32-input MFMA).
 namespace gnr {
 
-#ifndef GNR_PW2_VOL_UNROLL
-#define GNR_PW2_VOL_UNROLL 4      // volume instantiation: 4 k-steps in flight (1.67 against 1.72 ms per launch, 12 B of prologue scratch); the render instantiation spills 184 B at 4 and keeps 2
-#endif
 namespace l3p {
 constexpr int RGB1 = l3::TILES, RGB2 = RGB1 + frag_floats(10, 1), B_RGB1 = RGB2 + frag_floats(4, 1), B_RGB2 = B_RGB1 + 16, T_RGB3 = B_RGB2 + 16,
               RGB2T = T_RGB3 + 16, RGB0HT = RGB2T + frag_floats(4, 1), T_RGB0V = RGB0HT + frag_floats(4, 2), RGB_END = T_RGB0V + 16;
@@ -27,7 +24,9 @@ __global__ __launch_bounds__(512, 2) void k_view2_bwd_pw(View2BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (bwd_guard_skip(a.guard)) return;
     constexpr int NS = l3p::nslot(RENDER);
-    constexpr int UO = RENDER ? l1p::OUTER_UNROLL : GNR_PW2_VOL_UNROLL;      // k-steps of an outer product in flight (partner side)
+    // k-steps of an outer product in flight (partner side).  Volume instantiation: 4 (1.67 against 1.72 ms per launch, 12 B of prologue scratch);
+    // the render instantiation spills 184 B at 4 and keeps 2
+    constexpr int UO = RENDER ? l1p::OUTER_UNROLL : 4;
     for (int i = threadIdx.x; i < l3::BI; i += 512) lds[i] = a.wpk[pk::C16 + pk::c16_off(pk::BASE1) + i];
     if (threadIdx.x < 128) lds[l3::BI + threadIdx.x] = a.wpk[pk::B_BASE2 + threadIdx.x];
     if (threadIdx.x < 64) lds[l3::TB + threadIdx.x] = a.wpk[pk::T_VIS2R + threadIdx.x];
@@ -152,7 +151,6 @@ __global__ __launch_bounds__(512, 2) void k_view2_bwd_pw(View2BwdArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) E1[j] = s1[(9 + j) * 64];
             const float m = s1[18 * 64];
-#if GNR_BWD_SKIP_MASKED
             if constexpr (RENDER) {                                             // nothing flows through a view that no sample of the tile sees
                 if (__ballot(m != 0.f) == 0ull) {
                     float* o1 = a.dS1 + ((size_t)tile * V + v) * DS1 * 64 + lane;
@@ -161,7 +159,6 @@ __global__ __launch_bounds__(512, 2) void k_view2_bwd_pw(View2BwdArgs a) {
                     continue;                                                   // (nothing is published: the partner follows the stages, not the pairs)
                 }
             }
-#endif
             constexpr int D2W = RENDER ? 10 : 9;
             const float* d2 = a.dS2 + ((size_t)tile * V + v) * D2W * 64 + lane;
 #pragma unroll

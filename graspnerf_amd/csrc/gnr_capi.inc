@@ -152,14 +152,14 @@ static int poison_partials(void* p, size_t bytes, hipStream_t st, unsigned optio
 
 template <int V, bool RENDER, bool SAVE, bool USEVIS, bool SP>
 static int launch_chain_one(const ChainArgs& a, hipStream_t st, const char* label) {
-    constexpr size_t lds_bytes = (size_t)((SP ? pk::C16_END : pk::CHAIN_END) + COOP_TAB_FLOATS) * sizeof(float);
+    constexpr size_t lds_bytes = (size_t)(SP ? pk::C16_END : pk::CHAIN_END) * sizeof(float);
     const int tps = (a.P + 15) / 16;
     const long ntiles = (long)a.B * tps;
-    constexpr int WPB = GNR_CHAIN_THREADS / 64;
+    constexpr int WPB = kChainThreads / 64;
     long blocks = (ntiles + WPB - 1) / WPB;
     const long maxb = num_cus();
     if (blocks > maxb) blocks = maxb;
-    return launch<k_chain<V, RENDER, SAVE, USEVIS, SP>, lds_bytes>(label, st, dim3((unsigned)blocks), dim3(GNR_CHAIN_THREADS), lds_bytes, a);
+    return launch<k_chain<V, RENDER, SAVE, USEVIS, SP>, lds_bytes>(label, st, dim3((unsigned)blocks), dim3(kChainThreads), lds_bytes, a);
 }
 
 // One chain launch of the product = the pair kernel + its fp32-MFMA twin on the same arguments with only_if_flagged set: the
@@ -207,11 +207,8 @@ static void wire_chain(ChainArgs& a, const GnrScene* s, const Workspace& w, int 
 // The backward's view kernels (csrc/gnr_bwd.inc).  Default: the partner-wavefront kernels (gnr_bwd_view{1,2}_pw.inc: same outputs, same
 // slots of the deterministic reduction); GNR_OPT_VIEW{1,2}_ONE_WAVEFRONT: one wavefront per tile; use_vis levels take k_view1_bwd<true>
 // (the fourth decoder branch does not fit the partner's registers).
-#ifndef GNR_VIEW1_PARTNER
-#define GNR_VIEW1_PARTNER 1
-#endif
-static bool view1_partner(const GnrScene* s) { return GNR_VIEW1_PARTNER != 0 && GNR_BWD_PAIRS != 0 && !opt(s, GNR_OPT_VIEW1_ONE_WAVEFRONT) && !opt(s, GNR_OPT_FP32_CHAIN) && !s->use_vis; }
-static bool view2_partner(const GnrScene* s) { return GNR_VIEW1_PARTNER != 0 && GNR_BWD_PAIRS != 0 && !opt(s, GNR_OPT_VIEW2_ONE_WAVEFRONT) && !opt(s, GNR_OPT_FP32_CHAIN); }
+static bool view1_partner(const GnrScene* s) { return !opt(s, GNR_OPT_VIEW1_ONE_WAVEFRONT) && !opt(s, GNR_OPT_FP32_CHAIN) && !s->use_vis; }
+static bool view2_partner(const GnrScene* s) { return !opt(s, GNR_OPT_VIEW2_ONE_WAVEFRONT) && !opt(s, GNR_OPT_FP32_CHAIN); }
 // What tells the two chain backwards (gnr_sample_volume_bwd, gnr_render_chain_bwd) apart in the stages they share (chain_bwd):
 //   slot, slot2: the watch words of the training forwards the backward follows -- the volume's, or the render passes' RS_COARSE_TRAIN and
 //                RS_DEPTHS_TRAIN together (the backward is not told which of them it follows); slot2 < 0: none
@@ -327,10 +324,10 @@ static int launch_view1_single(const char* label, const View1BwdArgs& a, bool fi
     return fixed ? launch<k_view1_bwd<USEVIS, true, BP>, lds>(label, st, dim3(blocks), dim3(256), lds, a)
                  : launch<k_view1_bwd<USEVIS, false, BP>, lds>(label, st, dim3(blocks), dim3(256), lds, a);
 }
-static bool view1_bins(const GnrScene* s) { return view1_partner(s) && !opt(s, GNR_OPT_DIRECT_SCATTER) && !opt(s, GNR_OPT_FP32_CHAIN) && GNR_BWD_PAIRS != 0; }
+static bool view1_bins(const GnrScene* s) { return view1_partner(s) && !opt(s, GNR_OPT_DIRECT_SCATTER) && !opt(s, GNR_OPT_FP32_CHAIN); }
 static int launch_view1_bwd(const GnrScene* s, const Workspace& w, const BwdEntry& e, View1BwdArgs a, bool fixed, int ntiles, char* scatter_region, hipStream_t st) {
     const int blocks = chain_blocks(ntiles);
-    const bool f32 = opt(s, GNR_OPT_FP32_CHAIN) || GNR_BWD_PAIRS == 0;
+    const bool f32 = opt(s, GNR_OPT_FP32_CHAIN);
     const bool pw = view1_partner(s);
     const bool bins = view1_bins(s) && scatter_region;       // (both feature-gradient modes: the rows are parked as floats either way)
     if (!f32) {
@@ -378,16 +375,15 @@ static int launch_ray(RayArgs& a, hipStream_t st) {
     a.slots = a.dn > fdn ? a.dn : fdn;
     int ray_floats = a.dn * ray_per(RENDER);
     if (RENDER && ray_floats < rt::END) ray_floats = rt::END;
-    const int lds_budget = (RENDER && GNR_RAY_BLOCKS >= 3 ? 52 : 78) * 1024;      // three / two workgroups per CU
+    const int lds_budget = (RENDER ? 52 : 78) * 1024;      // three (kRayBlocks) / two workgroups per CU
     const int rpb = pack_rays(ray_floats, a.slots, lds_budget, &a.ray_stride);
     if (rpb < 1) return fail(GNR_ERR_SHAPE, "k_ray: a ray does not fit the LDS budget");
     a.rays_per_block = rpb;
     constexpr size_t MAX_LDS = 80 * 1024;
     const size_t lds_bytes = (size_t)rpb * a.ray_stride * sizeof(float);
     const dim3 grid((unsigned)((a.nrays + rpb - 1) / rpb));
-    constexpr bool MM = GNR_RAY_GEO_MFMA != 0;
-    if (int rc = launch<k_ray<RENDER, MM, VOLG>, MAX_LDS>(VOLG ? "k_ray.render@volume_grad" : RENDER ? "k_ray.render" : "k_ray.volume", st, grid, dim3(256), lds_bytes, a)) return rc;
-    if (RENDER && GNR_RAY_GEO_MFMA != 0 && a.range_word) {
+    if (int rc = launch<k_ray<RENDER, true, VOLG>, MAX_LDS>(VOLG ? "k_ray.render@volume_grad" : RENDER ? "k_ray.render" : "k_ray.volume", st, grid, dim3(256), lds_bytes, a)) return rc;
+    if (RENDER && a.range_word) {
         // the fp32 twin of the matrix-core tail: returns at once unless that launch flagged a non-finite value (range guard, k_ray)
         a.only_if = a.range_word;
         return launch<k_ray<RENDER, false, VOLG>, MAX_LDS>(VOLG ? "k_ray.render.fp32_twin@volume_grad" : "k_ray.render.fp32_twin", st, grid, dim3(256), lds_bytes, a);
@@ -479,7 +475,7 @@ static int volume_impl(const GnrScene* s, const float* bbox_min, int R, const fl
     if (ws_bytes < w.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     const int P = R * R * R;
     // the inference path's chain kernel computes the grid points itself (ChainArgs::pts_R); the per-column kernel never reads them: no k_points_volume
-    const bool inline_pts = GNR_VOLUME_POINTS_INLINE != 0 && chain && ray && !dbg && R * R * R < (1 << 22);
+    const bool inline_pts = chain && ray && !dbg && R * R * R < (1 << 22);
     if (points && !inline_pts)
         if (int rc = launch<k_points_volume>("k_points_volume@volume_impl", st, dim3((s->B * P + 255) / 256), dim3(256), 0, bbox_min, w.desc, R, s->B)) return rc;
     // GNR_OPT_SPLIT_LAUNCH: scenes [0, B/2) on the caller's stream, [B/2, B) on the library's side stream: the second half's chain launch
@@ -587,7 +583,7 @@ static int order_rays(const GnrScene* s, const GnrRays* q, Workspace& w, hipStre
 constexpr int SAMPLE_ORDER_MIN_TILES_PER_SLOT = 8;
 static bool sample_order_wanted(const GnrScene* s, const Workspace& w, int P) {
     if (opt(s, GNR_OPT_SAMPLE_ORDER_NATURAL) || !w.sample_perm || !w.sample_keys || P > MAX_SORT_SAMPLES) return false;
-    const long ntiles = (long)s->B * ((P + 15) / 16), slots = (long)num_cus() * (GNR_CHAIN_THREADS / 64);
+    const long ntiles = (long)s->B * ((P + 15) / 16), slots = (long)num_cus() * (kChainThreads / 64);
     return ntiles >= SAMPLE_ORDER_MIN_TILES_PER_SLOT * slots;
 }
 static int launch_sample_order(const unsigned char* keys, int* perm, int B, int P, hipStream_t st) {
@@ -911,7 +907,7 @@ extern "C" int gnr_sample_volume_fwd_train(const GnrScene* s, const float* bbox_
 template <bool RENDER>
 static int launch_view2_bwd(const GnrScene* s, const Workspace& w, const BwdEntry& e, View2BwdArgs a, int blocks, hipStream_t st) {
     constexpr size_t lds1 = (RENDER ? l3::TOTAL_RENDER : l3::TOTAL) * sizeof(float), ldsp = l3p::total(RENDER) * sizeof(float);
-    const bool f32 = opt(s, GNR_OPT_FP32_CHAIN) || GNR_BWD_PAIRS == 0;
+    const bool f32 = opt(s, GNR_OPT_FP32_CHAIN);
     const bool pw = view2_partner(s);
     const bool single_is_f32 = RENDER && !pw;               // k_view2_bwd<true> has no pair form
     if (!f32 && !single_is_f32) {

@@ -89,10 +89,7 @@ DEV float gsum(float x) {
 // The weight image in LDS is loop-invariant; without a compiler barrier the fragment loads are hoisted out of the
 // view/tile loops (LICM) and hundreds of registers spill.  Every loop iteration starts with GNR_ITER_FENCE();
 // LF (template flag of mm/load_bias) additionally fences every layer: needed for V >= 7 (S[V][20] leaves too few
-// registers for loads pulled across layers), 0.5 % slower for V <= 6.  -DGNR_LICM_FENCE=1 forces it everywhere.
-#ifndef GNR_LICM_FENCE
-#define GNR_LICM_FENCE 0
-#endif
+// registers for loads pulled across layers), 0.5 % slower for V <= 6.
 #define GNR_ITER_FENCE() asm volatile("" ::: "memory")
 
 template <int J, int NB, int J0 = 0, bool LF = true>
@@ -179,12 +176,8 @@ DEV float dot4(const float* __restrict__ T, int g, const float (&h)[4]) {
 #ifndef GNR_SPLIT16
 #define GNR_SPLIT16 1
 #endif
-#ifndef GNR_SPLIT_MM
-#define GNR_SPLIT_MM 0          // 1: also the fourth partial product Wm xm 2^-22 (one more MFMA per block and a multiply per output:
-                                // +10 % kernel time).  OFF: it is <= 2^-22 |w x|, 2^-25 on average, and without it the pair form is still
-                                // closer to fp64 than the fp32 MFMA chain (tools/ubench/split_mfma.hip, 51 200 dot products of K = 32:
-                                // max / rms error relative to sum|w x|  fp32 MFMA 2.0e-7 / 2.4e-8, 4 products 9.9e-8 / 1.8e-8, 3 products 1.2e-7 / 2.1e-8)
-#endif
+// The fourth partial product Wm xm 2^-22 is left out: it is <= 2^-22 |w x| and costs +10 % kernel time; the three-product form is
+// still closer to fp64 than the fp32 MFMA chain (tools/ubench/split_mfma.hip; numbers in docs/lab_notebook.md, "Removed switches").
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 struct P8 { h8 h, m; };
@@ -242,7 +235,7 @@ DEV P8 p8_load(const float* r) {
 }
 DEV f4 mfma32h(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
-// ---- GNR_UNSCALED_ACT: the cheaper pair of an ACTIVATION (inner layers only: operands that are ELU outputs, O(1) vectors).
+// ---- unscaled activation pairs: the cheaper pair of an ACTIVATION (inner layers only: operands that are ELU outputs, O(1) vectors).
 //   x = h + m   with  h = fp16(x),  m = fp16(x - h)  -- the residual UNSCALED, so that both products with the weight's high half
 //   accumulate in the layer's own accumulator:  W x = wh h + wh m + wm (h 2^-11)  (wm = the weight's residual, scaled by 2^11 as
 //   before; its B operand is the high half times 2^-11, exact unless subnormal).  No second accumulator, no fold: a split costs 5
@@ -251,9 +244,6 @@ DEV f4 mfma32h(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16
 //   2^-24: a pre-activation is off by at most 2^-25 sum|w| (1e-7 for these layers) on top of the fp32-like rounding.  Against the
 //   float64 arbiter the path is as close as with scaled residuals (tests/test_range_guard.py::test_fp64_arbiter).  Layers fed by
 //   feature maps or cross-view statistics (any magnitude) keep the scaled form.
-#ifndef GNR_UNSCALED_ACT
-#define GNR_UNSCALED_ACT 1
-#endif
 struct P8U { h8 h, m, s; };
 DEV void split2u(float x0, float x1, h2& h, h2& m, h2& s) {
     const f2 x = {x0, x1};
@@ -290,9 +280,6 @@ DEV P8U split8u(const float (&v)[N]) {
 //  * the gathered features are convex combinations of feature-map values, which k_repack_feats tests once per prepare.
 // A flagged launch sets a bit in GnrWorkspace's range word; the fp32-MFMA instantiation of the same kernel, launched right
 // behind every pair launch, returns at once unless a bit is set and otherwise recomputes the launch (gnr_capi.inc).
-#ifndef GNR_WATCH_LAST
-#define GNR_WATCH_LAST 0
-#endif
 #ifndef GNR_RANGE_GUARD
 #define GNR_RANGE_GUARD 1                     // 0: measurement builds without the watch and without the fp32 twin launches
 #endif
@@ -310,24 +297,13 @@ DEV void range_watch(float& word, const f4& a) {   // a: an output block of a pa
 // 2e-7 ... 2e-5, at one and at two wavefronts per SIMD) -- a dependency the compiler's hazard tables (ROCm 7.2) do not
 // cover; tails are zero-padded into a K32 block instead.
 // WATCH: the B operands are not bounded by construction (range guard, RangeWatch)
-#ifndef GNR_MFMA_PRIO
-#define GNR_MFMA_PRIO 0      // measurement builds: 1 = the younger half of a workgroup (wavefronts 4-7) at s_setprio 1 for the whole kernel; 2 = s_setprio 1 around every pair-form MFMA cluster
-#endif
 template <int KB, int NB, bool LF, bool WATCH = false>
 DEV void mm16(const float* __restrict__ w, int lane, const P8* __restrict__ x8, f4 (&acc)[NB], float* rw = nullptr) {
     if constexpr (LF) asm volatile("" ::: "memory");
     const h8* w8 = reinterpret_cast<const h8*>(w) + lane;
-#if GNR_MFMA_PRIO == 2
-    __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
         f4 lo = {0.f, 0.f, 0.f, 0.f};
-#if GNR_SPLIT_MM
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) lo = mfma32h(w8[((kb * NB + nb) * 2 + 1) * 64], x8[kb].m, lo);
-        lo *= kPairSi;
-#endif
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
             const h8 wh = w8[((kb * NB + nb) * 2) * 64], wm = w8[((kb * NB + nb) * 2 + 1) * 64];
@@ -342,10 +318,7 @@ DEV void mm16(const float* __restrict__ w, int lane, const P8* __restrict__ x8, 
         acc[nb].z = fmaf(lo.z, kPairSi, acc[nb].z); acc[nb].w = fmaf(lo.w, kPairSi, acc[nb].w);
 #endif
     }
-#if GNR_MFMA_PRIO == 2
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    if constexpr (WATCH) range_watch(*rw, acc[GNR_WATCH_LAST ? NB - 1 : 0]);
+    if constexpr (WATCH) range_watch(*rw, acc[0]);
 }
 // the same layer on unscaled activation pairs: three products into ONE accumulator (the k-blocks outermost, so that
 // consecutive MFMAs go to different output blocks)
@@ -353,9 +326,6 @@ template <int KB, int NB, bool LF, bool WATCH = false>
 DEV void mm16u(const float* __restrict__ w, int lane, const P8U* __restrict__ x8, f4 (&acc)[NB], float* rw = nullptr) {
     if constexpr (LF) asm volatile("" ::: "memory");
     const h8* w8 = reinterpret_cast<const h8*>(w) + lane;
-#if GNR_MFMA_PRIO == 2
-    __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
         h8 wh[NB], wm[NB];
@@ -368,14 +338,11 @@ DEV void mm16u(const float* __restrict__ w, int lane, const P8U* __restrict__ x8
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma32h(wm[nb], x8[kb].s, acc[nb]);
     }
-#if GNR_MFMA_PRIO == 2
-    __builtin_amdgcn_s_setprio(0);
-#endif
     if constexpr (WATCH) range_watch(*rw, acc[0]);
 }
 // ---- K-stacked pair layers (ST section, gnr_layout.h): the per-view layers with SLOTS = 4 or 2 real inputs per lane.  On the
 // fp32-input MFMA such a layer costs one instruction of 32 cycles per k-step and output block for an eighth of an f16 MFMA's
-// products; zero-padded into a K32 block it multiplies zeros in most k-slots (the round-6 GNR_RDF2_PAIRS record).  A lane group's
+// products; zero-padded into a K32 block it multiplies zeros in most k-slots (the round-6 record, docs/experiments/rdf2_pairs.patch).  A lane group's
 // eight k-slots are independent products, and A and B only have to agree slot by slot: the free slots carry the residual terms
 // of the unscaled pair form (mm16u:  W x = wh h + wh m + wm (h 2^-11)),
 //   SLOTS = 4:  A {wh0..3, wm0..3} (as stored) x B {h0..3, s0..3}, then the same A x B {m0..3, 0, 0, 0, 0}: two MFMAs per block,
@@ -408,9 +375,6 @@ template <int SLOTS, int NB, bool LF, bool WATCH = false>
 DEV void mm16s(const float* __restrict__ w, int lane, const P8S& x, f4 (&acc)[NB], float* rw = nullptr) {
     static_assert(SLOTS == 4 || (SLOTS == 2 && NB == 1), "stacked layers: 4 slots, or 2 slots and one output block");
     if constexpr (LF) asm volatile("" ::: "memory");
-#if GNR_MFMA_PRIO == 2
-    __builtin_amdgcn_s_setprio(1);
-#endif
     if constexpr (SLOTS == 4) {
         const h8* w8 = reinterpret_cast<const h8*>(w) + lane;
         h8 a[NB];
@@ -424,9 +388,6 @@ DEV void mm16s(const float* __restrict__ w, int lane, const P8S& x, f4 (&acc)[NB
         const f2 d = reinterpret_cast<const f2*>(w)[lane];
         acc[0] = mfma32h(__builtin_bit_cast(h8, (f4){d.x, d.y, d.x, d.y}), x.a, acc[0]);
     }
-#if GNR_MFMA_PRIO == 2
-    __builtin_amdgcn_s_setprio(0);
-#endif
     if constexpr (WATCH) range_watch(*rw, acc[0]);
 }
 
@@ -742,91 +703,24 @@ DEV Taps make_taps(float u, float v, float sx, float sy, float off, int fh, int 
     return t;
 }
 
-// ---- cooperative projection (k_chain's first view loop).  The four lanes of a point (one per lane group) would each compute the
-// same projection, two IEEE divisions and both sets of bilinear taps.  Instead lane group g does ONE axis of ONE map -- axis
-// g & 1 (u / v), map g >> 1 (feature map / full-resolution image): its row of K[R|t], its division, its 1-D tap (two indices
-// and a weight) and its in-image test -- and the groups exchange the results through ds_bpermute_b32 (12 per view; the LDS
-// crossbar, no VALU slot).  Every lane then assembles the 2 x 4 offsets and weights with the operations make_taps() uses,
-// so offsets, weights and the in-image mask are bit for bit the ones of project_view() + make_taps() (the parity suites pass
-// unchanged, all outputs bitwise equal).  The per-group constants (tap scale / offset, last index, image bound, row stride) sit
-// in a 32-float table behind the weight image in LDS.
-// MEASURED NEGATIVE, kept as a switch (default off): 41 vector instructions per view fewer (907 -> 866 in the first view loop,
-// -246 per tile) and the same time -- 3.36 - 3.40 ms per volume launch and 2.45 - 2.46 ms per pair of render launches either
-// way: the exchange puts an LDS round trip at the head of each view's dependency chain.
-#ifndef GNR_COOP_PROJ
-#define GNR_COOP_PROJ 0
-#endif
-constexpr int COOP_TAB_FLOATS = 32;
-struct CoopOut { Taps f, i; float m, z; };
-DEV void project_coop(const float* __restrict__ vp, const float* __restrict__ tab, int row_bytes, int bp, const float (&p)[3], CoopOut& o) {
-    const f4 row = *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(vp) + row_bytes);
-    const float pc = __fmaf_rn(row.z, p[2], __fmaf_rn(row.y, p[1], __fmul_rn(row.x, p[0]))) + row.w;
-    float z = __fmaf_rn(vp[10], p[2], __fmaf_rn(vp[9], p[1], __fmul_rn(vp[8], p[0]))) + vp[11];
-    const bool inval = fabsf(z) < 1e-4f;
-    if (inval) z = 1e-3f;
-    o.z = z;
-    const float q = __fdiv_rn(pc, z);
-    const f4 c = reinterpret_cast<const f4*>(tab)[0];                  // tap scale, tap offset, last index, image bound
-    const f4 ci = reinterpret_cast<const f4*>(tab)[1];                 // (as ints) row stride, last index
-    const int stride = __float_as_int(ci.x), n1 = __float_as_int(ci.y);
-    const bool outside = (q < -0.5f) | (q >= c.w);
-    float px = fmaf(q, c.x, c.y);
-    px = fminf(fmaxf(px, 0.f), c.z);
-    const float x0 = floorf(px);
-    const float w1 = px - x0;                                          // in [0, 1): the sign bit carries "not visible along this axis"
-    const int i0 = (int)x0, i1 = min(i0 + 1, n1);
-    const int o0 = __mul24(i0, stride), o1 = __mul24(i1, stride);
-    const int w1b = __float_as_int(w1) | ((outside | inval) ? (int)0x80000000 : 0);
-    int O0[4], O1[4], W1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        O0[k] = __builtin_amdgcn_ds_bpermute(bp + 64 * k, o0);
-        O1[k] = __builtin_amdgcn_ds_bpermute(bp + 64 * k, o1);
-        W1[k] = __builtin_amdgcn_ds_bpermute(bp + 64 * k, w1b);
-    }
-    o.m = ((W1[0] | W1[1]) >= 0) ? 1.f : 0.f;
-    auto assemble = [&](int kx, int ky, Taps& t) {
-        t.o00 = O0[ky] + O0[kx]; t.o01 = O0[ky] + O1[kx]; t.o10 = O1[ky] + O0[kx]; t.o11 = O1[ky] + O1[kx];
-        const float wx1 = fabsf(__int_as_float(W1[kx])), wy1 = fabsf(__int_as_float(W1[ky])), wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-        t.w00 = wx0 * wy0; t.w01 = wx1 * wy0; t.w10 = wx0 * wy1; t.w11 = wx1 * wy1;
-    };
-    assemble(0, 1, o.f);
-    assemble(2, 3, o.i);
-}
-// point-to-camera direction against the query direction (the FULL part of project_view)
-DEV void view_dir(const float* __restrict__ vp, const float (&p)[3], const float (&qd)[3], float (&dd)[4]) {
-    float d[3] = {p[0] - vp[12], p[1] - vp[13], p[2] - vp[14]};
-    const float inr = -__builtin_amdgcn_rsqf(fmaxf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2], 1e-10f));
-    d[0] *= inr; d[1] *= inr; d[2] *= inr;
-    dd[0] = d[0] - qd[0]; dd[1] = d[1] - qd[1]; dd[2] = d[2] - qd[2];
-    dd[3] = d[0] * qd[0] + d[1] * qd[1] + d[2] * qd[2];
-}
+// Measured negative, not in the sources (docs/experiments/coop_proj.patch; docs/lab_notebook.md "Removed switches"): the four lanes
+// of a point sharing the projection, one axis of one map each, exchanged through ds_bpermute_b32 -- 41 vector instructions per view
+// fewer and the same time: the exchange puts an LDS round trip at the head of each view's dependency chain.
 
 constexpr int SW = 20;     // per-view state width: X[9] E[8] gate m rgb  /  H2[8] v2 c . . . rgb
 // The per-view state lives in registers, so its rows need static indices while the view loops stay rolled (code size): the
 // state is a QUEUE that advances one row per view: (V-1) x 20 v_mov_b32 per view and loop, 1 320 per tile at V = 6 (14 % of the
-// kernel's vector instructions).  They cost next to nothing: GNR_TWO_QUEUES 1 splits the views into two halves with a queue
-// each and writes every view loop out twice (one rolled loop per queue: (V/2 - 1) x 20 moves per view, 600 per tile, 7 KB more
-// code) and changes a volume launch from 3.35 to 3.32 ms and a render launch from 2.43 to 2.51 (more scratch: 88 B) -- the
-// moves issue while the SIMD's other wavefront owns the matrix pipe.  (An earlier "no moves" ablation that showed 8 - 11 % had
-// let the compiler hoist the second loop's now view-invariant operand splits out of the loop.)  Kept as a switch, default off.
+// kernel's vector instructions).  They cost next to nothing: two half-length queues (every view loop written out twice, 600 moves
+// per tile) changed a volume launch from 3.35 to 3.32 ms and a render launch from 2.43 to 2.51 -- the moves issue while the SIMD's
+// other wavefront owns the matrix pipe (docs/experiments/two_queues.patch; docs/lab_notebook.md "Removed switches").
 // Other measured negatives: addressing the row through wave-uniform branches on the view index (V arms of 20
 // moves; every variant spills, 3.63 - 4.31 ms against 3.56); full unrolling (code 83 KB, 900 B of scratch: 6.6 ms); two / three
 // bodies per trip with the queue advancing two / three rows (200 - 400 B of scratch: 4.85 ms); v_swap_b32 (6.4 cycles per dword),
 // v_mov_b64 / v_pk_mov_b32 (2.8 / 3.1 cycles per dword against 3.2 for v_mov_b32, tools/ubench/mov_rates.hip).
-#ifndef GNR_TWO_QUEUES
-#define GNR_TWO_QUEUES 0
-#endif
-#ifndef GNR_RDF2_PAIRS
-#define GNR_RDF2_PAIRS 0      // measurement build: ray_dir_fc.2 on the f16 matrix cores (gnr_pack_body.h c16_pairs; round-6 A/B record)
-#endif
-// rows of the two queues
-constexpr int rows_a(int V) { return GNR_TWO_QUEUES ? (V + 1) / 2 : V; }
-constexpr int rows_b(int V) { return GNR_TWO_QUEUES ? V / 2 : 0; }
 
 // ---- sample order of the inference render passes (csrc/gnr_sample_order.h) ----
 // (project_view<false>: FULL only adds the point-to-camera direction terms dd[]; u, v, z and the mask m are the same statements in both
-// instantiations, so the key is bit for bit the m of the project_view<true> / project_coop that k_chain ballots on)
+// instantiations, so the key is bit for bit the m of the project_view<true> that k_chain ballots on)
 DEV unsigned view_mask_key(const float* __restrict__ viewp_b, const float (&p)[3], int V, int H, int W) {
     const float qd[3] = {0.f, 0.f, 0.f};
     unsigned k = 0;
@@ -955,35 +849,9 @@ __global__ __launch_bounds__(SO_THREADS) void k_sample_order(const unsigned char
         if (kk[u] >= 0) pb[sorder::slot_of(wbase[wave][kk[u]] + rank[u], P)] = s0 + 64 * u;
 }
 
-#ifndef GNR_DYN_TILES
-#define GNR_DYN_TILES 1         // k_chain takes its tiles from a per-XCD counter (ChainArgs::tile_ctr); 0: static round-robin shares; 2: a wavefront whose XCD's chunk is
-                                // empty goes on with the next XCD's -- MEASURED NEGATIVE (profiles/r06_c_dyn_tiles_ab.json: step 6.40 -> 6.83 ms, render launches
-                                // 2.28 -> 2.58 ms: the time between two tiles of a wavefront goes from 2.4 % to 6.7 % of its life)
-#endif
-#ifndef GNR_VOLUME_POINTS_INLINE
-#define GNR_VOLUME_POINTS_INLINE 1
-#endif
-#ifndef GNR_TAIL_OLD_ONLY
-#define GNR_TAIL_OLD_ONLY 0      // in quarters of the XCD's wavefront count: 4 = the last 256 tiles of a 256-wavefront XCD
-#endif
-#ifndef GNR_DESC_PREFETCH
-#define GNR_DESC_PREFETCH 0      // 1: the next tile's point descriptors are loaded behind the second view loop (eight registers carried through the tile's tail).
-                                 // MEASURED NEGATIVE: step 6.45 -> 6.55 ms, render launches 2.28 -> 2.35 (scratch 72 -> 108 B, volume 12 -> 48 B)
-#endif
-#ifndef GNR_DYN_CTR_INC
-#define GNR_DYN_CTR_INC 0
-#endif
-#ifndef GNR_DYN_TRAIN
-#define GNR_DYN_TRAIN 1       // 1: the training-forward volume instantiation too; 2: and the render one (measured negative); 0: inference only
-#endif
-#ifndef GNR_SKIP_MASKED
-#define GNR_SKIP_MASKED 1      // skip the (tile, view) pairs without a single valid point (inference kernels)
-#endif
-#ifndef GNR_CHAIN_THREADS
-#define GNR_CHAIN_THREADS 512     // 8 wavefronts = 2 per SIMD at 250 registers; 256 (1 per SIMD, 512 registers) was measured too;
-                                  // 768 / 1024 (3 / 4 per SIMD) would spill 356 / 524 B per lane: S[V][20] alone is 120 registers
-#endif
-#define GNR_CHAIN_MIN_BLOCKS (GNR_CHAIN_THREADS >= 1024 ? 1 : GNR_CHAIN_THREADS / 256)
+// 8 wavefronts = 2 per SIMD at 250 registers; 256 (1 per SIMD, 512 registers) was measured too; 768 / 1024 (3 / 4 per SIMD) would
+// spill 356 / 524 B per lane: S[V][20] alone is 120 registers
+constexpr int kChainThreads = 512, kChainMinBlocks = 2;
 // SAVE: training forward (writes the states the backward twins need); compiled out of the inference kernels
 // USEVIS: the optional fourth decoder branch (dist_decoder_cfg.use_vis; GnrScene.use_vis), its own instantiations: as a
 // run-time branch it cost the default kernels 5 - 18 % (3.65 -> 3.82 ms volume, 1.29 -> 1.52 ms render launch)
@@ -997,9 +865,9 @@ __device__ unsigned long long g_wave_clock[2][4096][8];      // [RENDER][workgro
 __device__ unsigned g_tile_clock[2][1 << 17];                // [RENDER][tile] ticks of one tile
 #endif
 template <int V, bool RENDER, bool SAVE = false, bool USEVIS = false, bool SP = (GNR_SPLIT16 != 0)>
-__global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_chain(ChainArgs a) {
+__global__ __launch_bounds__(kChainThreads, kChainMinBlocks) void k_chain(ChainArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr bool LF = (GNR_LICM_FENCE != 0) || V > 6;      // per-layer LICM fences (see mm())
+    constexpr bool LF = V > 6;      // per-layer LICM fences (see mm())
 #if GNR_WAVE_CLOCK
     const unsigned long long wc_t0 = wall_clock64();
 #endif
@@ -1019,14 +887,12 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
         if (a.range_flag && (__builtin_nontemporal_load(a.range_flag) & 5u) != 0u) return;
     }
     bool range_tripped = false;                           // wave-uniform
-    constexpr bool UA = SP && GNR_UNSCALED_ACT != 0;       // inner layers on unscaled activation pairs (split8u / mm16u)
     constexpr bool EP = SP && !SAVE;                       // e1 travels between the view loops as its fp16 pair (the training saves keep fp32)
-    // (in the pair kernels the slots LO(pk::RDF2), LO(pk::RGB2) and pk::ST_AT_RGB1X hold the STACKED fragments while the matching GNR_STACK_* switch is on, the fp32 fragments otherwise: pk::stage_src4)
+    // (in the pair kernels the slots LO(pk::RDF2), LO(pk::RGB2) and pk::ST_AT_RGB1X hold the STACKED fragments, not the fp32 ones: pk::stage_src4)
 #define LO(o) (SP ? pk::c16_off(o) : (o))                  /* offset of a CHAIN-section name inside the staged image */                    // fp16-pair layers on the f16 matrix cores (C16 image) / fp32 MFMA (CHAIN image)
-    // the pair kernels run the short per-view layers K-stacked (mm16s; each conversion has its switch, gnr_layout.h) -- the training
+    // the pair kernels run the short per-view layers K-stacked (mm16s) -- the training
     // forward (SAVE) too: its outputs are the inference launch's bit for bit (tests/test_torch_ops.py); the backward twins' recompute of
     // these three layers stays on the fp32-input MFMA (csrc/gnr_bwd.inc: pre-activations that differ from the forward's by rounding)
-    constexpr bool SK_RDF2 = SP && GNR_STACK_RDF2 != 0, SK_RGB2 = SP && GNR_STACK_RGB2 != 0, SK_RGB1X = SP && GNR_STACK_RGB1X != 0;
     // ---- stage the C16 (or CHAIN) section of the packed weights into LDS (once per workgroup); the pair kernels take the stacked
     // fragments in place of the fp32 fragments they no longer read (pk::stage_src4)
     {
@@ -1041,27 +907,11 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             for (int u = 0; u < SU; ++u) { const int i = i0 + u * (int)blockDim.x; if (i < N4) dst[i] = tmp[u]; }
         }
     }
-    constexpr int COOP_TAB = SP ? pk::C16_END : pk::CHAIN_END;            // per-lane-group constants of project_coop
-    if (threadIdx.x < 4) {
-        const int gg = threadIdx.x, axis = gg & 1, img = gg >> 1;
-        const int n = img ? (axis ? a.H : a.W) : (axis ? a.fh : a.fw);
-        float* tb = lds + COOP_TAB + gg * 8;
-        tb[0] = img ? 1.f : (axis ? (float)a.fh / (float)(a.H - 1) : (float)a.fw / (float)(a.W - 1));
-        tb[1] = img ? 0.f : -0.5f;
-        tb[2] = (float)(n - 1);
-        tb[3] = (float)(axis ? a.H : a.W) - 0.5f;
-        tb[4] = __int_as_float(axis ? (img ? a.W : a.fw) : 1);
-        tb[5] = __int_as_float(n - 1);
-        tb[6] = 0.f; tb[7] = 0.f;
-    }
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
     const int r = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if GNR_MFMA_PRIO == 1
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
 #if GNR_WAVE_CLOCK
     const unsigned long long wc_t1 = wall_clock64();
     unsigned long long wc_n = 0, wc_ph[4] = {0, 0, 0, 0};
@@ -1088,30 +938,14 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
     // (after the second view loop), so its latency is hidden; the order in which an XCD sweeps its chunk is unchanged.
     // (the training-forward render instantiation keeps its static shares: five tiles per wavefront at 8 scenes, and the fetch's wait drains
     // the state stores in front of it -- 378 us per launch static, 412 dynamic; the volume one gains 2 %: profiles/r06_c_dyn_tiles_ab.json)
-    const bool dyn = GNR_DYN_TILES != 0 && (GNR_DYN_TRAIN > 1 || !(SAVE && RENDER)) && (GNR_DYN_TRAIN != 0 || !SAVE) && a.tile_ctr != nullptr;
-    int cx = xcd;                                          // the chunk this wavefront draws from
-    // (GNR_DYN_CTR_INC 1: atomicInc instead of atomicAdd.  The compiler's atomic optimiser rewrites a uniform atomicAdd under a lane mask into
-    // its wave-aggregated form, whose broadcast -- s_waitcnt vmcnt(0) + v_readfirstlane -- sits right behind the instruction, so the fetch is
-    // waited for in the middle of the tile; a wrapping increment with the bound 2^32 - 1 is the same operation, is left alone, and with the
-    // index pinned in its vector register until the end of the tile the wait moves there.  MEASURED NEGATIVE: render launches 2.35 -> 2.46 ms,
-    // volume launch unchanged -- the other wavefront of the SIMD covers the wait, the longer live range costs the render instantiation more.)
-#if GNR_DYN_CTR_INC
-    auto grab = [&]() -> unsigned { unsigned t = 0u; if (lane == 0) t = atomicInc(a.tile_ctr + cx, 0xFFFFFFFFu); return t; };
-#else
-    auto grab = [&]() -> unsigned { unsigned t = 0u; if (lane == 0) t = atomicAdd(a.tile_ctr + cx, 1u); return t; };
-#endif
+    // Measured negatives (docs/lab_notebook.md "Removed switches"; profiles/r06_c_dyn_tiles_ab.json): a wavefront whose XCD's chunk is empty
+    // walking on to the next XCD's (docs/experiments/cross_xcd_walk.patch: step 6.40 -> 6.83 ms), and atomicInc in place of atomicAdd to move
+    // the fetch's wait to the end of the tile (render launches 2.35 -> 2.46 ms).
+    const bool dyn = !(SAVE && RENDER) && a.tile_ctr != nullptr;
+    auto grab = [&]() -> unsigned { unsigned t = 0u; if (lane == 0) t = atomicAdd(a.tile_ctr + xcd, 1u); return t; };
     auto resolve = [&](unsigned t_raw) -> int {            // fetched index -> tile; -1: nothing left
-        int t = __builtin_amdgcn_readfirstlane((int)t_raw);
-#if GNR_DYN_TILES > 1
-        for (int hops = 0; t >= min(ntiles, (cx + 1) * chunk) - cx * chunk;) {      // measured negative: walk on to the next XCD's chunk
-            if (++hops >= NXCD) return -1;
-            cx = cx + 1 == NXCD ? 0 : cx + 1;
-            t = __builtin_amdgcn_readfirstlane((int)grab());
-        }
-        return cx * chunk + t;
-#else
+        const int t = __builtin_amdgcn_readfirstlane((int)t_raw);
         return t < t_end - xcd * chunk ? xcd * chunk + t : -1;
-#endif
     };
     // scene and (brick-permuted) tile-in-scene of a tile of the list
     auto locate = [&](int tile_, int& b_, int& ts_) {
@@ -1133,19 +967,10 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             ts_ = ((BX * bx + wi / GY) * gpr + GY * by + wi % GY) * tpg + tin;
         }
     };
-    auto point_of = [&](int b_, int ts_) -> size_t {
-        int nr = min(ts_ * 16 + r, a.P - 1);
-        if (RENDER && !SAVE && a.sample_perm) nr = min(max(a.sample_perm[(size_t)b_ * a.P + nr], 0), a.P - 1);
-        return (size_t)b_ * a.P + nr;
-    };
     int tile = dyn ? resolve(grab()) : xcd * chunk + lblk * waves_per_block + wave;
-    constexpr bool DPF = GNR_DESC_PREFETCH != 0 && !SAVE;      // the next tile's point descriptors are fetched behind the second view loop
-    f4 d0n = {0.f, 0.f, 0.f, 0.f}, d1n = d0n;
-    bool have_nxt = false;                                  // wave-uniform
     for (; dyn ? tile >= 0 : tile < t_end;) {
         GNR_ITER_FENCE();
         unsigned tile_nxt = 0u;
-        int tile_after = -1;
 #if GNR_WAVE_CLOCK
         const unsigned long long wc_tt = wall_clock64();
 #endif
@@ -1166,8 +991,7 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
         float p[3], qd[3], lo, hi;
         {
             f4 d0, d1;
-            if (DPF && have_nxt) { d0 = d0n; d1 = d1n; }
-            else if (!RENDER && !SAVE && GNR_VOLUME_POINTS_INLINE != 0 && a.pts_R > 0) {
+            if (!RENDER && !SAVE && a.pts_R > 0) {
                 // the grid point of voxel n of scene b, as k_points_volume writes it (field_utils.py:17-27: float64 arithmetic, then the cast;
                 // renderer.py:167-170: + bbox_min, z from the top down): one launch and one exposed load per tile less
                 const int R = a.pts_R;
@@ -1182,17 +1006,14 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             else { d0 = reinterpret_cast<const f4*>(a.desc)[pt * 2]; d1 = reinterpret_cast<const f4*>(a.desc)[pt * 2 + 1]; }
             p[0] = d0.x; p[1] = d0.y; p[2] = d0.z; qd[0] = d0.w; qd[1] = d1.x; qd[2] = d1.y; lo = d1.z; hi = d1.w;
         }
-        constexpr int VA = rows_a(V), VB = rows_b(V);
-        float SA[VA][SW], SB[VB > 0 ? VB : 1][SW];
-        // row of view v (v a compile-time constant after unrolling: the branch folds)
-        auto S = [&](int v, int q) -> float& { return (VB == 0 || v < VA) ? SA[v < VA ? v : 0][q] : SB[v >= VA ? v - VA : 0][q]; };
+        float S[V][SW];
 #pragma unroll
         for (int k = 0; k < V; ++k)
 #pragma unroll
 #if GNR_ABLATE & 1
-            for (int q = 0; q < SW; ++q) S(k, q) = p[0] * (float)(k * SW + q + 1);      // opaque values: nothing downstream folds away
+            for (int q = 0; q < SW; ++q) S[k][q] = p[0] * (float)(k * SW + q + 1);      // opaque values: nothing downstream folds away
 #else
-            for (int q = 0; q < SW; ++q) S(k, q) = 0.f;
+            for (int q = 0; q < SW; ++q) S[k][q] = 0.f;
 #endif
         float msum = 0.f;
         unsigned vbits = 0;
@@ -1204,7 +1025,9 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
 #endif
 
         // ================= phase 1: per view, everything up to the first cross-view reduction
-        // Q: one of the two queues; the views v0 .. v0 + rows - 1 enter it in order (the loop is instantiated once per queue)
+        // Q: the state queue S; the views v0 .. v0 + rows - 1 enter it in order.  (The loop was once instantiated per queue of two.  It stays a
+        // lambda over a queue parameter: written as a plain loop over S, or as a lambda that captures S, the V = 6 kernels get more scratch,
+        // 36 -> 52 / 40 B on the inference volume launch; docs/lab_notebook.md "Removed switches".)
         auto phase1 = [&](auto& Q, const int v0) __attribute__((always_inline)) {
           constexpr int NQ = (int)(sizeof(Q) / sizeof(Q[0]));
 #pragma unroll 1
@@ -1223,13 +1046,6 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             Taps t, ti;
 #if GNR_ABLATE & 2
             vg = vg0; t = t0; ti = ti0;
-#elif GNR_COOP_PROJ
-            {
-                CoopOut co;
-                project_coop(vp, lds + COOP_TAB + g * 8, (g & 1) * 16, (lane & 15) << 2, p, co);
-                view_dir(vp, p, qd, vg.dd);
-                vg.z = co.z; vg.m = co.m; t = co.f; ti = co.i;
-            }
 #else
             project_view<true>(vp, p, qd, a.H, a.W, vg);
             t = make_taps(vg.u, vg.v, fsx, fsy, -0.5f, a.fh, a.fw);
@@ -1238,7 +1054,6 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             const float m = vg.m;
             msum += m;
             vbits |= (m != 0.f ? 1u : 0u) << v;
-#if GNR_SKIP_MASKED
             // No point of the tile lies inside this view (render_ops.py:24-31 mask == 0 for all 16): everything the view would hand to
             // the cross-view reductions carries the weight m = 0 (ibrnet.py:466-472: x, e1 and the gate enter as value * weight), so its
             // row is zeros and the gathers, the decoder and the embedding are not run.  A quarter of a ray's (sample, view) pairs are
@@ -1252,7 +1067,6 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                     continue;
                 }
             }
-#endif
 
             // ---- gather: ray channels 8g..8g+7, image-feature channels 8g..8g+7, rgb channel g
             float FR[8], XI[9];
@@ -1291,12 +1105,9 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                 else mm<8, 2, 0, LF>(lds + LO(pk::DEC1) + br * frag_floats(8, 2), lane, FR, acc);
                 elu_to<2, !SP>(acc, h1);
                 load_bias<2, LF>(lds + LO(pk::B_DEC2) + br * 32, g, acc);
-                if constexpr (SP) {
-                    if constexpr (UA) { const P8U hp = split8u<0>(h1); mm16u<1, 2, LF, true>(lds + LO(pk::DEC2) + br * frag_floats(8, 2), lane, &hp, acc, &msum); }
-                    else { const P8 hp = split8<0>(h1); mm16<1, 2, LF, true>(lds + LO(pk::DEC2) + br * frag_floats(8, 2), lane, &hp, acc, &msum); }
-                }
+                if constexpr (SP) { const P8U hp = split8u<0>(h1); mm16u<1, 2, LF, true>(lds + LO(pk::DEC2) + br * frag_floats(8, 2), lane, &hp, acc, &msum); }
                 else mm<8, 2, 0, LF>(lds + LO(pk::DEC2) + br * frag_floats(8, 2), lane, h1, acc);
-                elu_to<2, !SP || UA>(acc, h2);
+                elu_to<2, true>(acc, h2);
                 if (br < 2) {
                     o5[2 * br] = gsum(dot8(lds + LO(pk::T_DEC3) + (2 * br) * 32, g, h2)) + lds[LO(pk::T_DEC3_B) + 2 * br];
                     o5[2 * br + 1] = gsum(dot8(lds + LO(pk::T_DEC3) + (2 * br + 1) * 32, g, h2)) + lds[LO(pk::T_DEC3_B) + 2 * br + 1];
@@ -1325,12 +1136,9 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                     else mm<8, 2, 0, LF>(lds + LO(pk::DECV1), lane, FR, acc);
                     elu_to<2, !SP>(acc, h1);
                     load_bias<2, LF>(lds + LO(pk::B_DECV2), g, acc);
-                    if constexpr (SP) {
-                        if constexpr (UA) { const P8U hp = split8u<0>(h1); mm16u<1, 2, LF, true>(lds + LO(pk::DECV2), lane, &hp, acc, &msum); }
-                        else { const P8 hp = split8<0>(h1); mm16<1, 2, LF, true>(lds + LO(pk::DECV2), lane, &hp, acc, &msum); }
-                    }
+                    if constexpr (SP) { const P8U hp = split8u<0>(h1); mm16u<1, 2, LF, true>(lds + LO(pk::DECV2), lane, &hp, acc, &msum); }
                     else mm<8, 2, 0, LF>(lds + LO(pk::DECV2), lane, h1, acc);
-                    elu_to<2, !SP || UA>(acc, h2);
+                    elu_to<2, true>(acc, h2);
                     const float pv = sigmoid1(gsum(dot8(lds + LO(pk::T_DECV3), g, h2)) + lds[LO(pk::T_VIS)]);
                     cg *= pv;
                 }
@@ -1371,12 +1179,9 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                 elu_to<1, true>(acc1, d1);
                 load_bias<3, LF>(lds + LO(pk::B_RDF2), g, acc3);
                 // 4 k-steps: K-stacked in the pair kernels (6 f16 MFMAs for 12 fp32 ones), on the fp32 MFMA in the twin (zero-padded
-                // into a K32 pair block: 3.68 vs 3.71 ms alone, but 3.80 together with the padded tails of HOIST / GEO1, which gain more: 3.63)
-#if GNR_RDF2_PAIRS
-                if constexpr (SP && !USEVIS) { const P8 dp = split8z<0, 4>(d1); mm16<1, 3, LF>(lds + pk::c16_off(pk::DECV1), lane, &dp, acc3); }
-                else
-#endif
-                if constexpr (SK_RDF2) { const P8S dp = split_stacked<4, 0>(d1); mm16s<4, 3, LF, true>(lds + LO(pk::RDF2), lane, dp, acc3, &msum); }
+                // into a K32 pair block: 3.68 vs 3.71 ms alone, but 3.80 together with the padded tails of HOIST / GEO1, which gain more: 3.63;
+                // docs/experiments/rdf2_pairs.patch)
+                if constexpr (SP) { const P8S dp = split_stacked<4, 0>(d1); mm16s<4, 3, LF, true>(lds + LO(pk::RDF2), lane, dp, acc3, &msum); }
                 else mm<4, 3, 0, LF>(lds + LO(pk::RDF2), lane, d1, acc3);
                 elu_to<3, true>(acc3, df);
 #pragma unroll
@@ -1403,8 +1208,7 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             if (a.dbg && g == 0 && row_ok) { a.dbg[pt * 32 + v] = hit; a.dbg[pt * 32 + 8 + v] = vis; }
           }
         };
-        phase1(SA, 0);
-        if constexpr (VB > 0) phase1(SB, VA);
+        phase1(S, 0);
 #if GNR_WAVE_CLOCK
         const unsigned long long wc_p1 = wall_clock64();
 #endif
@@ -1418,16 +1222,16 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                 float mu0 = 0.f, mu1 = 0.f;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const float w = S(v, 18) * inv_msum;
-                    mu0 += S(v, j) * (S(v, 17) * w);
-                    mu1 += S(v, j) * w;
+                    const float w = S[v][18] * inv_msum;
+                    mu0 += S[v][j] * (S[v][17] * w);
+                    mu1 += S[v][j] * w;
                 }
                 float va0 = 0.f, va1 = 0.f;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const float w = S(v, 18) * inv_msum;
-                    const float d0 = S(v, j) - mu0, d1 = S(v, j) - mu1;
-                    va0 += (S(v, 17) * w) * d0 * d0;
+                    const float w = S[v][18] * inv_msum;
+                    const float d0 = S[v][j] - mu0, d1 = S[v][j] - mu1;
+                    va0 += (S[v][17] * w) * d0 * d0;
                     va1 += w * d1 * d1;
                 }
                 SV[j] = mu0; SV[9 + j] = va0; SV[18 + j] = mu1; SV[27 + j] = va1;
@@ -1477,7 +1281,6 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             for (int j = 0; j < 8; ++j) E[j] = Rv[9 + j];
             const float m = Rv[18];
             const float w = m * inv_msum;
-#if GNR_SKIP_MASKED
             if constexpr (!SAVE && RENDER) {                                    // the same (tile, view) pairs as in phase 1: visibility 0,
                 if (__ballot(m != 0.f) == 0ull) {                               // colour logit -1e9, features with weight 0 (ibrnet.py:479-484,509)
 #pragma unroll
@@ -1488,7 +1291,6 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                     continue;
                 }
             }
-#endif
             float Hh[8];
             {
                 f4 acc4[4] = {G[0], G[1], G[2], G[3]};
@@ -1505,12 +1307,9 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                 elu_to<4, !SP>(acc4, b1);
                 f4 acc[2];
                 load_bias<2, LF>(lds + LO(pk::B_BASE2), g, acc);
-                if constexpr (SP) {
-                    if constexpr (UA) { const P8U bp[2] = {split8u<0>(b1), split8u<8>(b1)}; mm16u<2, 2, LF, true>(lds + LO(pk::BASE2), lane, bp, acc, &msum); }
-                    else { const P8 bp[2] = {split8<0>(b1), split8<8>(b1)}; mm16<2, 2, LF, true>(lds + LO(pk::BASE2), lane, bp, acc, &msum); }
-                }
+                if constexpr (SP) { const P8U bp[2] = {split8u<0>(b1), split8u<8>(b1)}; mm16u<2, 2, LF, true>(lds + LO(pk::BASE2), lane, bp, acc, &msum); }
                 else mm<16, 2, 0, LF>(lds + LO(pk::BASE2), lane, b1, acc);
-                elu_to<2, !SP || UA>(acc, Hh);
+                elu_to<2, true>(acc, Hh);
             }
             float vis1;
             {
@@ -1519,19 +1318,13 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
 #pragma unroll
                 for (int j = 0; j < 8; ++j) xin[j] = Hh[j] * w;
                 load_bias<2, LF>(lds + LO(pk::B_VIS1), g, acc);
-                if constexpr (SP) {
-                    if constexpr (UA) { const P8U xp = split8u<0>(xin); mm16u<1, 2, LF, true>(lds + LO(pk::VIS1), lane, &xp, acc, &msum); }
-                    else { const P8 xp = split8<0>(xin); mm16<1, 2, LF, true>(lds + LO(pk::VIS1), lane, &xp, acc, &msum); }
-                }
+                if constexpr (SP) { const P8U xp = split8u<0>(xin); mm16u<1, 2, LF, true>(lds + LO(pk::VIS1), lane, &xp, acc, &msum); }
                 else mm<8, 2, 0, LF>(lds + LO(pk::VIS1), lane, xin, acc);
-                elu_to<2, !SP || UA>(acc, v1);
+                elu_to<2, true>(acc, v1);
                 load_bias<2, LF>(lds + LO(pk::B_VIS2), g, acc);
-                if constexpr (SP) {
-                    if constexpr (UA) { const P8U vp8 = split8u<0>(v1); mm16u<1, 2, LF, true>(lds + LO(pk::VIS2), lane, &vp8, acc, &msum); }
-                    else { const P8 vp8 = split8<0>(v1); mm16<1, 2, LF, true>(lds + LO(pk::VIS2), lane, &vp8, acc, &msum); }
-                }
+                if constexpr (SP) { const P8U vp8 = split8u<0>(v1); mm16u<1, 2, LF, true>(lds + LO(pk::VIS2), lane, &vp8, acc, &msum); }
                 else mm<8, 2, 0, LF>(lds + LO(pk::VIS2), lane, v1, acc);
-                elu_to<2, !SP || UA>(acc, res);
+                elu_to<2, true>(acc, res);
                 const float logit = elu1(gsum(dot8(lds + LO(pk::T_VIS2R), g, v1)) + lds[LO(pk::T_SCAL) + 1]);
                 vis1 = sigmoid1(logit) * m;                                    // ibrnet.py:479
 #pragma unroll
@@ -1544,12 +1337,9 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
 #pragma unroll
                 for (int j = 0; j < 8; ++j) xin[j] = Hh[j] * vis1;
                 load_bias<2, LF>(lds + LO(pk::B_VISB1), g, acc);
-                if constexpr (SP) {
-                    if constexpr (UA) { const P8U xp = split8u<0>(xin); mm16u<1, 2, LF, true>(lds + LO(pk::VISB1), lane, &xp, acc, &msum); }
-                    else { const P8 xp = split8<0>(xin); mm16<1, 2, LF, true>(lds + LO(pk::VISB1), lane, &xp, acc, &msum); }
-                }
+                if constexpr (SP) { const P8U xp = split8u<0>(xin); mm16u<1, 2, LF, true>(lds + LO(pk::VISB1), lane, &xp, acc, &msum); }
                 else mm<8, 2, 0, LF>(lds + LO(pk::VISB1), lane, xin, acc);
-                elu_to<2, !SP || UA>(acc, t1);
+                elu_to<2, true>(acc, t1);
                 v2 = sigmoid1(gsum(dot8(lds + LO(pk::T_VISB2), g, t1)) + lds[LO(pk::T_SCAL) + 2]) * m;   // :481
             }
             vsum += v2;
@@ -1563,14 +1353,14 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
                 load_bias<1, LF>(lds + LO(pk::B_RGB1), g, acc1);
                 const float ex[2] = {g == 0 ? v2 : (g == 1 ? vg.dd[0] : (g == 2 ? vg.dd[1] : vg.dd[2])), g == 0 ? vg.dd[3] : 0.f};
                 // (v2, dir diff: bounded by construction; the accumulator is watched by the K32 block behind)
-                if constexpr (SK_RGB1X) { const P8S xp = split_stacked<2, 0>(ex); mm16s<2, 1, LF>(lds + pk::ST_AT_RGB1X, lane, xp, acc1); }
+                if constexpr (SP) { const P8S xp = split_stacked<2, 0>(ex); mm16s<2, 1, LF>(lds + pk::ST_AT_RGB1X, lane, xp, acc1); }
                 else mm<2, 1, 8, LF>(lds + LO(pk::RGB1), lane, ex, acc1);
                 if constexpr (SP) { const P8 hp = split8<0>(Hh); mm16<1, 1, LF, true>(lds + LO(pk::RGB1), lane, &hp, acc1, &msum); }
                 else mm<8, 1, 0, LF>(lds + LO(pk::RGB1), lane, Hh, acc1);
                 elu_to<1, !SP>(acc1, c1);
                 load_bias<1, LF>(lds + LO(pk::B_RGB2), g, acc1);
                 // 4 k-steps, one output block: K-stacked in the pair kernels, on the fp32 MFMA in the twin
-                if constexpr (SK_RGB2) { const P8S cp = split_stacked<4, 0>(c1); mm16s<4, 1, LF, true>(lds + LO(pk::RGB2), lane, cp, acc1, &msum); }
+                if constexpr (SP) { const P8S cp = split_stacked<4, 0>(c1); mm16s<4, 1, LF, true>(lds + LO(pk::RGB2), lane, cp, acc1, &msum); }
                 else mm<4, 1, 0, LF>(lds + LO(pk::RGB2), lane, c1, acc1);
                 elu_to<1, true>(acc1, c2);
                 clog = gsum(dot4(lds + LO(pk::T_RGB3), g, c2)) + lds[LO(pk::T_SCAL) + 3];
@@ -1594,29 +1384,14 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
             if (a.dbg && g == 0 && row_ok) a.dbg[pt * 32 + 16 + v] = v2;
           }
         };
-        phase2(SA, 0);
-        if constexpr (VB > 0) phase2(SB, VA);
+        phase2(S, 0);
 #if GNR_WAVE_CLOCK
         const unsigned long long wc_p3 = wall_clock64();
 #endif
         if (dyn) {
-            // GNR_TAIL_OLD_ONLY: the younger half of a workgroup (wavefronts 4-7: the SIMD issues them second, a tile takes them ~1.5x as long)
-            // leaves the chunk's last tiles to the older half -- a wavefront whose current index is within TAIL_K of the chunk's end fetches no further one
-            bool more = true;
-#if GNR_TAIL_OLD_ONLY
-            if (wave >= 4) more = (t_end - tile) > (GNR_TAIL_OLD_ONLY * nlblk * waves_per_block) / 4;
-#endif
-            tile_nxt = more ? grab() : 0x7fffffffu;
-        }
-        if constexpr (DPF) {
-            tile_after = dyn ? resolve(tile_nxt) : tile + nlblk * waves_per_block;
-            have_nxt = dyn ? tile_after >= 0 : tile_after < t_end;
-            if (have_nxt) {
-                int bn, tsn;
-                locate(tile_after, bn, tsn);
-                const size_t ptn = point_of(bn, tsn);
-                d0n = reinterpret_cast<const f4*>(a.desc)[ptn * 2]; d1n = reinterpret_cast<const f4*>(a.desc)[ptn * 2 + 1];
-            }
+            // (measured negatives, docs/lab_notebook.md "Removed switches": the younger half of a workgroup leaving the chunk's last tiles to the
+            // older half; loading the next tile's point descriptors here, docs/experiments/desc_prefetch.patch: step 6.45 -> 6.55 ms)
+            tile_nxt = grab();
         }
 
         // ================= cross-view reduction 2 (ibrnet.py:482-484,488) + colour blend (:510-511)
@@ -1625,25 +1400,25 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
         {
             const float inv_vsum = rcp1(vsum + 1e-8f);
 #pragma unroll
-            for (int v = 0; v < V; ++v) wbar += S(v, 8) * inv_vsum;
+            for (int v = 0; v < V; ++v) wbar += S[v][8] * inv_vsum;
             wbar *= (1.f / (float)V);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 float mu = 0.f, va = 0.f;
 #pragma unroll
-                for (int v = 0; v < V; ++v) mu += S(v, j) * (S(v, 8) * inv_vsum);
+                for (int v = 0; v < V; ++v) mu += S[v][j] * (S[v][8] * inv_vsum);
 #pragma unroll
-                for (int v = 0; v < V; ++v) { const float d = S(v, j) - mu; va += (S(v, 8) * inv_vsum) * d * d; }
+                for (int v = 0; v < V; ++v) { const float d = S[v][j] - mu; va += (S[v][8] * inv_vsum) * d * d; }
                 Z[j] = mu; Z[8 + j] = va;
             }
         }
         if constexpr (RENDER) {
             float cmax = -3.0e38f;
 #pragma unroll
-            for (int v = 0; v < V; ++v) cmax = fmaxf(cmax, S(v, 9));
+            for (int v = 0; v < V; ++v) cmax = fmaxf(cmax, S[v][9]);
             float den = 0.f, num = 0.f;
 #pragma unroll
-            for (int v = 0; v < V; ++v) { const float e = __expf(S(v, 9) - cmax); den += e; num += S(v, 19) * e; }
+            for (int v = 0; v < V; ++v) { const float e = __expf(S[v][9] - cmax); den += e; num += S[v][19] * e; }
             if (g < 3 && row_ok) a.colors[opt * 3 + g] = num * rcp1(den);
         }
         if (SAVE && a.saveZ) {
@@ -1702,11 +1477,7 @@ __global__ __launch_bounds__(GNR_CHAIN_THREADS, GNR_CHAIN_MIN_BLOCKS) void k_cha
         if constexpr (SP && !SAVE) { const unsigned long long wc_e = wall_clock64(); ++wc_n; wc_ph[0] += wc_p1 - wc_tt; wc_ph[1] += wc_p2 - wc_p1; wc_ph[2] += wc_p3 - wc_p2; wc_ph[3] += wc_e - wc_p3;
             if (lane == 0 && tile < (1 << 17)) g_tile_clock[RENDER ? 1 : 0][tile] = (unsigned)(wc_e - wc_tt); }
 #endif
-#if GNR_DYN_CTR_INC
-        if (dyn) asm volatile("" : "+v"(tile_nxt));       // the fetched index stays in its vector register until here
-#endif
-        if constexpr (DPF) tile = have_nxt ? tile_after : (dyn ? -1 : t_end);
-        else tile = dyn ? resolve(tile_nxt) : tile + nlblk * waves_per_block;
+        tile = dyn ? resolve(tile_nxt) : tile + nlblk * waves_per_block;
     }
     if (dyn && lane == 0) {        // the launch's last wavefront (every other one has made its last, failing, fetches) re-arms the counters for the next launch
         if (atomicAdd(a.tile_ctr + 8, 1u) == gridDim.x * (unsigned)waves_per_block - 1u) {
@@ -1805,16 +1576,13 @@ DEV void head_logits_s(const float (&qs)[16], const float* __restrict__ Kj, floa
 // the same logits with the softmax shift as the seed of each dot product's FMA chain (SD): s_h - shift_h in four instructions per
 // head instead of five, and one rounding less.  The seeded chain and the plain one differ by the rounding of the partial sums, so a
 // row whose shift is its EXACT maximum (found with the plain chain) must subtract it from the plain chain too: only then is the
-// largest exponent exactly 0 whatever the magnitude of the logits -- k_ray's `exact` rows run with SD = false.  (GNR_RAY_SEED=0: never seeded.)
-#ifndef GNR_RAY_SEED
-#define GNR_RAY_SEED 1
-#endif
+// largest exponent exactly 0 whatever the magnitude of the logits -- k_ray's `exact` rows run with SD = false.
 template <bool SD>
 DEV void head_logits_shifted(const float (&qs)[16], const float* __restrict__ Kj, const float (&shift)[4], float (&s)[4]) {
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
         const f4 k = reinterpret_cast<const f4*>(Kj)[h];
-        if constexpr (SD && GNR_RAY_SEED)
+        if constexpr (SD)
             s[h] = fmaf(qs[4 * h + 3], k.w, fmaf(qs[4 * h + 2], k.z, fmaf(qs[4 * h + 1], k.y, fmaf(qs[4 * h], k.x, -shift[h]))));
         else
             s[h] = (qs[4 * h] * k.x + qs[4 * h + 1] * k.y + qs[4 * h + 2] * k.z + qs[4 * h + 3] * k.w) - shift[h];
@@ -1823,26 +1591,16 @@ DEV void head_logits_shifted(const float (&qs)[16], const float* __restrict__ Kj
 // a . b - c for float4 a, b the same way
 template <bool SD = true>
 DEV float dot4_minus(float a0, float a1, float a2, float a3, const f4& b, float c) {
-    if constexpr (SD && GNR_RAY_SEED) return fmaf(a3, b.w, fmaf(a2, b.z, fmaf(a1, b.y, fmaf(a0, b.x, -c))));
+    if constexpr (SD) return fmaf(a3, b.w, fmaf(a2, b.z, fmaf(a1, b.y, fmaf(a0, b.x, -c))));
     else return (a0 * b.x + a1 * b.y + a2 * b.z + a3 * b.w) - c;
 }
 
-#ifndef GNR_RAY_UNROLL
-#define GNR_RAY_UNROLL 1
-#endif
 // LDS per ray: K [dn][16], V [dn][16], squared key norms [dn][4]; the render kernel's column pass re-uses the same floats for
 // Q [dn][16], dO [dn][16] and the row statistics [dn][12] once every lane is past the row pass (RAY_PER floats per sample: 7.2 KB
 // per 40-sample ray, 43 KB per workgroup of six rays), which lets THREE workgroups share a CU (launch bounds 3: <= 168
 // registers) where the separate Q / dO / statistics arrays (76 floats per sample) allowed two.
-#ifndef GNR_RAY_BLOCKS
-#define GNR_RAY_BLOCKS 3
-#endif
-constexpr int ray_per(bool render) { return render ? (GNR_RAY_BLOCKS >= 3 ? 44 : 80) : 36; }
-// GNR_RAY_GEO_MFMA: geometry_fc's backward inside k_ray<true> (2 632 of the ~12 500 vector instructions of a wavefront as fp32 FMAs) on the
-// f16 matrix cores, 16 samples as MFMA columns; 0: the fp32 FMA form
-#ifndef GNR_RAY_GEO_MFMA
-#define GNR_RAY_GEO_MFMA (GNR_RAY_BLOCKS >= 3)
-#endif
+constexpr int kRayBlocks = 3;
+constexpr int ray_per(bool render) { return render ? 44 : 36; }
 // wave-level ordering of LDS traffic between lanes of the same wavefront
 DEV void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1854,8 +1612,10 @@ DEV void wave_sync() {
 // VOLG (RENDER only): the volume output mode of gnr_sample_volume_grad_fwd -- the "rays" are the volume's columns (k_points_volume's
 // descriptors); behind the VJP the kernel writes the gradient (and the SDF) of sample i into voxel (x, y, R-1-i) and the column's sum of
 // (|grad| - 1)^2, and returns: no depths, no alpha, no compositing, no resampler
-template <bool RENDER, bool MM = (GNR_RAY_GEO_MFMA != 0), bool VOLG = false>
-__global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayArgs a) {
+// (MM: geometry_fc's backward, 2 632 of the ~12 500 vector instructions of a wavefront as fp32 FMAs, with 16 samples as MFMA columns:
+// docs/experiments/r05_ray_mfma.patch)
+template <bool RENDER, bool MM = true, bool VOLG = false>
+__global__ __launch_bounds__(256, (RENDER ? kRayBlocks : 2)) void k_ray(RayArgs a) {
     static_assert(RENDER || !VOLG, "the volume output mode follows the VJP of the render instantiation");
     if constexpr (RENDER && !MM) {
         if (a.only_if && (__builtin_nontemporal_load(a.only_if) & 2u) == 0u) return;
@@ -1873,15 +1633,15 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
     const int ray = min(ray_u, a.nrays - 1);
     const bool act = rvalid && slot < dn;
     const int i = min(slot, dn - 1);
-    constexpr bool OVL = RENDER && GNR_RAY_BLOCKS >= 3;   // Q / dO / statistics overlay K / V / key norms
     float* sc = sm + (size_t)rl * a.ray_stride;
     float* Kb = sc;                                   // [dn][16]
     float* Vb = sc + dn * 16;                         // [dn][16]
     float* KN = sc + dn * 32;                         // [dn][4]    squared key norms per head
     constexpr int KNS = 4;
-    float* Qb = OVL ? sc : sc + dn * 36;              // [dn][16]   (RENDER, column pass)
-    float* Ob = OVL ? sc + dn * 16 : sc + dn * 52;    // [dn][16]   dO
-    float* St = OVL ? sc + dn * 32 : sc + dn * 68;    // [dn][12]   shift[4] (log2 domain), rs[4] / sum[4] (dO is stored divided by the row sum as well); a workgroup with an `exact` row: shift, rs, 1/sum
+    // RENDER, column pass: Q / dO / statistics overlay K / V / key norms
+    float* Qb = sc;                                   // [dn][16]
+    float* Ob = sc + dn * 16;                         // [dn][16]   dO
+    float* St = sc + dn * 32;                         // [dn][12]   shift[4] (log2 domain), rs[4] / sum[4] (dO is stored divided by the row sum as well); a workgroup with an `exact` row: shift, rs, 1/sum
     (void)Qb; (void)St; (void)Ob;
     const size_t pt = (size_t)ray * dn + i;
     // the ray in the caller's order (RENDER with sorted descriptors): index of every user-visible array
@@ -1892,8 +1652,8 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
     constexpr int REC = RENDER ? REC_RAY : REC_VOL;
     const float* rec = a.rec + pt * REC;
     const float* W = a.wpk;
-    constexpr int UB = GNR_RAY_UNROLL;                    // (no measurable effect: the kernel is VALU-throughput bound)
-    constexpr int UA = RENDER ? UB : 4;                   // key-loop unroll (register pressure vs LDS latency)
+    constexpr int UA = RENDER ? 1 : 4;                    // key-loop unroll (register pressure vs LDS latency; more has no measurable effect on the
+                                                          // render kernel's loops, which stay rolled: it is VALU-throughput bound)
 
     float g16[16], t[16];
     {
@@ -1934,10 +1694,6 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
             reinterpret_cast<f4*>(Kb + i * 16)[c] = k4;
             reinterpret_cast<f4*>(Vb + i * 16)[c] = v4;
             KN[i * KNS + c] = k4.x * k4.x + k4.y * k4.y + k4.z * k4.z + k4.w * k4.w;
-            if constexpr (RENDER && !OVL) {
-                const f4 q4 = {qs[4 * c], qs[4 * c + 1], qs[4 * c + 2], qs[4 * c + 3]};
-                reinterpret_cast<f4*>(Qb + i * 16)[c] = q4;
-            }
         }
     }
     __syncthreads();
@@ -2079,7 +1835,7 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
             // chain over the same numbers); a seeded chain would leave the rounding of a huge dA times a huge k there.
             auto row_pass = [&](auto fast) {
                 constexpr bool FAST = decltype(fast)::value;
-#pragma unroll UB
+#pragma unroll 1
                 for (int j = 0; j < dn; ++j) {
                     float sj[4];
                     head_logits_shifted<FAST>(qs, Kb + j * 16, amax, sj);
@@ -2102,23 +1858,18 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
                 dQ[4 * h] = d4.x; dQ[4 * h + 1] = d4.y; dQ[4 * h + 2] = d4.z; dQ[4 * h + 3] = d4.w;
             }
         }
-        if constexpr (OVL) {                              // the lane's own key / value row, before the arrays are re-used
+        // the lane's own key / value row, before the arrays are re-used
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const f4 k4 = reinterpret_cast<const f4*>(Kb + i * 16)[c], v4 = reinterpret_cast<const f4*>(Vb + i * 16)[c];
-                kk[4 * c] = k4.x; kk[4 * c + 1] = k4.y; kk[4 * c + 2] = k4.z; kk[4 * c + 3] = k4.w;
-                vv[4 * c] = v4.x; vv[4 * c + 1] = v4.y; vv[4 * c + 2] = v4.z; vv[4 * c + 3] = v4.w;
-            }
+        for (int c = 0; c < 4; ++c) {
+            const f4 k4 = reinterpret_cast<const f4*>(Kb + i * 16)[c], v4 = reinterpret_cast<const f4*>(Vb + i * 16)[c];
+            kk[4 * c] = k4.x; kk[4 * c + 1] = k4.y; kk[4 * c + 2] = k4.z; kk[4 * c + 3] = k4.w;
+            vv[4 * c] = v4.x; vv[4 * c + 1] = v4.y; vv[4 * c + 2] = v4.z; vv[4 * c + 3] = v4.w;
         }
         // The barrier carries a vote: ONE `exact` query row among the workgroup's rays sends every lane of the workgroup through the
         // plain column pass (lanes that shadow a ray beyond the launch ran on stale LDS: they do not vote).
         __shared__ int exact_wave[4];
         {
-#ifdef GNR_DBG_SHADOW_VOTE      // (the bug as found: tests/test_range_guard.py::test_stale_lds_does_not_reach_the_outputs must FAIL on this build)
-            const bool w_exact = __ballot(exact) != 0ull;
-#else
-            const bool w_exact = __ballot(exact && act) != 0ull;
-#endif
+            const bool w_exact = __ballot(exact && act) != 0ull;      // (the bug as found: docs/experiments/shadow_vote_bug.patch)
             if ((threadIdx.x & 63) == 0) exact_wave[threadIdx.x >> 6] = w_exact ? 1 : 0;
         }
         __syncthreads();                                  // every lane is past the row pass (and the key-norm sweep): K / V / KN are free
@@ -2130,10 +1881,8 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
                 const float sc = any_exact ? 1.f : ainv[c];
                 const f4 d4 = {dO[4 * c] * sc, dO[4 * c + 1] * sc, dO[4 * c + 2] * sc, dO[4 * c + 3] * sc};
                 reinterpret_cast<f4*>(Ob + i * 16)[c] = d4;
-                if constexpr (OVL) {
-                    const f4 q4 = {qs[4 * c], qs[4 * c + 1], qs[4 * c + 2], qs[4 * c + 3]};
-                    reinterpret_cast<f4*>(Qb + i * 16)[c] = q4;
-                }
+                const f4 q4 = {qs[4 * c], qs[4 * c + 1], qs[4 * c + 2], qs[4 * c + 3]};
+                reinterpret_cast<f4*>(Qb + i * 16)[c] = q4;
             }
             const f4 m4 = {amax[0], amax[1], amax[2], amax[3]}, i4 = {ainv[0], ainv[1], ainv[2], ainv[3]};
             const f4 r4 = any_exact ? (f4){rsv[0], rsv[1], rsv[2], rsv[3]} : (f4){rsv[0] * ainv[0], rsv[1] * ainv[1], rsv[2] * ainv[2], rsv[3] * ainv[3]};
@@ -2152,7 +1901,7 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
             for (int h = 0; h < 4; ++h) { dK4[h] = (f4){0.f, 0.f, 0.f, 0.f}; dV4[h] = (f4){0.f, 0.f, 0.f, 0.f}; }
             auto col_pass = [&](auto fast) {
                 constexpr bool FAST = decltype(fast)::value;
-#pragma unroll UB
+#pragma unroll 1
                 for (int qi = 0; qi < dn; ++qi) {
                     const f4 mx4 = reinterpret_cast<const f4*>(St + qi * 12)[0];
                     const f4 rs4 = reinterpret_cast<const f4*>(St + qi * 12)[1];
@@ -2229,7 +1978,6 @@ __global__ __launch_bounds__(256, (RENDER ? GNR_RAY_BLOCKS : 2)) void k_ray(RayA
         // chain stays in registers: the D layout of each layer is the B layout the next one was packed for (dT -> ELU' -> dc -> du ->
         // ELU' -> da -> de), and de comes back through the same row.
         {
-            static_assert(OVL, "the transfer rows re-use the overlaid attention scratch");
             const int lane = threadIdx.x & 63, mr = lane & 15, mg = lane >> 4;
             const unsigned magic = (65536u + (unsigned)S - 1u) / (unsigned)S;      // T / S for T < 256 as (T * magic) >> 16
             constexpr int GS = 36;                            // row stride (floats): 16-byte aligned, rows of a group on different banks

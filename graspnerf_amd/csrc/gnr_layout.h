@@ -186,23 +186,14 @@ static_assert(C16_END % 4 == 0 && C16_END * 4 <= 160 * 1024, "the C16 image must
 constexpr int TOTAL = C16 + C16_END;
 // The image the pair instantiations of k_chain stage into LDS: the C16 image with the stacked fragments over the fp32
 // fragments they replace (ray_dir_fc.2: the first three quarters of its slot; rgb_fc.2: the whole slot; rgb_fc.0: the first half of
-// its two left-over k-steps behind the K32 block).  Each conversion has a switch of its own (measured one by one: profiles/chain_stacked_ab.json).
-#ifndef GNR_STACK_RDF2
-#define GNR_STACK_RDF2 1
-#endif
-#ifndef GNR_STACK_RGB2
-#define GNR_STACK_RGB2 1
-#endif
-#ifndef GNR_STACK_RGB1X
-#define GNR_STACK_RGB1X 1
-#endif
+// its two left-over k-steps behind the K32 block).  (Measured one by one: profiles/chain_stacked_ab.json.)
 constexpr int ST_AT_RGB1X = c16_off(RGB1) + k32_floats(1);     // where the staged image holds rgb_fc.0's stacked k-steps 8, 9
 // 16-byte word i4 of the staged image <- this 16-byte word of the blob
 constexpr int stage_src4(int i4) {
     const int o = 4 * i4;
-    if (GNR_STACK_RDF2 != 0 && o >= c16_off(RDF2) && o < c16_off(RDF2) + st_floats(4, 3)) return (ST_RDF2 + o - c16_off(RDF2)) / 4;
-    if (GNR_STACK_RGB2 != 0 && o >= c16_off(RGB2) && o < c16_off(RGB2) + st_floats(4, 1)) return (ST_RGB2 + o - c16_off(RGB2)) / 4;
-    if (GNR_STACK_RGB1X != 0 && o >= ST_AT_RGB1X && o < ST_AT_RGB1X + st_floats(2, 1)) return (ST_RGB1X + o - ST_AT_RGB1X) / 4;
+    if (o >= c16_off(RDF2) && o < c16_off(RDF2) + st_floats(4, 3)) return (ST_RDF2 + o - c16_off(RDF2)) / 4;
+    if (o >= c16_off(RGB2) && o < c16_off(RGB2) + st_floats(4, 1)) return (ST_RGB2 + o - c16_off(RGB2)) / 4;
+    if (o >= ST_AT_RGB1X && o < ST_AT_RGB1X + st_floats(2, 1)) return (ST_RGB1X + o - ST_AT_RGB1X) / 4;
     return (C16 + o) / 4;
 }
 static_assert(ST_RDF2 % 4 == 0 && C16 % 4 == 0 && c16_off(RDF2) % 4 == 0 && c16_off(RGB2) % 4 == 0 && ST_AT_RGB1X % 4 == 0, "staged as 16-byte words");

@@ -1,7 +1,7 @@
 """Round 6: the float64 arbiter of the BACKWARD at the benched training shape (pytest -m gpu, through the C ABI).
 
 The view kernels of the backward recompute the forward and run their dX chains on the f16 matrix cores, every fp32 operand an
-fp16 pair, the upstream gradient of a (tile, view) normalised by a power of two (csrc/gnr_bwd.inc, GNR_BWD_PAIRS); the per-ray tails
+fp16 pair, the upstream gradient of a (tile, view) normalised by a power of two (csrc/gnr_bwd.inc, the BP instantiations); the per-ray tails
 use the same form.  The forward's licence for "f32" is tests/test_range_guard.py::test_fp64_arbiter_benched_shape; this is the same
 arbiter for the gradients: on BASELINE configs[4]'s shape -- 8 scenes x 6 views of 288 x 512, the 40^3 volume of the coarse level,
 a coarse pass of 512 rays x 40 samples, a fine pass of 512 x 40 on its own depths --

@@ -361,7 +361,7 @@ def test_nothing_reads_memory_it_did_not_write(weights_np, monkeypatch):
             assert torch.equal(v, b[k]), k
 
         # A second scene whose fourth view sees nothing (its principal point lies 10 000 pixels outside the image): on the ray points
-        # every (tile, view) pair of that view is skipped by the render pass's backward kernels (GNR_BWD_SKIP_MASKED).  Every path but
+        # every (tile, view) pair of that view is skipped by the render pass's backward kernels (View1BwdArgs::skip_masked).  Every path but
         # the binned one takes the fixed-point quantum from a maximum over the WHOLE dS1 buffer, skipped pairs included: with the
         # allocations filled with 0x71 bytes (floats of 1.19e30) an entry nobody stored would move the quantum by a hundred binades.
         scenes4 = [make_scene(80 + i, dict(CONFIGS['cfg1'], V=4, rn=rn)) for i in range(B)]

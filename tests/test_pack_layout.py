@@ -378,7 +378,7 @@ def pair_parts(packed, base, NB, block, nb, part):
 
 def emulate_pairs(packed, base, NB, blocks_in, acc):
     """blocks_in[b][e][lane] fp32 activations of K32 block b -> acc[nb][t][lane] += W x with the kernel's arithmetic: operands as
-    fp16 pairs (h = fp16(x), m = fp16((x - h) 2^11)), partial products Wh xh + (Wh xm + Wm xh) 2^-11 (Wm xm dropped: GNR_SPLIT_MM 0)."""
+    fp16 pairs (h = fp16(x), m = fp16((x - h) 2^11)), partial products Wh xh + (Wh xm + Wm xh) 2^-11 (Wm xm dropped)."""
     out = acc.astype(np.float64).copy()
     for b, xin in enumerate(blocks_in):                       # xin [8][64]
         xh = xin.astype(np.float16)

@@ -144,7 +144,7 @@ def test_stale_lds_does_not_reach_the_outputs(rn, weights_np):
     rays and six ray slots whose lanes shadow the last ray on LDS nobody wrote.  Those lanes take part in the barriers -- and, since
     round 6, would take part in the workgroup's vote for the plain-chain column pass (csrc/gnr_kernels.hip: `exact`): they must not,
     or the last rays' SDF gradients depend on what earlier kernels left behind (found as a one-ulp difference between a launch and
-    its repeat that only showed after the x3000 scene had run; a build with -DGNR_DBG_SHADOW_VOTE=1 fails here).  The whole forward
+    its repeat that only showed after the x3000 scene had run; a build with docs/experiments/shadow_vote_bug.patch applied fails here).  The whole forward
     after gnr_debug_fill_lds(0), after a NaN pattern and after 1e30: the same bits, SDF gradient included."""
     from graspnerf_amd import _lib
     from graspnerf_amd.hotpath import batch_scenes
@@ -265,7 +265,7 @@ def test_fp64_arbiter_on_weights_an_optimiser_has_moved(weights_trained_np, weig
 
 def _arbiter_benched_shape(case, weights_np, tag=''):
     """The same arbiter at the shape bench.py times (BASELINE configs[1] / configs[2]): 6 views of 288x512, 40^3 voxels, 512 rays x
-    (40 coarse + 40 fine) samples -- where the unscaled-residual floor of the inner layers (gnr_kernels.hip GNR_UNSCALED_ACT) meets
+    (40 coarse + 40 fine) samples -- where the unscaled-residual floor of the inner layers (gnr_kernels.hip "unscaled activation pairs") meets
     6-view statistics.  |HIP pair form - fp64| against |fp32 oracle - fp64| over every voxel and every coarse / fine sample (the fine
     pass of both oracles runs on the HIP path's resampled depths: the resampler is compared elsewhere, this test is about arithmetic).
     Requirement as at 16^3: rms within 1.5x and 99th percentile within 2x of the fp32 oracle's distance."""
