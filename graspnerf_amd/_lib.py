@@ -74,6 +74,10 @@ class GnrTsdfParams(C.Structure):
                 ('voxel_size', C.c_double), ('sdf_trunc', C.c_double), ('depth_scale', C.c_double), ('depth_trunc', C.c_double)]
 
 
+class GnrMeshParams(C.Structure):
+    _fields_ = [('iso', C.c_float), ('scale', C.c_double), ('origin', C.c_double * 3)]
+
+
 class GnrError(RuntimeError):
     pass
 
@@ -252,6 +256,11 @@ def lib():
     L.gnr_surface_points_fwd.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(GnrSurfaceParams)] + [C.c_void_p] * 4 + \
                                         [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.gnr_surface_points_fwd.restype = C.c_int
+    L.gnr_surface_mesh_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    L.gnr_surface_mesh_workspace_bytes.restype = C.c_size_t
+    L.gnr_surface_mesh_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GnrMeshParams)] + [C.c_void_p] * 4 + \
+                                      [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.gnr_surface_mesh_fwd.restype = C.c_int
     L.gnr_tsdf_reset.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnr_tsdf_reset.restype = C.c_int
     L.gnr_tsdf_integrate.argtypes = [C.POINTER(GnrTsdfParams)] + [C.c_void_p] * 7
@@ -315,7 +324,7 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_frame_metrics_workspace_bytes', 'gnr_frame_metrics',
             'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd',
             'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd',
-            'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid',
+            'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid', 'gnr_surface_mesh_workspace_bytes', 'gnr_surface_mesh_fwd',
             'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gnr_compact.h"
 #include "gnr_host.h"
 
 namespace gnr_post {
@@ -126,21 +127,6 @@ __global__ __launch_bounds__(1024) void k_compact(const unsigned char* __restric
     if (threadIdx.x == 0) count[b] = base_s;
 }
 
-// Exclusive rank of this thread among the threads of a 1024-thread workgroup whose flag is set, and the number of set flags
-// (the ballot scan of k_compact as a function; wave_tot: 16 ints of LDS).  Every thread of the workgroup calls it.
-__device__ inline int block_rank(bool f, int* wave_tot, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(f);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    __syncthreads();                                   // the readers of the previous call are done with wave_tot
-    if (lane == 0) wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int w = 0; w < 16; ++w) { const int c = wave_tot[w]; if (w < wave) off += c; tot += c; }
-    total = tot;
-    return off + before;
-}
-
 // float -> unsigned whose ASCENDING order is the floats' DESCENDING order (negative scores included): the usual order-preserving
 // map (flip every bit of a negative, the sign bit of a non-negative), complemented
 __device__ inline unsigned key_desc(float v) {
@@ -235,23 +221,8 @@ __global__ __launch_bounds__(1024) void k_surf_count(const float* __restrict__ v
 
 __global__ __launch_bounds__(1024) void k_surf_scan(int* __restrict__ chunk, int nc, int* __restrict__ count) {
     __shared__ int wave_tot[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int* c = chunk + (size_t)blockIdx.x * nc;
-    int base = 0;
-    for (int c0 = 0; c0 < nc; c0 += 1024) {
-        const int t = c0 + threadIdx.x;
-        const int v = t < nc ? c[t] : 0;
-        int inc = v;
-        for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(inc, d); if (lane >= d) inc += u; }
-        __syncthreads();
-        if (lane == 63) wave_tot[wave] = inc;
-        __syncthreads();
-        int off = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) { const int s = wave_tot[w]; if (w < wave) off += s; tot += s; }
-        if (t < nc) c[t] = base + off + inc - v;
-        base += tot;
-    }
-    if (threadIdx.x == 0) count[blockIdx.x] = base;
+    const int total = scan_chunks(chunk + (size_t)blockIdx.x * nc, nc, wave_tot);
+    if (threadIdx.x == 0) count[blockIdx.x] = total;
 }
 
 struct SurfColor { int value_map; float rgb[3]; float a, b, m; };

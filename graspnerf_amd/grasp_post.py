@@ -2,7 +2,8 @@
 kernels (csrc/gnr_post.hip) instead of scipy.ndimage on the host, plus the host-side tail of `GraspNeRFPlanner.__call__`
 (main.py:197-209: seeded permutation, voxel -> metric coordinates).  The real-robot route of src/nr/utils/grasp_utils.py and
 draw_utils.py is here too: `process` with its three thresholds (GRASP_UTILS_PROCESS), `sim_grasp`'s ranking by score
-(order='score', top_k), and the surface point cloud of `extract_surface_points_from_volume` (SurfaceExtractor, write_ply)."""
+(order='score', top_k), and the surface point cloud of `extract_surface_points_from_volume` (SurfaceExtractor, write_ply).  The
+triangle mesh of the volume's iso-surface (MeshExtractor, csrc/gnr_mesh.hip) has no counterpart in the reference."""
 import ctypes as C
 
 import numpy as np
@@ -161,9 +162,81 @@ def unit_normals(gradient):
     return np.divide(g, n, out=np.zeros_like(g), where=n > 0)
 
 
-def write_ply(path, points, colors, normals=None):
+def mesh_bounds(R):
+    """The most vertices and triangles the surface mesh of an [R,R,R] volume can have: one vertex per cell, two triangles per interior
+    edge.  (At least one row each: R = 2 has no interior edge and a buffer of no rows is refused.)"""
+    return (R - 1) ** 3, max(1, 6 * (R - 1) * (R - 2) ** 2)
+
+
+class MeshExtractor:
+    """The indexed triangle mesh of the iso-surface vol = iso of B volumes at once, on the device (gnr_surface_mesh_fwd: naive surface
+    nets; include/gnr.h has the statement).  No reference counterpart."""
+
+    def __init__(self, device='cuda:0'):
+        self.L = _lib.lib()
+        if not torch.cuda.is_available():
+            raise _lib.GnrError('the HIP surface mesh needs a ROCm GPU; there is no CPU fallback')
+        self.device = torch.device(device)
+        self._ws = None
+
+    def __call__(self, vol, iso=0.0, scale=0.3 / 40, origin=(0.0, 0.0, 0.0), max_vertices=None, max_faces=None, gradient=None):
+        """vol [B,R,R,R] (or [B,1,R,R,R], or one [R,R,R]), 2 <= R <= 256  ->  dict of device tensors: count [B,2] int32 (vertices,
+        triangles: the true totals); vertices [B,max_vertices,3] float64 = origin + (voxel-index position) * scale, one per
+        sign-changing cell in ascending cell index; faces [B,max_faces,3] int32, rows of `vertices`, normals towards increasing vol.
+        Rows beyond count[b] are undefined.  max_vertices / max_faces = None: the exact upper bounds (mesh_bounds), nothing is
+        truncated.  gradient [B,R,R,R,3] (HotPath.sample_volume_gradient): adds `gradient` [B,max_vertices,3] float32, the volume's
+        rows interpolated to the vertices like the positions (not normalised)."""
+        d = self.device
+        vol = torch.as_tensor(vol, dtype=torch.float32, device=d).contiguous()
+        R = vol.shape[-1]
+        if vol.dim() < 3 or tuple(vol.shape[-3:]) != (R, R, R) or vol.numel() % R ** 3:
+            raise ValueError(f'vol must be [B,R,R,R], got {tuple(vol.shape)}')
+        B = vol.numel() // R ** 3
+        bv, bf = mesh_bounds(R)
+        MV, MF = bv if max_vertices is None else int(max_vertices), bf if max_faces is None else int(max_faces)
+        p = _lib.GnrMeshParams()
+        p.iso, p.scale = float(iso), float(scale)
+        p.origin[:] = [float(c) for c in origin]
+        need = self.L.gnr_surface_mesh_workspace_bytes(B, R)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=d)
+        out = {'count': torch.empty(B, 2, dtype=torch.int32, device=d), 'vertices': torch.empty(B, max(MV, 0), 3, dtype=torch.float64, device=d),
+               'faces': torch.empty(B, max(MF, 0), 3, dtype=torch.int32, device=d)}
+        g = None
+        if gradient is not None:
+            g = torch.as_tensor(gradient, dtype=torch.float32, device=d).contiguous()
+            if tuple(g.shape) != (B, R, R, R, 3):
+                raise ValueError(f'gradient must be [{B},{R},{R},{R},3], got {tuple(g.shape)}')
+            out['gradient'] = torch.empty(B, max(MV, 0), 3, dtype=torch.float32, device=d)
+        rc = self.L.gnr_surface_mesh_fwd(vol.data_ptr(), None if g is None else g.data_ptr(), B, R, C.byref(p), out['count'].data_ptr(),
+                                         out['vertices'].data_ptr(), out['faces'].data_ptr(),
+                                         None if g is None else out['gradient'].data_ptr(), MV, MF, self._ws.data_ptr(),
+                                         self._ws.numel(), C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+        _lib.check(rc, 'gnr_surface_mesh_fwd')
+        return out
+
+
+def mesh_from_extraction(res, b=0):
+    """Scene b of a MeshExtractor result -> numpy dict: `vertices` [N,3] float64, `faces` [F,3] int64; a result with `gradient` adds
+    `gradient` [N,3] float32 (the device's rows) and `normals` [N,3] float64 = g / |g| (unit_normals, as for the cloud).  Raises when
+    a buffer held fewer rows than the scene has vertices or triangles."""
+    nv, nf = (int(c) for c in res['count'][b].tolist())
+    if nv > res['vertices'].shape[1]:
+        raise _lib.GnrError(f'{nv} mesh vertices but the buffers hold {res["vertices"].shape[1]}: raise max_vertices')
+    if nf > res['faces'].shape[1]:
+        raise _lib.GnrError(f'{nf} mesh triangles but the buffers hold {res["faces"].shape[1]}: raise max_faces')
+    out = {'vertices': res['vertices'][b, :nv].cpu().numpy(), 'faces': res['faces'][b, :nf].cpu().numpy().astype(np.int64)}
+    if 'gradient' in res:
+        out['gradient'] = res['gradient'][b, :nv].cpu().numpy()
+        out['normals'] = unit_normals(out['gradient'])
+    return out
+
+
+def write_ply(path, points, colors, normals=None, faces=None):
     """A point cloud as an ASCII PLY 1.0 file (draw_utils.py:382 writes open3d's): x y z as float64, colours in [0, 1] as uchar;
-    normals [N,3]: nx ny nz as float64 between them (open3d's property order).  Without normals the file is what it was before."""
+    normals [N,3]: nx ny nz as float64 between them (open3d's property order).  faces [F,3]: the points are a mesh's vertices and
+    the file gains `element face F` with `property list uchar int vertex_indices` and a row "3 i j k" per triangle.  Without
+    normals and faces the file is what it was before."""
     points, colors = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(colors, np.float64).reshape(-1, 3)
     if len(points) != len(colors):
         raise ValueError(f'{len(points)} points but {len(colors)} colours')
@@ -171,18 +244,27 @@ def write_ply(path, points, colors, normals=None):
         normals = np.asarray(normals, np.float64).reshape(-1, 3)
         if len(normals) != len(points):
             raise ValueError(f'{len(points)} points but {len(normals)} normals')
+    if faces is not None:
+        faces = np.asarray(faces, np.int64).reshape(-1, 3)
+        if len(faces) and (faces.min() < 0 or faces.max() >= len(points)):
+            raise ValueError(f'faces name vertices outside 0..{len(points) - 1}')
     rgb = np.clip(np.floor(colors * 255.0 + 0.5), 0, 255).astype(np.uint8)
     with open(path, 'w') as f:
         f.write('ply\nformat ascii 1.0\ncomment graspnerf_amd surface cloud\n'
                 f'element vertex {len(points)}\nproperty double x\nproperty double y\nproperty double z\n'
                 + ('property double nx\nproperty double ny\nproperty double nz\n' if normals is not None else '') +
-                'property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
+                'property uchar red\nproperty uchar green\nproperty uchar blue\n'
+                + (f'element face {len(faces)}\nproperty list uchar int vertex_indices\n' if faces is not None else '') +
+                'end_header\n')
         if normals is None:
             for (x, y, z), (r, g, b) in zip(points.tolist(), rgb.tolist()):
                 f.write(f'{x!r} {y!r} {z!r} {r} {g} {b}\n')
         else:
             for (x, y, z), (nx, ny, nz), (r, g, b) in zip(points.tolist(), normals.tolist(), rgb.tolist()):
                 f.write(f'{x!r} {y!r} {z!r} {nx!r} {ny!r} {nz!r} {r} {g} {b}\n')
+        if faces is not None:
+            for i, j, k in faces.tolist():
+                f.write(f'3 {i} {j} {k}\n')
 
 
 def grasps_from_selection(sel, b=0, voxel_size=0.3 / 40, seed=None):

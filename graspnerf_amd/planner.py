@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from .renderer import GraspNeRF
-from .grasp_post import GRASP_UTILS_PROCESS, GraspSelector, SurfaceExtractor, grasps_from_selection, surface_from_extraction
+from .grasp_post import GRASP_UTILS_PROCESS, GraspSelector, MeshExtractor, SurfaceExtractor, grasps_from_selection, mesh_from_extraction, \
+    surface_from_extraction
 from .ingest import axis_tables
 from .planner_session import PlannerSession
 from .tsdf import create_tsdf
@@ -108,18 +109,33 @@ REAL_BBOX3D = ((-0.15, -0.15, 0.0), (0.15, 0.15, 0.3))                          
 REAL_DEPTH_RANGE, REAL_QUE_ID, REAL_VOXEL_SIZE = (0.2, 0.8), 3, 0.3 / 40                                  # grasp_utils.py:122,137,146
 
 
-def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, **kw):
+def _mesh_params(mesh):
+    """plan_real's `mesh` argument -> None, or the surface_mesh parameters of a PlannerSession (True: iso = 0, the exact upper bounds)."""
+    if mesh is None or mesh is False:
+        return None
+    mesh = {} if mesh is True else dict(mesh)
+    unknown = sorted(set(mesh) - {'iso', 'max_vertices', 'max_faces'})
+    if unknown:
+        raise TypeError(f'unknown mesh parameters {unknown}; mesh is True or dict(iso=..., max_vertices=..., max_faces=...)')
+    return {'iso': 0.0, 'max_vertices': None, 'max_faces': None, **mesh}
+
+
+def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, mesh=False,
+                 **kw):
     """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud
-    (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True))."""
+    (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True);  mesh: plan_real's, with the
+    triangle mesh of the volume's iso-surface in the graph)."""
     if normals:
         kw = dict(kw, surface_normals=True)
+    if _mesh_params(mesh) is not None:
+        kw = dict(kw, surface_mesh=_mesh_params(mesh))
     return PlannerSession(net, n_views, src_hw, img_wh, max_grasps=max_grasps, voxel_size=REAL_VOXEL_SIZE,
                           surface=dict(rg=tuple(surface_rg)), order='score' if order == 'score' else 'index', top_k=top_k,
                           **GRASP_UTILS_PROCESS, **kw)
 
 
 def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None,
-              normals=False):
+              normals=False, mesh=False):
     """`run_real` (grasp_utils.py:119-151) without its file output: one plan from camera frames.
     images: V >= 4 uint8 frames [h,w,3] (list or array); extrinsics: V world->camera [3|4,4]; intrinsic [3,3], the same for every view.
     run_real's workspace box, depth range (0.2, 0.8) and query view 3; grasp_utils.process's thresholds (GRASP_UTILS_PROCESS),
@@ -130,7 +146,12 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         cloud dict: points [N,3] float64, colors [N,3], index [N,3] of the voxels with surface_rg[0] < tsdf < surface_rg[1];  seconds).
     normals=True: the cloud also carries `gradient` [N,3] float32 -- the rows of the SDF gradient volume at its voxels
     (NeuralRayRenderer.sample_volume_gradient: the reference's summed VJP, world frame) -- and `normals` [N,3] float64 = g / |g|;
-    a session must have been built with real_session(normals=True).  The grasps do not depend on the switch."""
+    a session must have been built with real_session(normals=True).  The grasps do not depend on the switch.
+    mesh=True: the cloud dict gains `mesh` = {vertices [N,3] float64, faces [F,3] int64}: the triangle mesh of the surface tsdf = 0
+    (grasp_post.MeshExtractor, naive surface nets; no counterpart in run_real) in the cloud's own frame -- origin 0, REAL_VOXEL_SIZE per
+    voxel, so it overlays `points` -- with triangle normals towards increasing tsdf; with normals=True also `gradient` [N,3] float32 and
+    `normals` [N,3] float64 at the vertices.  mesh=dict(iso=..., max_vertices=..., max_faces=...) sets another level or smaller
+    buffers; a session must have been built with the same real_session(mesh=...).  Grasps and cloud do not depend on it."""
     if order not in ('permuted', 'score'):
         raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
     ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
@@ -146,11 +167,14 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         sp, su = session.selector_params, session.surface_params
         want = dict(GRASP_UTILS_PROCESS, order=sel_order, top_k=top_k)
         if session.net is not net or su is None or tuple(su['rg']) != tuple(surface_rg) or any(sp[k] != v for k, v in want.items()) \
-                or session.voxel_size != REAL_VOXEL_SIZE or bool(normals) != bool(getattr(session, 'surface_normals', False)):
-            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range or normals '
+                or session.voxel_size != REAL_VOXEL_SIZE or bool(normals) != bool(getattr(session, 'surface_normals', False)) \
+                or _mesh_params(mesh) != getattr(session, 'mesh_params', None):
+            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range, normals or mesh '
                              '(build it with planner.real_session)')
         g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
         tsdf_vol, cloud = g.pop('volumes')[0], session.cloud
+        if session.mesh_params is not None:
+            cloud = dict(cloud, mesh=session.mesh)
     else:
         dev = next(net.parameters()).device
         frames = np.stack([np.asarray(f) for f in images], 0)
@@ -174,6 +198,10 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         res = SurfaceExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), rg=surface_rg,                # grasp_utils.py:149
                                     **({'gradient': grad} if normals else {}))
         cloud = surface_from_extraction(res, 0)
+        if _mesh_params(mesh) is not None:
+            res = MeshExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), **_mesh_params(mesh), scale=REAL_VOXEL_SIZE,
+                                     **({'gradient': grad} if normals else {}))
+            cloud['mesh'] = mesh_from_extraction(res, 0)
     tsdf_vol = np.asarray(tsdf_vol).reshape(tsdf_vol.shape[-3:])
     n = len(g['score'])
     if order == 'permuted' and n > 0:                                                                     # grasp_utils.py:144-147

@@ -13,13 +13,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import GraspSelector, SurfaceExtractor, grasps_from_selection, unit_normals
+from .grasp_post import GraspSelector, MeshExtractor, SurfaceExtractor, grasps_from_selection, mesh_bounds, unit_normals
 from .ingest import DeviceIngest
 
 _SELECTOR_DEFAULTS = {k: p.default for k, p in inspect.signature(GraspSelector.__call__).parameters.items()
                       if p.default is not inspect.Parameter.empty}
 _SURFACE_DEFAULTS = {k: p.default for k, p in inspect.signature(SurfaceExtractor.__call__).parameters.items()
                      if p.default is not inspect.Parameter.empty and k != 'gradient'}      # (the gradient volume is the session's: surface_normals)
+_MESH_DEFAULTS = dict(iso=0.0, max_vertices=None, max_faces=None)
 _SEG = 64                                                    # floats: every camera block starts on a 256-byte boundary
 
 
@@ -40,11 +41,15 @@ class PlannerSession:
     output `surface`) and are recomputed on the host as index * scale, which is the same float64 product.
     surface_normals=True (needs `surface`): the SDF gradient volume (NeuralRayRenderer.sample_volume_gradient) and the gather of its
     rows at the cloud's voxels are captured in the graph too; the gradient rows are read back in the same sized step as the index
-    rows, and self.cloud gains `gradient` [N,3] float32 and `normals` [N,3] float64 (g / |g| on the host).  A session built
-    without any of these records the graph it always recorded."""
+    rows, and self.cloud gains `gradient` [N,3] float32 and `normals` [N,3] float64 (g / |g| on the host).
+    surface_mesh = dict(iso=..., max_vertices=..., max_faces=...) ({} for iso = 0 and the exact upper bounds): the triangle mesh of
+    the iso-surface of the volume (grasp_post.MeshExtractor) is captured in the graph too, in the cloud's frame (origin 0, the cloud's
+    scale); its two counts come with the selection, the stored vertex and face rows in the same sized step as the cloud's rows, and
+    self.mesh holds the last plan's mesh (vertices float64, faces int64; with surface_normals=True also `gradient` and `normals` at the
+    vertices).  A session built without any of these records the graph it always recorded."""
 
     def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
-                 surface=None, surface_normals=False, **selector_params):
+                 surface=None, surface_normals=False, surface_mesh=None, **selector_params):
         cfg = net.nr_net.cfg
         if surface_normals and surface is None:
             raise ValueError('surface_normals=True needs the surface cloud: pass surface=dict(...) ({} for its defaults)')
@@ -59,6 +64,10 @@ class PlannerSession:
             unknown = sorted(set(surface) - set(_SURFACE_DEFAULTS))
             if unknown:
                 raise TypeError(f'unknown surface parameters {unknown}; SurfaceExtractor takes {sorted(_SURFACE_DEFAULTS)}')
+        if surface_mesh is not None:
+            unknown = sorted(set(surface_mesh) - set(_MESH_DEFAULTS))
+            if unknown:
+                raise TypeError(f'unknown surface_mesh parameters {unknown}; it takes {sorted(_MESH_DEFAULTS)}')
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise _lib.GnrError('PlannerSession needs the model on a ROCm GPU; there is no CPU fallback')
@@ -89,13 +98,14 @@ class PlannerSession:
         self._d = view(self._d_cam)
         self.images = torch.zeros(V, 3, H, W, dtype=torch.float32, device=dev)       # the ingested frames of the last plan
         # the selection, packed for one read-back: count | index [M,3] | score [M] | quat [M,4] | width [M], 4-byte words
-        # (+ the cloud's row count, when the session extracts one)
+        # (+ the cloud's row count, when the session extracts one; + the mesh's vertex and triangle counts, likewise)
         self.surface_params = None if surface is None else {**_SURFACE_DEFAULTS, **surface}
         self.surface_normals = bool(surface_normals)
-        words = 1 + 9 * M + (0 if surface is None else 1)
+        self.mesh_params = None if surface_mesh is None else {**_MESH_DEFAULTS, **surface_mesh}
+        words = 1 + 9 * M + (0 if surface is None else 1) + (0 if surface_mesh is None else 2)
         self._d_out = torch.zeros(words, dtype=torch.int32, device=dev)
         self._h_out = torch.zeros(words, dtype=torch.int32, pin_memory=True)
-        self.selection = self.cloud = None
+        self.selection = self.cloud = self.mesh = None
         if surface is not None:
             R = int(cfg['volume_resolution'])
             self.surface = SurfaceExtractor(dev)
@@ -104,6 +114,15 @@ class PlannerSession:
             self._h_surf_colors = torch.zeros(self._surface_rows, 3, dtype=torch.float32, pin_memory=True)
             if self.surface_normals:
                 self._h_surf_grad = torch.zeros(self._surface_rows, 3, dtype=torch.float32, pin_memory=True)
+        if surface_mesh is not None:
+            bv, bf = mesh_bounds(int(cfg['volume_resolution']))
+            mp = self.mesh_params
+            self.mesher = MeshExtractor(dev)
+            self._mesh_rows = (bv if mp['max_vertices'] is None else int(mp['max_vertices']), bf if mp['max_faces'] is None else int(mp['max_faces']))
+            self._h_mesh_vertices = torch.zeros(self._mesh_rows[0], 3, dtype=torch.float64, pin_memory=True)
+            self._h_mesh_faces = torch.zeros(self._mesh_rows[1], 3, dtype=torch.int32, pin_memory=True)
+            if self.surface_normals:
+                self._h_mesh_grad = torch.zeros(self._mesh_rows[0], 3, dtype=torch.float32, pin_memory=True)
         self.captures = 0
         self._set_example_cameras()
         self._capture()
@@ -135,10 +154,15 @@ class PlannerSession:
         for k, a, b in (('score', 1 + 3 * M, 1 + 4 * M), ('quat', 1 + 4 * M, 1 + 8 * M), ('width', 1 + 8 * M, 1 + 9 * M)):
             o[a:b].copy_(sel[k].reshape(-1).view(torch.int32))
         out = {'volume': vol, 'qual': q, 'rot': r, 'width': w, 'sel_qual': sel['qual']}
+        grad = nr.sample_volume_gradient(ref, _prep=prep) if self.surface_normals else None
         if self.surface_params is not None:
-            grad = nr.sample_volume_gradient(ref, _prep=prep) if self.surface_normals else None
             out['surface'] = self.surface(vol, **self.surface_params, **({'gradient': grad} if self.surface_normals else {}))
             o[1 + 9 * M:2 + 9 * M].copy_(out['surface']['count'])
+        if self.mesh_params is not None:
+            at = 1 + 9 * M + (0 if self.surface_params is None else 1)
+            out['mesh'] = self.mesher(vol, **self.mesh_params, scale=(self.surface_params or _SURFACE_DEFAULTS)['scale'],
+                                      **({'gradient': grad} if self.surface_normals else {}))
+            o[at:at + 2].copy_(out['mesh']['count'].reshape(-1))
         return out
 
     def _state(self):
@@ -195,25 +219,46 @@ class PlannerSession:
             np.copyto(dst, f)
         self._d_frames.copy_(self._h_frames, non_blocking=True)
 
-    def _read_cloud(self, count, st):
-        """The stored rows of the cloud: one sized copy of the index (and of the colours in value-map mode)."""
-        if count > self._surface_rows:
-            raise _lib.GnrError(f'{count} surface voxels but the buffers hold {self._surface_rows}: raise surface max_points')
-        sp, surf = self.surface_params, self._out['surface']
-        self._h_surf_index[:count].copy_(surf['index'][0, :count], non_blocking=True)
-        if sp['color'] is None:
-            self._h_surf_colors[:count].copy_(surf['colors'][0, :count], non_blocking=True)
-        if self.surface_normals:
-            self._h_surf_grad[:count].copy_(surf['gradient'][0, :count], non_blocking=True)
+    def _read_rows(self, h, st):
+        """The stored rows of the cloud and of the mesh, sized by the counts that came with the selection: one copy of the cloud's index
+        (and of its colours in value-map mode, of its gradient rows with normals), one each of the mesh's vertex, face (and gradient)
+        rows, then one wait."""
+        at = 1 + 9 * self.max_grasps
+        count = nv = nf = None
+        if self.surface_params is not None:
+            count, at = int(h[at]), at + 1
+            if count > self._surface_rows:
+                raise _lib.GnrError(f'{count} surface voxels but the buffers hold {self._surface_rows}: raise surface max_points')
+            sp, surf = self.surface_params, self._out['surface']
+            self._h_surf_index[:count].copy_(surf['index'][0, :count], non_blocking=True)
+            if sp['color'] is None:
+                self._h_surf_colors[:count].copy_(surf['colors'][0, :count], non_blocking=True)
+            if self.surface_normals:
+                self._h_surf_grad[:count].copy_(surf['gradient'][0, :count], non_blocking=True)
+        if self.mesh_params is not None:
+            nv, nf = int(h[at]), int(h[at + 1])
+            if nv > self._mesh_rows[0] or nf > self._mesh_rows[1]:
+                raise _lib.GnrError(f'{nv} mesh vertices and {nf} triangles but the buffers hold {self._mesh_rows[0]} and '
+                                    f'{self._mesh_rows[1]}: raise surface_mesh max_vertices / max_faces')
+            mesh = self._out['mesh']
+            self._h_mesh_vertices[:nv].copy_(mesh['vertices'][0, :nv], non_blocking=True)
+            self._h_mesh_faces[:nf].copy_(mesh['faces'][0, :nf], non_blocking=True)
+            if self.surface_normals:
+                self._h_mesh_grad[:nv].copy_(mesh['gradient'][0, :nv], non_blocking=True)
         st.synchronize()
-        index = self._h_surf_index[:count].numpy().astype(np.int64)
-        colors = self._h_surf_colors[:count].numpy().astype(np.float64) if sp['color'] is None else \
-            np.array([sp['color']], np.float64).repeat(count, axis=0)
-        cloud = {'count': count, 'index': index, 'points': index.astype(np.float64) * float(sp['scale']), 'colors': colors}
-        if self.surface_normals:
-            cloud['gradient'] = self._h_surf_grad[:count].numpy().copy()
-            cloud['normals'] = unit_normals(cloud['gradient'])
-        return cloud
+        if count is not None:
+            index = self._h_surf_index[:count].numpy().astype(np.int64)
+            colors = self._h_surf_colors[:count].numpy().astype(np.float64) if sp['color'] is None else \
+                np.array([sp['color']], np.float64).repeat(count, axis=0)
+            self.cloud = {'count': count, 'index': index, 'points': index.astype(np.float64) * float(sp['scale']), 'colors': colors}
+            if self.surface_normals:
+                self.cloud['gradient'] = self._h_surf_grad[:count].numpy().copy()
+                self.cloud['normals'] = unit_normals(self.cloud['gradient'])
+        if nv is not None:
+            self.mesh = {'vertices': self._h_mesh_vertices[:nv].numpy().copy(), 'faces': self._h_mesh_faces[:nf].numpy().astype(np.int64)}
+            if self.surface_normals:
+                self.mesh['gradient'] = self._h_mesh_grad[:nv].numpy().copy()
+                self.mesh['normals'] = unit_normals(self.mesh['gradient'])
 
     def plan(self, frames_u8, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497)),
              seed=None, return_volumes=False):
@@ -243,8 +288,8 @@ class PlannerSession:
         self.selection = {'count': h[0:1], 'index': h[1:1 + 3 * M].view(1, M, 3), 'score': f(1 + 3 * M, 1 + 4 * M),
                           'quat': f(1 + 4 * M, 1 + 8 * M, 4), 'width': f(1 + 8 * M, 1 + 9 * M),
                           'order': self.selector_params['order'], 'top_k': self.selector_params['top_k']}
-        if self.surface_params is not None:
-            self.cloud = self._read_cloud(int(h[1 + 9 * M]), st)
+        if self.surface_params is not None or self.mesh_params is not None:
+            self._read_rows(h, st)
             dt = time.time() - t0
         grasps = grasps_from_selection(self.selection, 0, self.voxel_size, seed)
         if return_volumes:

@@ -671,6 +671,42 @@ int gnr_surface_points_fwd(const float* vol, int B, int R, const GnrSurfaceParam
 int gnr_surface_gradient_fwd(const float* grad, const int* index, const int* count, int B, int R, int max_points,
                              float* out /*[B,max_points,3]*/, void* stream);
 
+/* gnr_surface_mesh_fwd: an indexed triangle mesh of the iso-surface vol = iso of B volumes [B,R,R,R], 2 <= R <= 256 (predicted SDF
+ * volumes and fused TSDF grids alike), by naive surface nets.  No reference counterpart; tests/mesh_reference.py is the same
+ * statement in numpy and the call produces its bits.
+ *   inside     voxel p is inside iff vol[p] < iso, compared in float32 (a value equal to iso is outside).
+ *   cells      cell q in [0,R-2]^3 has the corners q + {0,1}^3 and is active iff they are not all on one side.
+ *   vertex     of an active cell: its 12 edges in the order  for a in (0,1,2): b, c = (a+1)%3, (a+2)%3; for dc in (0,1): for db in (0,1):
+ *              from p0 = q + db e_b + dc e_c to p1 = p0 + e_a.  Where the ends differ in the inside test: t = ((double)iso - v0) / (v1 - v0),
+ *              crossing point p0 + t e_a in voxel-index units.  The points are summed sequentially in that order per component,
+ *              mean = sum / n, vertex = origin + mean * scale (a multiplication, then an addition), all float64.
+ *              Vertex order: ascending cell index x (R-1)^2 + y (R-1) + z.
+ *   faces      edge (p, a) from voxel p to p + e_a is interior iff p_a <= R-2, 1 <= p_b <= R-2 and 1 <= p_c <= R-2.  A sign-changing
+ *              interior edge gives one quad over the four cells around it, named by minimum corner: q0 = p - e_b - e_c, q1 = p - e_c,
+ *              q2 = p, q3 = p - e_b.  p inside (vol rises along +a): triangles (q0,q1,q2), (q0,q2,q3); otherwise (q0,q2,q1), (q0,q3,q2);
+ *              entries are the cells' vertex rows, int32.  Face order: ascending (voxel index of p) * 3 + a, a quad's two triangles
+ *              adjacent.  Triangle normals point towards increasing vol: out of the object for a signed distance.
+ *   gradient   optional: with grad [B,R,R,R,3] float32, gradient[vertex] = the mean over the same edges in the same order of
+ *              g0 + t (g1 - g0), float64 per component, rounded once to float32; not normalised.  grad and gradient are both
+ *              given or both NULL.
+ *   count [B,2]              vertices and triangles per scene: the true totals, also beyond max_v / max_f
+ *   vertices [B,max_v,3]     float64;   faces [B,max_f,3] int32;   gradient [B,max_v,3] float32
+ * Rows beyond a cap and rows beyond the count are left untouched; a face names the true row of a vertex even when that row is beyond
+ * max_v.  At most (R-1)^3 vertices and 6 (R-1) (R-2)^2 triangles per scene.  1 <= B <= 65535, max_v, max_f >= 1; iso, scale and origin
+ * finite.  The volume is finite (sample_volume clips to [-1,1]); the result on a NaN or an infinity is undefined.
+ * Asynchronous on `stream`, no atomics, no allocation, no synchronisation (it can be captured in a graph); a refused call has
+ * launched nothing.  The workspace need not be cleared between calls.                                                       */
+typedef struct GnrMeshParams {
+    float iso;
+    double scale;                              /* 0.3 / 40: the surface cloud's                         */
+    double origin[3];
+} GnrMeshParams;
+size_t gnr_surface_mesh_workspace_bytes(int B, int R);
+int gnr_surface_mesh_fwd(const float* vol, const float* grad /*NULL: no normals*/, int B, int R, const GnrMeshParams* params,
+                         int* count /*[B,2]: vertices, triangles*/, double* vertices /*[B,max_v,3]*/, int* faces /*[B,max_f,3]*/,
+                         float* gradient /*[B,max_v,3], NULL iff grad is*/, int max_v, int max_f, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
