@@ -78,6 +78,15 @@ class GnrMeshParams(C.Structure):
     _fields_ = [('iso', C.c_float), ('scale', C.c_double), ('origin', C.c_double * 3)]
 
 
+class GnrRaycastParams(C.Structure):
+    _fields_ = [('B', C.c_int), ('V', C.c_int), ('h', C.c_int), ('w', C.c_int), ('R', C.c_int), ('bisections', C.c_int),
+                ('iso', C.c_float), ('scale', C.c_double), ('step', C.c_double), ('near_s', C.c_double), ('far_s', C.c_double),
+                ('origin', C.c_double * 3)]
+
+
+GNR_RAYCAST_MAX_SAMPLES = 65536
+
+
 class GnrError(RuntimeError):
     pass
 
@@ -261,6 +270,8 @@ def lib():
     L.gnr_surface_mesh_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GnrMeshParams)] + [C.c_void_p] * 4 + \
                                       [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.gnr_surface_mesh_fwd.restype = C.c_int
+    L.gnr_volume_raycast_fwd.argtypes = [C.POINTER(GnrRaycastParams)] + [C.c_void_p] * 7
+    L.gnr_volume_raycast_fwd.restype = C.c_int
     L.gnr_tsdf_reset.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnr_tsdf_reset.restype = C.c_int
     L.gnr_tsdf_integrate.argtypes = [C.POINTER(GnrTsdfParams)] + [C.c_void_p] * 7
@@ -325,6 +336,7 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd',
             'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd',
             'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid', 'gnr_surface_mesh_workspace_bytes', 'gnr_surface_mesh_fwd',
+            'gnr_volume_raycast_fwd',
             'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 

@@ -16,6 +16,7 @@ from .grasp_post import GRASP_UTILS_PROCESS, GraspSelector, MeshExtractor, Surfa
     surface_from_extraction
 from .ingest import axis_tables
 from .planner_session import PlannerSession
+from .raycast import RAYCAST_DEFAULTS, VolumeRaycaster, images_from_raycast
 from .tsdf import create_tsdf
 
 
@@ -120,11 +121,50 @@ def _mesh_params(mesh):
     return {'iso': 0.0, 'max_vertices': None, 'max_faces': None, **mesh}
 
 
+def _depth_params(volume_depth):
+    """plan_real's `volume_depth` argument -> None, or the ray cast's parameters (True: the plan's own cameras and image size, iso = 0,
+    half-voxel steps, four bisections);  extrinsics -> float32 [V',3,4], intrinsic -> float32 [3,3], hw -> (h, w)."""
+    if volume_depth is None or volume_depth is False:
+        return None
+    vd = {} if volume_depth is True else dict(volume_depth)
+    known = {'extrinsics', 'intrinsic', 'hw', *RAYCAST_DEFAULTS}
+    unknown = sorted(set(vd) - known)
+    if unknown:
+        raise TypeError(f'unknown volume_depth parameters {unknown}; volume_depth is True or dict(extrinsics=..., intrinsic=..., hw=..., '
+                        f'iso=..., step=..., bisections=...)')
+    out = {'extrinsics': None, 'intrinsic': None, 'hw': None, **RAYCAST_DEFAULTS, **vd}
+    if out['extrinsics'] is not None:
+        ext = np.stack([np.asarray(e, np.float32) for e in out['extrinsics']], 0)
+        if ext.ndim != 3 or ext.shape[1:] not in ((3, 4), (4, 4)):
+            raise ValueError(f'volume_depth extrinsics must be V world->camera [3|4,4], got {ext.shape}')
+        out['extrinsics'] = np.ascontiguousarray(ext[:, :3, :])
+    if out['intrinsic'] is not None:
+        out['intrinsic'] = np.ascontiguousarray(np.asarray(out['intrinsic'], np.float32).reshape(3, 3))
+    if out['hw'] is not None:
+        out['hw'] = (int(out['hw'][0]), int(out['hw'][1]))
+    out['iso'], out['step'], out['bisections'] = float(out['iso']), float(out['step']), int(out['bisections'])
+    return out
+
+
+def _same_depth_params(a, b):
+    if a is None or b is None:
+        return a is None and b is None
+    same = lambda x, y: (x is None and y is None) if (x is None or y is None) else np.array_equal(x, y)
+    return all(same(a[k], b.get(k)) for k in a)
+
+
+def real_volume_origin():
+    """World position of voxel (0,0,0)'s centre of run_real's volume: the lattice origin of its ray cast."""
+    return np.asarray(REAL_BBOX3D[0], np.float64) + 0.5 * REAL_VOXEL_SIZE
+
+
 def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, mesh=False,
-                 **kw):
+                 volume_depth=False, **kw):
     """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud
     (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True);  mesh: plan_real's, with the
-    triangle mesh of the volume's iso-surface in the graph)."""
+    triangle mesh of the volume's iso-surface in the graph;  volume_depth: plan_real's, with the ray cast of the volume in the graph)."""
+    if _depth_params(volume_depth) is not None:
+        kw = dict(kw, volume_depth=dict(_depth_params(volume_depth), origin=tuple(real_volume_origin())))
     if normals:
         kw = dict(kw, surface_normals=True)
     if _mesh_params(mesh) is not None:
@@ -135,7 +175,7 @@ def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, sur
 
 
 def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None,
-              normals=False, mesh=False):
+              normals=False, mesh=False, volume_depth=False):
     """`run_real` (grasp_utils.py:119-151) without its file output: one plan from camera frames.
     images: V >= 4 uint8 frames [h,w,3] (list or array); extrinsics: V world->camera [3|4,4]; intrinsic [3,3], the same for every view.
     run_real's workspace box, depth range (0.2, 0.8) and query view 3; grasp_utils.process's thresholds (GRASP_UTILS_PROCESS),
@@ -151,9 +191,16 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     (grasp_post.MeshExtractor, naive surface nets; no counterpart in run_real) in the cloud's own frame -- origin 0, REAL_VOXEL_SIZE per
     voxel, so it overlays `points` -- with triangle normals towards increasing tsdf; with normals=True also `gradient` [N,3] float32 and
     `normals` [N,3] float64 at the vertices.  mesh=dict(iso=..., max_vertices=..., max_faces=...) sets another level or smaller
-    buffers; a session must have been built with the same real_session(mesh=...).  Grasps and cloud do not depend on it."""
+    buffers; a session must have been built with the same real_session(mesh=...).  Grasps and cloud do not depend on it.
+    volume_depth=True: the cloud dict gains `volume_depth` [V,h,w] float32 -- the camera-z depth in metres (0: no surface) of the surface
+    tsdf = 0 of the volume seen from the plan's own V cameras at the network's image size (raycast.VolumeRaycaster; world frame, voxel
+    centres at REAL_BBOX3D[0] + (i + 0.5) * REAL_VOXEL_SIZE; `intrinsic` is that of the frames the network sees); with normals=True also
+    `volume_depth_normals` [V,h,w,3] float64, unit vectors, zero on a miss.  volume_depth=dict(extrinsics=..., intrinsic=..., hw=...,
+    iso=..., step=..., bisections=...) chooses other cameras, another image size or level; a session must have been built with the same
+    real_session(volume_depth=...).  Grasps, cloud and mesh do not depend on it."""
     if order not in ('permuted', 'score'):
         raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
+    vd = _depth_params(volume_depth)
     ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
     V = ext.shape[0]
     if V <= REAL_QUE_ID:
@@ -168,13 +215,16 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         want = dict(GRASP_UTILS_PROCESS, order=sel_order, top_k=top_k)
         if session.net is not net or su is None or tuple(su['rg']) != tuple(surface_rg) or any(sp[k] != v for k, v in want.items()) \
                 or session.voxel_size != REAL_VOXEL_SIZE or bool(normals) != bool(getattr(session, 'surface_normals', False)) \
-                or _mesh_params(mesh) != getattr(session, 'mesh_params', None):
-            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range, normals or mesh '
-                             '(build it with planner.real_session)')
+                or _mesh_params(mesh) != getattr(session, 'mesh_params', None) \
+                or not _same_depth_params(vd, getattr(session, 'volume_depth_params', None)):
+            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range, normals, mesh or '
+                             'volume_depth (build it with planner.real_session)')
         g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
         tsdf_vol, cloud = g.pop('volumes')[0], session.cloud
         if session.mesh_params is not None:
             cloud = dict(cloud, mesh=session.mesh)
+        if session.volume_depth_params is not None:
+            cloud = dict(cloud, **session.volume_images)
     else:
         dev = next(net.parameters()).device
         frames = np.stack([np.asarray(f) for f in images], 0)
@@ -202,6 +252,13 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
             res = MeshExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), **_mesh_params(mesh), scale=REAL_VOXEL_SIZE,
                                      **({'gradient': grad} if normals else {}))
             cloud['mesh'] = mesh_from_extraction(res, 0)
+        if vd is not None:
+            K = Ks[0] if vd['intrinsic'] is None else vd['intrinsic']
+            poses = ext[:, :3, :] if vd['extrinsics'] is None else vd['extrinsics']
+            res = VolumeRaycaster(dev)(torch.as_tensor(tsdf_vol, device=dev), poses, np.repeat(K[None], len(poses), 0),
+                                       frames.shape[1:3] if vd['hw'] is None else vd['hw'], origin=real_volume_origin(), scale=REAL_VOXEL_SIZE,
+                                       iso=vd['iso'], step=vd['step'], bisections=vd['bisections'], **({'gradient': grad} if normals else {}))
+            cloud.update(images_from_raycast(res, 0))
     tsdf_vol = np.asarray(tsdf_vol).reshape(tsdf_vol.shape[-3:])
     n = len(g['score'])
     if order == 'permuted' and n > 0:                                                                     # grasp_utils.py:144-147

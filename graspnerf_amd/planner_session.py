@@ -15,12 +15,15 @@ import torch
 from . import _lib
 from .grasp_post import GraspSelector, MeshExtractor, SurfaceExtractor, grasps_from_selection, mesh_bounds, unit_normals
 from .ingest import DeviceIngest
+from .raycast import RAYCAST_DEFAULTS, VolumeRaycaster
 
 _SELECTOR_DEFAULTS = {k: p.default for k, p in inspect.signature(GraspSelector.__call__).parameters.items()
                       if p.default is not inspect.Parameter.empty}
 _SURFACE_DEFAULTS = {k: p.default for k, p in inspect.signature(SurfaceExtractor.__call__).parameters.items()
                      if p.default is not inspect.Parameter.empty and k != 'gradient'}      # (the gradient volume is the session's: surface_normals)
 _MESH_DEFAULTS = dict(iso=0.0, max_vertices=None, max_faces=None)
+_DEPTH_DEFAULTS = dict(extrinsics=None, intrinsic=None, hw=None, origin=(-0.15 + 0.5 * 0.3 / 40, -0.15 + 0.5 * 0.3 / 40, -0.0503 + 0.5 * 0.3 / 40),
+                       **RAYCAST_DEFAULTS)
 _SEG = 64                                                    # floats: every camera block starts on a 256-byte boundary
 
 
@@ -46,10 +49,18 @@ class PlannerSession:
     the iso-surface of the volume (grasp_post.MeshExtractor) is captured in the graph too, in the cloud's frame (origin 0, the cloud's
     scale); its two counts come with the selection, the stored vertex and face rows in the same sized step as the cloud's rows, and
     self.mesh holds the last plan's mesh (vertices float64, faces int64; with surface_normals=True also `gradient` and `normals` at the
-    vertices).  A session built without any of these records the graph it always recorded."""
+    vertices).
+    volume_depth = dict(extrinsics=..., intrinsic=..., hw=..., origin=..., iso=..., step=..., bisections=...) ({} for the defaults): the
+    ray cast of the volume (raycast.VolumeRaycaster) is recorded in the graph after sample_volume.  extrinsics [V',3,4] / intrinsic [3,3] /
+    hw: the cameras and the image size; None: the plan's own V cameras -- the kernel reads them from the session's device block, which
+    every plan uploads anyway -- at the network's image size.  origin: the world position of voxel (0,0,0)'s centre (the default is that
+    of plan()'s default box; the spacing is voxel_size).  The images are read back in the cloud's sized step, and self.volume_images
+    holds the last plan's: `volume_depth` [V,h,w] float32 (metres, 0: no surface), with surface_normals=True also `volume_depth_normals`
+    [V,h,w,3] float64.
+    A session built without any of these records the graph it always recorded."""
 
     def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
-                 surface=None, surface_normals=False, surface_mesh=None, **selector_params):
+                 surface=None, surface_normals=False, surface_mesh=None, volume_depth=None, **selector_params):
         cfg = net.nr_net.cfg
         if surface_normals and surface is None:
             raise ValueError('surface_normals=True needs the surface cloud: pass surface=dict(...) ({} for its defaults)')
@@ -68,6 +79,10 @@ class PlannerSession:
             unknown = sorted(set(surface_mesh) - set(_MESH_DEFAULTS))
             if unknown:
                 raise TypeError(f'unknown surface_mesh parameters {unknown}; it takes {sorted(_MESH_DEFAULTS)}')
+        if volume_depth is not None:
+            unknown = sorted(set(volume_depth) - set(_DEPTH_DEFAULTS))
+            if unknown:
+                raise TypeError(f'unknown volume_depth parameters {unknown}; it takes {sorted(_DEPTH_DEFAULTS)}')
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise _lib.GnrError('PlannerSession needs the model on a ROCm GPU; there is no CPU fallback')
@@ -123,6 +138,22 @@ class PlannerSession:
             self._h_mesh_faces = torch.zeros(self._mesh_rows[1], 3, dtype=torch.int32, pin_memory=True)
             if self.surface_normals:
                 self._h_mesh_grad = torch.zeros(self._mesh_rows[0], 3, dtype=torch.float32, pin_memory=True)
+        self.volume_depth_params = None if volume_depth is None else {**_DEPTH_DEFAULTS, **volume_depth}
+        self.volume_images = None
+        if volume_depth is not None:
+            vd = self.volume_depth_params
+            self.raycaster = VolumeRaycaster(dev)
+            dh, dw = (H, W) if vd['hw'] is None else (int(vd['hw'][0]), int(vd['hw'][1]))
+            nv = V if vd['extrinsics'] is None else len(vd['extrinsics'])
+            self._depth_hw = (dh, dw)
+            # other cameras than the plan's own are the session's: uploaded once
+            self._depth_poses = None if vd['extrinsics'] is None else \
+                torch.from_numpy(np.ascontiguousarray(np.asarray(vd['extrinsics'], np.float32)[:, :3, :])).to(dev)
+            self._depth_Ks = None if vd['intrinsic'] is None else \
+                torch.from_numpy(np.repeat(np.asarray(vd['intrinsic'], np.float32).reshape(1, 3, 3), nv, 0)).to(dev)
+            self._h_depth = torch.zeros(nv, dh, dw, dtype=torch.float32, pin_memory=True)
+            if self.surface_normals:
+                self._h_depth_grad = torch.zeros(nv, dh, dw, 3, dtype=torch.float32, pin_memory=True)
         self.captures = 0
         self._set_example_cameras()
         self._capture()
@@ -163,6 +194,15 @@ class PlannerSession:
             out['mesh'] = self.mesher(vol, **self.mesh_params, scale=(self.surface_params or _SURFACE_DEFAULTS)['scale'],
                                       **({'gradient': grad} if self.surface_normals else {}))
             o[at:at + 2].copy_(out['mesh']['count'].reshape(-1))
+        if self.volume_depth_params is not None:
+            vd = self.volume_depth_params
+            poses = self._d['poses'] if self._depth_poses is None else self._depth_poses
+            Ks = self._d['Ks'] if self._depth_Ks is None else self._depth_Ks
+            if Ks.shape[0] != poses.shape[0]:                # the plan's own intrinsics (one per view, all equal on this route) for other cameras
+                Ks = Ks[:1].expand(poses.shape[0], 3, 3)
+            out['volume_depth'] = self.raycaster(vol, poses, Ks, self._depth_hw, origin=vd['origin'], scale=self.voxel_size, iso=vd['iso'],
+                                                 step=vd['step'], bisections=vd['bisections'],
+                                                 **({'gradient': grad} if self.surface_normals else {}))
         return out
 
     def _state(self):
@@ -222,7 +262,7 @@ class PlannerSession:
     def _read_rows(self, h, st):
         """The stored rows of the cloud and of the mesh, sized by the counts that came with the selection: one copy of the cloud's index
         (and of its colours in value-map mode, of its gradient rows with normals), one each of the mesh's vertex, face (and gradient)
-        rows, then one wait."""
+        rows, the volume's depth images when the session casts them, then one wait."""
         at = 1 + 9 * self.max_grasps
         count = nv = nf = None
         if self.surface_params is not None:
@@ -245,7 +285,16 @@ class PlannerSession:
             self._h_mesh_faces[:nf].copy_(mesh['faces'][0, :nf], non_blocking=True)
             if self.surface_normals:
                 self._h_mesh_grad[:nv].copy_(mesh['gradient'][0, :nv], non_blocking=True)
+        if self.volume_depth_params is not None:
+            self._h_depth.copy_(self._out['volume_depth']['depth'][0], non_blocking=True)
+            if self.surface_normals:
+                self._h_depth_grad.copy_(self._out['volume_depth']['gradient'][0], non_blocking=True)
         st.synchronize()
+        if self.volume_depth_params is not None:
+            self.volume_images = {'volume_depth': self._h_depth.numpy().copy()}
+            if self.surface_normals:
+                g = self._h_depth_grad.numpy()
+                self.volume_images['volume_depth_normals'] = unit_normals(g).reshape(g.shape)
         if count is not None:
             index = self._h_surf_index[:count].numpy().astype(np.int64)
             colors = self._h_surf_colors[:count].numpy().astype(np.float64) if sp['color'] is None else \
@@ -288,7 +337,7 @@ class PlannerSession:
         self.selection = {'count': h[0:1], 'index': h[1:1 + 3 * M].view(1, M, 3), 'score': f(1 + 3 * M, 1 + 4 * M),
                           'quat': f(1 + 4 * M, 1 + 8 * M, 4), 'width': f(1 + 8 * M, 1 + 9 * M),
                           'order': self.selector_params['order'], 'top_k': self.selector_params['top_k']}
-        if self.surface_params is not None or self.mesh_params is not None:
+        if self.surface_params is not None or self.mesh_params is not None or self.volume_depth_params is not None:
             self._read_rows(h, st)
             dt = time.time() - t0
         grasps = grasps_from_selection(self.selection, 0, self.voxel_size, seed)

@@ -286,7 +286,7 @@ class Trainer:
         is_better = better(key_metric_prefer)
         if self.validator.key_metric_name != key_metric_name:
             v = self.validator
-            self.validator = Validator(key_metric_name, v.loss_fn, v.eval_margin_ratio, v.ssim)
+            self.validator = Validator(key_metric_name, v.loss_fn, v.eval_margin_ratio, v.ssim, v.volume_depth)
         writer = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
         pth, best_pth = os.path.join(model_dir, 'model.pth'), os.path.join(model_dir, 'model_best.pth')
         if writer:

@@ -35,7 +35,9 @@ class TSDFVolume:
         self.sdf_trunc = 4 * self.voxel_size if sdf_trunc is None else float(sdf_trunc)
         self.depth_scale, self.depth_trunc = float(depth_scale), float(depth_trunc)
         o = np.asarray(origin.detach().cpu() if torch.is_tensor(origin) else origin, np.float32)
-        self.origin = torch.from_numpy(np.broadcast_to(o, (self.B, 3)).copy()).to(self.device)
+        self._origin_host = np.broadcast_to(o, (self.B, 3)).copy()
+        self.origin = torch.from_numpy(self._origin_host).to(self.device)
+        self._raycaster = None
         R = self.resolution
         self.tsdf = torch.empty(self.B, R, R, R, device=self.device)
         self.weight = torch.empty(self.B, R, R, R, device=self.device)
@@ -118,6 +120,26 @@ class TSDFVolume:
     def sdf_label(self):
         """[B,R,R,R]: get_grid() * 2 - 1, the trainer's sdf_gt (database.py:207-209); -1 marks a voxel without a label."""
         return self._grid(_lib.GNR_TSDF_SDF_LABEL)
+
+    def render_depth(self, intrinsic, extrinsics, hw, step=0.5, bisections=4):
+        """Depth images [B,V,h,w] (device, float32 camera-z metres, 0: no surface) of the fused grid's zero level from the cameras
+        `extrinsics` (V of them, as integrate takes them) -- the projection of the grid back into images (raycast.VolumeRaycaster).
+        The volume is tsdf where weight > 0 and 1 elsewhere: unobserved space reads as outside.  The voxel centres are the lattice:
+        origin + 0.5 * voxel_size, one voxel_size apart."""
+        from .raycast import VolumeRaycaster
+        E = extrinsics if torch.is_tensor(extrinsics) else np.asarray(extrinsics, np.float64)
+        matrices = tuple(E.shape[-2:]) in ((4, 4), (3, 4))                         # else the 7-lists [qx,qy,qz,qw,tx,ty,tz]
+        lead = E.shape[:-2] if matrices else E.shape[:-1]
+        K, P = self._cameras(intrinsic, E, lead[-1] if lead else 1)
+        if self._raycaster is None:
+            self._raycaster = VolumeRaycaster(self.device)
+        vol = torch.where(self.weight > 0, self.tsdf, torch.ones((), device=self.device))
+        half = 0.5 * self.voxel_size
+        rows = self._origin_host.astype(np.float64)
+        if (rows == rows[0]).all():
+            return self._raycaster(vol, P, K, hw, origin=rows[0] + half, scale=self.voxel_size, iso=0.0, step=step, bisections=bisections)['depth']
+        return torch.cat([self._raycaster(vol[b:b + 1], P[b:b + 1], K[b:b + 1], hw, origin=rows[b] + half, scale=self.voxel_size, iso=0.0,
+                                          step=step, bisections=bisections)['depth'].clone() for b in range(self.B)], 0)
 
 
 def create_tsdf(size, resolution, depth_imgs, intrinsic, extrinsics, device='cuda:0'):

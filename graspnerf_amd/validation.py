@@ -21,8 +21,13 @@ def better(prefer):
 
 
 class Validator:
-    def __init__(self, key_metric_name='loss_vgn', loss_fn=None, eval_margin_ratio=1.0, ssim=True):
-        """loss_fn(out, data) -> dict of terms (default trainer.train_losses);  eval_margin_ratio, ssim: metrics.frame_metrics."""
+    def __init__(self, key_metric_name='loss_vgn', loss_fn=None, eval_margin_ratio=1.0, ssim=True, volume_depth=False):
+        """loss_fn(out, data) -> dict of terms (default trainer.train_losses);  eval_margin_ratio, ssim: metrics.frame_metrics.
+        volume_depth=True adds `volume_depth_mae` per scene: the volume's camera-space error -- the mean of |depth of the surface
+        volume = 0 seen from the reference views (raycast.VolumeRaycaster) - true_depth| in metres over their pixels where the ray hit and
+        true_depth > 0, NaN when there is none -- the quantity to put beside the render passes' depth_mae.  The ray cast and the reduction
+        run on the device; the scene's box (six floats) is read on the host for the lattice's frame."""
+        self.volume_depth, self._raycaster = bool(volume_depth), None
         if key_metric_name not in _metrics.name2key_metrics:
             raise KeyError(f'unknown key metric {key_metric_name!r} (metrics.name2key_metrics)')
         self.key_metric_name = key_metric_name
@@ -38,7 +43,24 @@ class Validator:
         out = net(data)
         terms = dict(loss_fn(out, data))
         terms.update(_metrics.frame_metrics(out, data, self.eval_margin_ratio, self.ssim))
+        if self.volume_depth:
+            terms['volume_depth_mae'] = self.volume_depth_mae(out, data)
         return terms
+
+    def volume_depth_mae(self, out, data):
+        """Device scalar [1]: see __init__.  The voxel centres are sample_volume's: bbox3d[0] + (i + 0.5) * (box edge / R)."""
+        from .raycast import VolumeRaycaster, depth_mae
+        ref = data['ref_imgs_info']
+        if 'volume' not in out or 'true_depth' not in ref:
+            raise KeyError("volume_depth=True needs cfg['sample_volume'] and ref_imgs_info['true_depth']")
+        vol, true = out['volume'], ref['true_depth']
+        if self._raycaster is None or self._raycaster.device != vol.device:
+            self._raycaster = VolumeRaycaster(vol.device)
+        R = vol.shape[-1]
+        box = ref['bbox3d'].detach().to('cpu', torch.float64).numpy()
+        scale = float(box[1, 0] - box[0, 0]) / R
+        res = self._raycaster(vol, ref['poses'], ref['Ks'], true.shape[-2:], origin=box[0] + 0.5 * scale, scale=scale)
+        return depth_mae(res['depth'][0], true[:, 0].to(torch.float32)).reshape(1)
 
     def __call__(self, net, scenes, step=0):
         """scenes: the GLOBAL sequence of `data` dicts (every rank passes the same list and evaluates its sharding.scene_shard).

@@ -707,6 +707,46 @@ int gnr_surface_mesh_fwd(const float* vol, const float* grad /*NULL: no normals*
                          float* gradient /*[B,max_v,3], NULL iff grad is*/, int max_v, int max_f, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* gnr_volume_raycast_fwd: depth (and gradient) images of the iso-surface vol = iso of B volumes [B,R,R,R], 2 <= R <= 256, seen from V
+ * pinhole cameras each (poses: world->camera, OpenCV axes), one ray through every integer pixel centre (u, v).  No reference
+ * counterpart; tests/raycast_reference.py is the same statement in numpy and the call produces its bits.  poses and Ks convert to
+ * float64 before the first operation; everything below is float64, single correctly rounded operations in the order written.
+ *   ray        dc = ((u - cx) / fx, (v - cy) / fy, 1);  eye_a = -((R[0][a] t[0] + R[1][a] t[1]) + R[2][a] t[2]);
+ *              dw_a = (R[0][a] dc_x + R[1][a] dc_y) + R[2][a].  The parameter s of eye + s dw is camera-z depth in metres.
+ *   index      e = (eye - origin) / scale, d = dw / scale per component: lattice point i sits at world origin + i * scale (the mesh's
+ *              convention; a caller with voxel centres passes origin = bbox_min + 0.5 * scale).
+ *   box        slabs against [0, R-1] per axis: lo_a = min((0 - e_a) / d_a, ((R-1) - e_a) / d_a), hi_a likewise with max.  An axis with
+ *              d_a == 0 imposes no bound when 0 <= e_a <= R-1 and makes the ray miss otherwise (nothing rests on inf / NaN
+ *              arithmetic).  s0 = max(lo_x, lo_y, lo_z, near_s), s1 = min(hi_x, hi_y, hi_z, far_s); a miss unless s0 < s1 (and s1 finite).
+ *   march      ds = step / sqrt((d_x d_x + d_y d_y) + d_z d_z): `step` voxels of path per sample.  n = ceil((s1 - s0) / ds), at most
+ *              ceil(sqrt(3) (R-1) / step) + 1 (a bound that holds for every ray in exact arithmetic; it ends the loop on cameras that hold
+ *              no numbers).  s_k = min(s0 + (double)k * ds, s1), k = 0..n;  f(s) = trilinear(vol, e + s * d) - (double)iso.
+ *   trilinear  base b = clamp(floor(p), 0, R-2) per axis, t = p - b; the eight float32 corners convert to float64; lerp along z, then y,
+ *              then x, each a + t * (b - a).
+ *   hit        the first k >= 1 with f(s_{k-1}) >= 0 and f(s_k) < 0: outside -> inside, inside being the mesh's vol < iso.  A ray that
+ *              starts inside does not hit until it has left and entered again.
+ *   refine     `bisections` halvings of [A, B] = [s_{k-1}, s_k]: m = 0.5 * (A + B), f(m) < 0 replaces B, otherwise A; then one secant
+ *              step s* = A + (B - A) * (fA / (fA - fB)).  depth = (float)s*; a miss gives 0, gnr_tsdf_integrate's "no depth".
+ *   gradient   optional: with grad [B,R,R,R,3] float32, gradient[pixel] = the same trilinear form per component at e + s* d, rounded
+ *              once to float32, not normalised (the mesh's rule); 0 on a miss.  grad and gradient are both given or both NULL.
+ *   vol [B,R,R,R];  poses [B,V,3,4];  Ks [B,V,3,3];  depth [B,V,h,w];  gradient [B,V,h,w,3].  Every pixel of depth (and of gradient)
+ *   is written, nothing else is.
+ * 1 <= B <= 65535, V >= 1, h, w >= 1 (at most 2^28 tiles of 8 x 8 pixels), 0 <= bisections <= 32; scale, step finite and > 0, and step
+ * large enough that the march's bound is at most GNR_RAYCAST_MAX_SAMPLES; iso, origin finite; near_s >= 0, far_s > near_s (far_s may
+ * be infinite).  The result on a volume that holds a NaN or an infinity is undefined (but no access leaves the volume).
+ * Asynchronous on `stream`, no atomics, no workspace, no allocation, no synchronisation (it can be captured in a graph); a refused
+ * call has launched nothing.                                                                                                  */
+#define GNR_RAYCAST_MAX_SAMPLES 65536
+typedef struct GnrRaycastParams {
+    int B, V, h, w, R, bisections;
+    float iso;
+    double scale, step, near_s, far_s;
+    double origin[3];
+} GnrRaycastParams;
+int gnr_volume_raycast_fwd(const GnrRaycastParams* params, const float* vol /*[B,R,R,R]*/, const float* grad /*[B,R,R,R,3] or NULL*/,
+                           const float* poses /*[B,V,3,4]*/, const float* Ks /*[B,V,3,3]*/, float* depth /*[B,V,h,w]*/,
+                           float* gradient /*[B,V,h,w,3], NULL iff grad is*/, void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:

@@ -1,0 +1,125 @@
+"""Cost of the ray cast of SDF volumes into depth images (gnr_volume_raycast_fwd, raycast.VolumeRaycaster): full 288 x 512 frames of
+40^3 volumes from 6 cameras for B = 1 and B = 32, and of one 120^3 volume from one camera, with and without the gradient volume: p10 /
+p50 / p90 of single calls between HIP events, next to the host route to the same bits -- the volume read back and the numpy float64
+statement (tests/raycast_reference.py) on this box's CPU.  The volumes are tools/time_mesh.py's (a sphere and a torus, a clipped signed
+distance) on the real-robot route's lattice; the cameras ring the workspace at the planner's distance.
+Then the real-robot plan (planner.plan_real through planner.real_session) with and without the ray cast in the session's graph, host
+clock around the whole call, alternating: the plan's own 6 cameras at the network's image size, at iso = 0 (volume_depth=True) and with the
+level at the synthetic checkpoint's median, where more rays end on a surface.
+Usage: python tools/time_raycast.py [--calls 100] [--out profiles/volume_raycast.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import raycast_reference as RC                                               # noqa: E402
+from graspnerf_amd import planner                                            # noqa: E402
+from graspnerf_amd.raycast import VolumeRaycaster                            # noqa: E402
+from graspnerf_amd.synth import ring_cameras                                 # noqa: E402
+from time_mesh import scene                                                  # noqa: E402
+from time_tsdf import event_ms, pct                                          # noqa: E402
+
+HW = (288, 512)
+K = np.float32([[357.048, 0, 255.8], [0, 357.048, 143.8], [0, 0, 1]])
+
+
+def kernels(a):
+    dev = torch.device('cuda:0')
+    res = {'unit': 'ms per call between HIP events, p10 / p50 / p90 of single calls', 'calls': a.calls, 'image': list(HW),
+           'volumes': 'a sphere and a torus, clipped signed distance (tools/time_mesh.py), iso = 0, step 0.5, 4 bisections',
+           'device': torch.cuda.get_device_name(0)}
+    rng = np.random.default_rng(0)
+    for R, B, V in ((40, 1, 6), (40, 32, 6), (120, 1, 1)):
+        frame = dict(origin=np.asarray(planner.REAL_BBOX3D[0], np.float64) + 0.5 * 0.3 / R, scale=0.3 / R)
+        vol = torch.from_numpy(np.stack([scene(R, 0.37 * b) for b in range(B)])).to(dev)
+        grad = torch.from_numpy(rng.standard_normal((B, R, R, R, 3)).astype(np.float32)).to(dev)
+        poses = np.asarray(ring_cameras(6), np.float32)[:V, :3, :]
+        Ks = np.repeat(K[None], V, 0)
+        P, Kd = torch.from_numpy(poses).to(dev), torch.from_numpy(Ks).to(dev)
+        rc = VolumeRaycaster(dev)
+        got = rc(vol, P, Kd, HW, **frame)['depth'][0].cpu().numpy()
+        rec = {'views': V, 'rays': B * V * HW[0] * HW[1], 'hit_share_scene0': round(float((got > 0).mean()), 4),
+               'raycast_ms': pct(event_ms(lambda: rc(vol, P, Kd, HW, **frame), a.calls)),
+               'raycast_with_gradient_ms': pct(event_ms(lambda: rc(vol, P, Kd, HW, gradient=grad, **frame), a.calls))}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        host = vol[0].cpu().numpy()
+        want = RC.raycast(host, poses, Ks, *HW, **frame)
+        rec['host_route_one_scene_ms'] = {'once': round((time.perf_counter() - t0) * 1e3, 1), 'what': 'volume read back + numpy float64 statement, no gradient'}
+        rec['equals_host_route'] = bool(np.array_equal(got.view(np.uint32), want.view(np.uint32)))
+        res[f'R={R},B={B},V={V}'] = rec
+    return res
+
+
+def session(a):
+    import time_planner as TP
+    shapes = {k: tuple(v.shape) for k, v in TP.GraspNeRF(dict(TP.CFG)).state_dict().items()}
+    sd = {k: torch.from_numpy(np.asarray(v)) for k, v in TP.synth_state_dict(shapes).items()}
+    sd['vgn_net.conv_qual.bias'] = sd['vgn_net.conv_qual.bias'] + 2.5
+    sd['vgn_net.conv_width.bias'] = sd['vgn_net.conv_width.bias'] + 5.0
+    net = planner.load_model(dict(TP.CFG), sd)
+    V, hw = 6, (TP.IMG_WH[1], TP.IMG_WH[0])
+    frames = np.random.default_rng(0).integers(0, 256, (V, *hw, 3), dtype=np.uint8)
+    poses = TP.ring_cameras(V)
+    vol = planner.plan_real(net, frames, poses, K)[2]
+    rg = (float(np.percentile(vol, 40)), float(np.percentile(vol, 60)))
+    iso = float(np.float32(np.median(vol)))
+    kw = dict(order='score', top_k=10, surface_rg=rg)
+    legs = {'a_session_ranked_top10_and_cloud': {}, 'b_with_volume_depth_iso0': dict(volume_depth=True),
+            'c_with_volume_depth_at_the_median': dict(volume_depth=dict(iso=iso))}
+    sess = {k: planner.real_session(net, V, hw, TP.IMG_WH, **kw, **m) for k, m in legs.items()}
+
+    def run(k):
+        t0 = time.perf_counter()
+        out = planner.plan_real(net, frames, poses, K, **kw, **legs[k], session=sess[k])
+        return time.perf_counter() - t0, out
+
+    for _ in range(5):
+        last = {k: run(k)[1] for k in legs}
+    times = {k: [] for k in legs}
+    for _ in range(a.calls):                                                 # alternating: the legs see the same machine state
+        for k in legs:
+            times[k].append(run(k)[0])
+    res = {'shape': {'views': V, 'frames_hw': hw, 'volume_resolution': 40, 'weights': 'synthetic', 'depth_images': [V, *hw]}, 'calls': a.calls, 'warmup': 5,
+           'unit': 'ms, host clock around the whole plan_real(session=...) call (ends in a device synchronisation)',
+           'device': torch.cuda.get_device_name(0)}
+    for k, t in times.items():
+        res[k] = {q: TP.pct(t, p) for q, p in (('p10', 10), ('p50', 50), ('p90', 90))}
+    res['hit_share_iso0'] = round(float((last['b_with_volume_depth_iso0'][3]['volume_depth'] > 0).mean()), 4)
+    res['hit_share_at_the_median'] = round(float((last['c_with_volume_depth_at_the_median'][3]['volume_depth'] > 0).mean()), 4)
+    res['same_grasps_and_cloud'] = bool(all(np.array_equal(last[k][0]['index'], last['a_session_ranked_top10_and_cloud'][0]['index']) and
+                                            np.array_equal(last[k][3]['index'], last['a_session_ranked_top10_and_cloud'][3]['index']) for k in legs))
+    res['b_minus_a_p50'] = res['b_with_volume_depth_iso0']['p50'] - res['a_session_ranked_top10_and_cloud']['p50']
+    res['c_minus_a_p50'] = res['c_with_volume_depth_at_the_median']['p50'] - res['a_session_ranked_top10_and_cloud']['p50']
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--calls', type=int, default=100)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'volume_raycast.json'))
+    ap.add_argument('--skip-session', action='store_true')
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('time_raycast.py measures on a ROCm GPU; there is nothing to time without one')
+    if a.calls < 50:
+        sys.exit('--calls must be at least 50')
+    res = kernels(a)
+    if not a.skip_session:
+        res['planner_session'] = session(a)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
