@@ -5,11 +5,82 @@ draw_utils.py is here too: `process` with its three thresholds (GRASP_UTILS_PROC
 (order='score', top_k), and the surface point cloud of `extract_surface_points_from_volume` (SurfaceExtractor, write_ply).  The
 triangle mesh of the volume's iso-surface (MeshExtractor, csrc/gnr_mesh.hip) has no counterpart in the reference."""
 import ctypes as C
+import inspect
 
 import numpy as np
 import torch
 
 from . import _lib
+
+
+class DeviceOp:
+    """What every wrapper of a libgnr.so entry point keeps: the library, its device, the current stream's pointer and a byte workspace
+    that only grows -- a request it already covers never reallocates, so its address is stable for a captured graph once a warm-up call
+    has sized it.  noun: what the wrapper does, for the error of a box without a GPU."""
+
+    def __init__(self, device, noun):
+        self.L = _lib.lib()
+        if not torch.cuda.is_available():
+            raise _lib.GnrError(f'the HIP {noun} needs a ROCm GPU; there is no CPU fallback')
+        self.device = torch.device(device)
+        self._ws = None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _workspace(self, need):
+        """-> (address, bytes) of a workspace of at least `need` bytes."""
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws.data_ptr(), self._ws.numel()
+
+
+def volume_batch(vol, device):
+    """vol [B,R,R,R] (or [B,1,R,R,R], or one [R,R,R]) -> (contiguous float32 device tensor, B, R)."""
+    vol = torch.as_tensor(vol, dtype=torch.float32, device=device).contiguous()
+    R = vol.shape[-1]
+    if vol.dim() < 3 or tuple(vol.shape[-3:]) != (R, R, R) or vol.numel() % R ** 3:
+        raise ValueError(f'vol must be [B,R,R,R], got {tuple(vol.shape)}')
+    return vol, vol.numel() // R ** 3, R
+
+
+def gradient_batch(gradient, B, R, device):
+    """The gradient volume [B,R,R,R,3] of B volumes as a contiguous float32 device tensor; None stays None."""
+    if gradient is None:
+        return None
+    g = torch.as_tensor(gradient, dtype=torch.float32, device=device).contiguous()
+    if tuple(g.shape) != (B, R, R, R, 3):
+        raise ValueError(f'gradient must be [{B},{R},{R},{R},3], got {tuple(g.shape)}')
+    return g
+
+
+def expand_cameras(a, b, B, V):
+    """Two stacks of per-view camera matrices ([..,3,4] poses and [..,3,3] intrinsics, in the caller's order) -> each [B,V,..]: one
+    scene's, or one view's, serve all."""
+    try:
+        return a.expand(B, V, *a.shape[-2:]), b.expand(B, V, *b.shape[-2:])
+    except RuntimeError:
+        raise ValueError(f'cameras {tuple(a.shape)} / {tuple(b.shape)} do not fit {B} scene(s) of {V} view(s)') from None
+
+
+def checked_params(what, given, defaults):
+    """The parameters of one optional output: None / False -> None (not asked for), True -> the defaults, a dict -> the defaults with
+    its entries; a key the defaults do not have is a TypeError that names `what`."""
+    if given is None or given is False:
+        return None
+    given = {} if given is True else dict(given)
+    unknown = sorted(set(given) - set(defaults))
+    if unknown:
+        raise TypeError(f'unknown {what} parameters {unknown}; it takes {sorted(defaults)}')
+    return {**defaults, **given}
+
+
+def _call_defaults(cls, *skip):
+    return {k: p.default for k, p in inspect.signature(cls.__call__).parameters.items() if p.default is not inspect.Parameter.empty and k not in skip}
+
+
+def _host(rows):
+    return {k: v.cpu().numpy() for k, v in rows.items()}
 
 
 def gaussian_weights(sigma, truncate=4.0):
@@ -29,17 +100,13 @@ GRASP_UTILS_PROCESS = dict(gaussian_filter_sigma=1.0, min_width=0, max_width=12,
 _ORDERS = {'index': _lib.GNR_SELECT_ORDER_INDEX, 'score': _lib.GNR_SELECT_ORDER_SCORE}
 
 
-class GraspSelector:
+class GraspSelector(DeviceOp):
     """process() + select() for B scenes at once.  Defaults are the reference functions' defaults; the planner passes
     tsdf_thres_high=0, tsdf_thres_low=-0.85 (main.py:93-94,199)."""
 
     def __init__(self, device='cuda:0', max_grasps=2048):
-        self.L = _lib.lib()
-        if not torch.cuda.is_available():
-            raise _lib.GnrError('the HIP grasp post-processing needs a ROCm GPU; there is no CPU fallback')
-        self.device = torch.device(device)
+        super().__init__(device, 'grasp post-processing')
         self.max_grasps = int(max_grasps)
-        self._ws = None
 
     def __call__(self, tsdf, qual, rot, width, gaussian_filter_sigma=1.0, min_width=1.33, max_width=9.33,
                  tsdf_thres_high=0.5, tsdf_thres_low=1e-3, threshold=0.90, max_filter_size=4, tsdf_thres_outside=None, order='index',
@@ -73,8 +140,6 @@ class GraspSelector:
             p2.tsdf_thres_outside = float(tsdf_thres_high if tsdf_thres_outside is None else tsdf_thres_outside)
             p2.order, p2.top_k = _ORDERS[order], int(top_k or 0)
         need = self.L.gnr_grasp_select_v2_workspace_bytes(B, R, _ORDERS[order]) if v2 else self.L.gnr_grasp_select_workspace_bytes(B, R)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=d)
         M = self.max_grasps
         out = {'qual': torch.empty(B, R, R, R, device=d), 'count': torch.empty(B, dtype=torch.int32, device=d),
                'index': torch.empty(B, M, 3, dtype=torch.int32, device=d), 'score': torch.empty(B, M, device=d),
@@ -82,22 +147,17 @@ class GraspSelector:
         fn, name = (self.L.gnr_grasp_select_v2_fwd, 'gnr_grasp_select_v2_fwd') if v2 else (self.L.gnr_grasp_select_fwd, 'gnr_grasp_select_fwd')
         rc = fn(tsdf.data_ptr(), qual.data_ptr(), rot.data_ptr(), width.data_ptr(), B, R, C.byref(p2 if v2 else p),
                 out['qual'].data_ptr(), out['count'].data_ptr(), out['index'].data_ptr(), out['score'].data_ptr(),
-                out['quat'].data_ptr(), out['width'].data_ptr(), M, self._ws.data_ptr(), self._ws.numel(),
-                C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+                out['quat'].data_ptr(), out['width'].data_ptr(), M, *self._workspace(need), self._stream())
         _lib.check(rc, name)
         out['order'], out['top_k'] = order, None if top_k is None else int(top_k)
         return out
 
 
-class SurfaceExtractor:
+class SurfaceExtractor(DeviceOp):
     """extract_surface_points_from_volume (draw_utils.py:355-377) for B volumes at once, on the device."""
 
     def __init__(self, device='cuda:0'):
-        self.L = _lib.lib()
-        if not torch.cuda.is_available():
-            raise _lib.GnrError('the HIP surface extraction needs a ROCm GPU; there is no CPU fallback')
-        self.device = torch.device(device)
-        self._ws = None
+        super().__init__(device, 'surface extraction')
 
     def __call__(self, vol, rg=(-0.2, 0.2), bound=(-1, 1), color=(0, 0, 1), scale=0.3 / 40, max_points=None, gradient=None):
         """vol [B,R,R,R] (or [B,1,R,R,R], or one [R,R,R])  ->  dict of device tensors: count [B] voxels with rg[0] < vol < rg[1];
@@ -107,52 +167,55 @@ class SurfaceExtractor:
         gradient [B,R,R,R,3] (HotPath.sample_volume_gradient): adds `gradient` [B,max,3] float32, its rows at the cloud's voxels
         gathered on the device (gnr_surface_gradient_fwd); rows beyond count[b] are zero."""
         d = self.device
-        vol = torch.as_tensor(vol, dtype=torch.float32, device=d).contiguous()
-        R = vol.shape[-1]
-        if vol.dim() < 3 or tuple(vol.shape[-3:]) != (R, R, R) or vol.numel() % R ** 3:
-            raise ValueError(f'vol must be [B,R,R,R], got {tuple(vol.shape)}')
-        B = vol.numel() // R ** 3
+        vol, B, R = volume_batch(vol, d)
         M = R ** 3 if max_points is None else int(max_points)
         p = _lib.GnrSurfaceParams()
         p.lo, p.hi, p.scale = float(rg[0]), float(rg[1]), float(scale)
         p.color_mode = _lib.GNR_SURFACE_COLOR_VALUE if color is None else _lib.GNR_SURFACE_COLOR_FIXED
         p.color[:] = [float(c) for c in (color or (0, 0, 0))]
         p.bound_a, p.bound_b = float(bound[0]), float(bound[1])
-        need = self.L.gnr_surface_points_workspace_bytes(B, R)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=d)
         out = {'count': torch.empty(B, dtype=torch.int32, device=d), 'index': torch.empty(B, M, 3, dtype=torch.int32, device=d),
                'points': torch.empty(B, M, 3, dtype=torch.float64, device=d), 'colors': torch.empty(B, M, 3, device=d)}
         rc = self.L.gnr_surface_points_fwd(vol.data_ptr(), B, R, C.byref(p), out['count'].data_ptr(), out['index'].data_ptr(),
-                                           out['points'].data_ptr(), out['colors'].data_ptr(), M, self._ws.data_ptr(),
-                                           self._ws.numel(), C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+                                           out['points'].data_ptr(), out['colors'].data_ptr(), M,
+                                           *self._workspace(self.L.gnr_surface_points_workspace_bytes(B, R)), self._stream())
         _lib.check(rc, 'gnr_surface_points_fwd')
-        if gradient is not None:
-            g = torch.as_tensor(gradient, dtype=torch.float32, device=d).contiguous()
-            if tuple(g.shape) != (B, R, R, R, 3):
-                raise ValueError(f'gradient must be [{B},{R},{R},{R},3], got {tuple(g.shape)}')
+        g = gradient_batch(gradient, B, R, d)
+        if g is not None:
             out['gradient'] = torch.zeros(B, M, 3, dtype=torch.float32, device=d)
             rc = self.L.gnr_surface_gradient_fwd(g.data_ptr(), out['index'].data_ptr(), out['count'].data_ptr(), B, R, M,
-                                                 out['gradient'].data_ptr(), C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+                                                 out['gradient'].data_ptr(), self._stream())
             _lib.check(rc, 'gnr_surface_gradient_fwd')
         out['scale'], out['value_map'] = float(scale), color is None
         return out
 
 
-def surface_from_extraction(res, b=0):
-    """Scene b of a SurfaceExtractor result -> numpy dict: `index` [N,3] int64, `points` [N,3] float64 (metres), `colors` [N,3]
-    float64 (what open3d's Vector3dVector holds).  Raises when the buffers held fewer rows than the scene has voxels in range.
-    A result with `gradient` adds `gradient` [N,3] float32 (the device's rows) and `normals` [N,3] float64 = g / |g| computed here on
-    the host (the convention of `points` = index * scale); a zero row stays zero."""
-    n = int(res['count'][b].item())
+SELECTOR_DEFAULTS = _call_defaults(GraspSelector)
+SURFACE_DEFAULTS = _call_defaults(SurfaceExtractor, 'gradient')      # (the gradient volume is the caller's, not a parameter)
+
+
+def surface_rows(res, b, n):
+    """The device rows of scene b of a SurfaceExtractor result, given its count n.  Raises when the buffers held fewer rows than the
+    scene has voxels in range."""
     if n > res['index'].shape[1]:
         raise _lib.GnrError(f'{n} surface voxels but the buffers hold {res["index"].shape[1]}: raise max_points')
-    out = {'index': res['index'][b, :n].cpu().numpy().astype(np.int64), 'points': res['points'][b, :n].cpu().numpy(),
-           'colors': res['colors'][b, :n].cpu().numpy().astype(np.float64)}
-    if 'gradient' in res:
-        out['gradient'] = res['gradient'][b, :n].cpu().numpy()
+    return {k: res[k][b, :n] for k in ('index', 'points', 'colors', 'gradient') if k in res}
+
+
+def surface_from_rows(rows):
+    """surface_rows on the host (numpy) -> the cloud: `index` [N,3] int64, `points` [N,3] float64 (metres), `colors` [N,3] float64 (what
+    open3d's Vector3dVector holds); with `gradient` [N,3] float32 (the device's rows) also `normals` [N,3] float64 = g / |g| computed
+    here on the host (the convention of `points` = index * scale); a zero row stays zero."""
+    out = {'index': rows['index'].astype(np.int64), 'points': rows['points'], 'colors': rows['colors'].astype(np.float64)}
+    if 'gradient' in rows:
+        out['gradient'] = rows['gradient']
         out['normals'] = unit_normals(out['gradient'])
     return out
+
+
+def surface_from_extraction(res, b=0):
+    """Scene b of a SurfaceExtractor result -> numpy dict (surface_from_rows), every row read back."""
+    return surface_from_rows(_host(surface_rows(res, b, int(res['count'][b].item()))))
 
 
 def unit_normals(gradient):
@@ -168,16 +231,12 @@ def mesh_bounds(R):
     return (R - 1) ** 3, max(1, 6 * (R - 1) * (R - 2) ** 2)
 
 
-class MeshExtractor:
+class MeshExtractor(DeviceOp):
     """The indexed triangle mesh of the iso-surface vol = iso of B volumes at once, on the device (gnr_surface_mesh_fwd: naive surface
     nets; include/gnr.h has the statement).  No reference counterpart."""
 
     def __init__(self, device='cuda:0'):
-        self.L = _lib.lib()
-        if not torch.cuda.is_available():
-            raise _lib.GnrError('the HIP surface mesh needs a ROCm GPU; there is no CPU fallback')
-        self.device = torch.device(device)
-        self._ws = None
+        super().__init__(device, 'surface mesh')
 
     def __call__(self, vol, iso=0.0, scale=0.3 / 40, origin=(0.0, 0.0, 0.0), max_vertices=None, max_faces=None, gradient=None):
         """vol [B,R,R,R] (or [B,1,R,R,R], or one [R,R,R]), 2 <= R <= 256  ->  dict of device tensors: count [B,2] int32 (vertices,
@@ -187,49 +246,51 @@ class MeshExtractor:
         truncated.  gradient [B,R,R,R,3] (HotPath.sample_volume_gradient): adds `gradient` [B,max_vertices,3] float32, the volume's
         rows interpolated to the vertices like the positions (not normalised)."""
         d = self.device
-        vol = torch.as_tensor(vol, dtype=torch.float32, device=d).contiguous()
-        R = vol.shape[-1]
-        if vol.dim() < 3 or tuple(vol.shape[-3:]) != (R, R, R) or vol.numel() % R ** 3:
-            raise ValueError(f'vol must be [B,R,R,R], got {tuple(vol.shape)}')
-        B = vol.numel() // R ** 3
+        vol, B, R = volume_batch(vol, d)
         bv, bf = mesh_bounds(R)
         MV, MF = bv if max_vertices is None else int(max_vertices), bf if max_faces is None else int(max_faces)
         p = _lib.GnrMeshParams()
         p.iso, p.scale = float(iso), float(scale)
         p.origin[:] = [float(c) for c in origin]
-        need = self.L.gnr_surface_mesh_workspace_bytes(B, R)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=d)
         out = {'count': torch.empty(B, 2, dtype=torch.int32, device=d), 'vertices': torch.empty(B, max(MV, 0), 3, dtype=torch.float64, device=d),
                'faces': torch.empty(B, max(MF, 0), 3, dtype=torch.int32, device=d)}
-        g = None
-        if gradient is not None:
-            g = torch.as_tensor(gradient, dtype=torch.float32, device=d).contiguous()
-            if tuple(g.shape) != (B, R, R, R, 3):
-                raise ValueError(f'gradient must be [{B},{R},{R},{R},3], got {tuple(g.shape)}')
+        g = gradient_batch(gradient, B, R, d)
+        if g is not None:
             out['gradient'] = torch.empty(B, max(MV, 0), 3, dtype=torch.float32, device=d)
         rc = self.L.gnr_surface_mesh_fwd(vol.data_ptr(), None if g is None else g.data_ptr(), B, R, C.byref(p), out['count'].data_ptr(),
                                          out['vertices'].data_ptr(), out['faces'].data_ptr(),
-                                         None if g is None else out['gradient'].data_ptr(), MV, MF, self._ws.data_ptr(),
-                                         self._ws.numel(), C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+                                         None if g is None else out['gradient'].data_ptr(), MV, MF,
+                                         *self._workspace(self.L.gnr_surface_mesh_workspace_bytes(B, R)), self._stream())
         _lib.check(rc, 'gnr_surface_mesh_fwd')
         return out
 
 
-def mesh_from_extraction(res, b=0):
-    """Scene b of a MeshExtractor result -> numpy dict: `vertices` [N,3] float64, `faces` [F,3] int64; a result with `gradient` adds
-    `gradient` [N,3] float32 (the device's rows) and `normals` [N,3] float64 = g / |g| (unit_normals, as for the cloud).  Raises when
-    a buffer held fewer rows than the scene has vertices or triangles."""
-    nv, nf = (int(c) for c in res['count'][b].tolist())
+MESH_DEFAULTS = dict(iso=0.0, max_vertices=None, max_faces=None)     # what a plan sets of MeshExtractor.__call__: the frame is the cloud's
+
+
+def mesh_rows(res, b, nv, nf):
+    """The device rows of scene b of a MeshExtractor result, given its vertex and triangle counts.  Raises when a buffer held fewer
+    rows than the scene has vertices or triangles."""
     if nv > res['vertices'].shape[1]:
         raise _lib.GnrError(f'{nv} mesh vertices but the buffers hold {res["vertices"].shape[1]}: raise max_vertices')
     if nf > res['faces'].shape[1]:
         raise _lib.GnrError(f'{nf} mesh triangles but the buffers hold {res["faces"].shape[1]}: raise max_faces')
-    out = {'vertices': res['vertices'][b, :nv].cpu().numpy(), 'faces': res['faces'][b, :nf].cpu().numpy().astype(np.int64)}
-    if 'gradient' in res:
-        out['gradient'] = res['gradient'][b, :nv].cpu().numpy()
+    return {k: res[k][b, :nf if k == 'faces' else nv] for k in ('vertices', 'faces', 'gradient') if k in res}
+
+
+def mesh_from_rows(rows):
+    """mesh_rows on the host (numpy) -> the mesh: `vertices` [N,3] float64, `faces` [F,3] int64; with `gradient` [N,3] float32 (the
+    device's rows) also `normals` [N,3] float64 = g / |g| (unit_normals, as for the cloud)."""
+    out = {'vertices': rows['vertices'], 'faces': rows['faces'].astype(np.int64)}
+    if 'gradient' in rows:
+        out['gradient'] = rows['gradient']
         out['normals'] = unit_normals(out['gradient'])
     return out
+
+
+def mesh_from_extraction(res, b=0):
+    """Scene b of a MeshExtractor result -> numpy dict (mesh_from_rows), every row read back."""
+    return mesh_from_rows(_host(mesh_rows(res, b, *(int(c) for c in res['count'][b].tolist()))))
 
 
 def write_ply(path, points, colors, normals=None, faces=None):

@@ -12,12 +12,12 @@ import numpy as np
 import torch
 
 from .renderer import GraspNeRF
-from .grasp_post import GRASP_UTILS_PROCESS, GraspSelector, MeshExtractor, SurfaceExtractor, grasps_from_selection, mesh_from_extraction, \
-    surface_from_extraction
+from .grasp_post import GRASP_UTILS_PROCESS, MESH_DEFAULTS, GraspSelector, MeshExtractor, SurfaceExtractor, checked_params, \
+    grasps_from_selection, mesh_from_extraction, surface_from_extraction
 from .ingest import axis_tables
-from .planner_session import PlannerSession
-from .raycast import RAYCAST_DEFAULTS, VolumeRaycaster, images_from_raycast
-from .tsdf import create_tsdf
+from .planner_session import PLAN_BBOX3D, PlannerSession, deterministic_convolutions
+from .raycast import VolumeRaycaster, depth_params as _depth_params, images_from_raycast, same_depth_params as _same_depth_params, volume_origin
+from .tsdf import create_tsdf, rotation_matrix
 
 
 def load_model(cfg, checkpoint=None, device='cuda:0', depth_coords_rng='device'):
@@ -37,20 +37,28 @@ def full_frame_coords(h, w):
     return np.stack([xs, ys], -1).reshape(1, -1, 2).astype(np.float32)
 
 
+def _scene(dev, images, extrinsics, intrinsics, depth_range, bbox3d, que_id=None, coords=None):
+    """One scene from arrays, on the device: `ref_imgs_info` alone (que_id None), or the forward's `data` with the query view que_id at
+    the pixel coordinates `coords` [1,N,2]."""
+    V = len(images)
+    t = lambda a: torch.as_tensor(np.array(a, np.float32), device=dev)
+    ext, K = np.asarray(extrinsics, np.float32)[:, :3, :], np.asarray(intrinsics, np.float32)
+    dr = np.broadcast_to(np.asarray(depth_range, np.float32), (V, 2)) if np.ndim(depth_range) == 1 else np.asarray(depth_range, np.float32)
+    ref = {'imgs': t(images), 'poses': t(ext), 'Ks': t(K), 'depth_range': t(dr), 'bbox3d': t(bbox3d)}
+    if que_id is None:
+        return ref
+    que = {'poses': t(ext[que_id])[None], 'Ks': t(K[que_id])[None], 'coords': coords, 'depth_range': t(dr[que_id])[None]}
+    return {'step': 0, 'eval': True, 'full_vol': True, 'ref_imgs_info': ref, 'que_imgs_info': que, 'src_imgs_info': dict(ref)}
+
+
 def core(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8),
          bbox3d=((-0.15, -0.15, -0.05), (0.15, 0.15, 0.25)), que_id=0):
     """images [V,3,H,W] in [0,1]; extrinsics [V,3|4,4] world->camera; intrinsics [V,3,3]; H, W multiples of 32.
     -> volume [1,1,R,R,R], qual [1,1,40^3], rot [1,4,40^3], width [1,1,40^3] (numpy) and the forward seconds."""
-    V, _, h, w = images.shape
+    h, w = images.shape[2:]
     assert h % 32 == 0 and w % 32 == 0                                          # main.py:226
     dev = next(net.parameters()).device
-    t = lambda a: torch.as_tensor(np.array(a, np.float32), device=dev)
-    ext = np.asarray(extrinsics, np.float32)[:, :3, :]
-    dr = np.broadcast_to(np.asarray(depth_range, np.float32), (V, 2)) if np.ndim(depth_range) == 1 else np.asarray(depth_range, np.float32)
-    ref = {'imgs': t(images), 'poses': t(ext), 'Ks': t(intrinsics), 'depth_range': t(dr), 'bbox3d': t(bbox3d)}
-    que = {'poses': t(ext[que_id])[None], 'Ks': t(np.asarray(intrinsics, np.float32)[que_id])[None],
-           'coords': t(full_frame_coords(h, w)), 'depth_range': t(dr[que_id])[None]}
-    data = {'step': 0, 'eval': True, 'full_vol': True, 'ref_imgs_info': ref, 'que_imgs_info': que, 'src_imgs_info': dict(ref)}
+    data = _scene(dev, images, extrinsics, intrinsics, depth_range, bbox3d, que_id, torch.as_tensor(full_frame_coords(h, w), device=dev))
     with torch.no_grad():
         torch.cuda.synchronize(dev)
         t0 = time.time()
@@ -61,7 +69,7 @@ def core(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8),
     return out['volume'].cpu().numpy(), q.cpu().numpy(), r.cpu().numpy(), wd.cpu().numpy(), dt
 
 
-def plan(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497)),
+def plan(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=PLAN_BBOX3D,
          seed=None, selector=None, tsdf_thres_high=0.0, tsdf_thres_low=-0.85, voxel_size=0.3 / 40, return_volumes=False,
          session=None, tsdf_thres_outside=None, order='index', top_k=None, que_id=0):
     """`GraspNeRFPlanner.__call__` from arrays (main.py:185-209): forward, process + select on the device, seeded
@@ -79,14 +87,7 @@ def plan(net, images, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-
                              '(its GraspSelector is its own: pass no selector)')
         return session.plan(images, extrinsics, intrinsics, depth_range, bbox3d, seed=seed, return_volumes=return_volumes)
     dev = next(net.parameters()).device
-    V, _, h, w = images.shape
-    t = lambda a: torch.as_tensor(np.array(a, np.float32), device=dev)
-    ext = np.asarray(extrinsics, np.float32)[:, :3, :]
-    dr = np.broadcast_to(np.asarray(depth_range, np.float32), (V, 2)) if np.ndim(depth_range) == 1 else np.asarray(depth_range, np.float32)
-    ref = {'imgs': t(images), 'poses': t(ext), 'Ks': t(intrinsics), 'depth_range': t(dr), 'bbox3d': t(bbox3d)}
-    que = {'poses': t(ext[que_id])[None], 'Ks': t(np.asarray(intrinsics, np.float32)[que_id])[None],
-           'coords': torch.zeros(1, 1, 2, device=dev), 'depth_range': t(dr[que_id])[None]}
-    data = {'step': 0, 'eval': True, 'full_vol': True, 'ref_imgs_info': ref, 'que_imgs_info': que, 'src_imgs_info': dict(ref)}
+    data = _scene(dev, images, extrinsics, intrinsics, depth_range, bbox3d, que_id, torch.zeros(1, 1, 2, device=dev))
     selector = selector or GraspSelector(dev)
     with torch.no_grad():
         torch.cuda.synchronize(dev)
@@ -111,51 +112,14 @@ REAL_DEPTH_RANGE, REAL_QUE_ID, REAL_VOXEL_SIZE = (0.2, 0.8), 3, 0.3 / 40        
 
 
 def _mesh_params(mesh):
-    """plan_real's `mesh` argument -> None, or the surface_mesh parameters of a PlannerSession (True: iso = 0, the exact upper bounds)."""
-    if mesh is None or mesh is False:
-        return None
-    mesh = {} if mesh is True else dict(mesh)
-    unknown = sorted(set(mesh) - {'iso', 'max_vertices', 'max_faces'})
-    if unknown:
-        raise TypeError(f'unknown mesh parameters {unknown}; mesh is True or dict(iso=..., max_vertices=..., max_faces=...)')
-    return {'iso': 0.0, 'max_vertices': None, 'max_faces': None, **mesh}
-
-
-def _depth_params(volume_depth):
-    """plan_real's `volume_depth` argument -> None, or the ray cast's parameters (True: the plan's own cameras and image size, iso = 0,
-    half-voxel steps, four bisections);  extrinsics -> float32 [V',3,4], intrinsic -> float32 [3,3], hw -> (h, w)."""
-    if volume_depth is None or volume_depth is False:
-        return None
-    vd = {} if volume_depth is True else dict(volume_depth)
-    known = {'extrinsics', 'intrinsic', 'hw', *RAYCAST_DEFAULTS}
-    unknown = sorted(set(vd) - known)
-    if unknown:
-        raise TypeError(f'unknown volume_depth parameters {unknown}; volume_depth is True or dict(extrinsics=..., intrinsic=..., hw=..., '
-                        f'iso=..., step=..., bisections=...)')
-    out = {'extrinsics': None, 'intrinsic': None, 'hw': None, **RAYCAST_DEFAULTS, **vd}
-    if out['extrinsics'] is not None:
-        ext = np.stack([np.asarray(e, np.float32) for e in out['extrinsics']], 0)
-        if ext.ndim != 3 or ext.shape[1:] not in ((3, 4), (4, 4)):
-            raise ValueError(f'volume_depth extrinsics must be V world->camera [3|4,4], got {ext.shape}')
-        out['extrinsics'] = np.ascontiguousarray(ext[:, :3, :])
-    if out['intrinsic'] is not None:
-        out['intrinsic'] = np.ascontiguousarray(np.asarray(out['intrinsic'], np.float32).reshape(3, 3))
-    if out['hw'] is not None:
-        out['hw'] = (int(out['hw'][0]), int(out['hw'][1]))
-    out['iso'], out['step'], out['bisections'] = float(out['iso']), float(out['step']), int(out['bisections'])
-    return out
-
-
-def _same_depth_params(a, b):
-    if a is None or b is None:
-        return a is None and b is None
-    same = lambda x, y: (x is None and y is None) if (x is None or y is None) else np.array_equal(x, y)
-    return all(same(a[k], b.get(k)) for k in a)
+    """plan_real's `mesh` argument -> None, or the surface_mesh parameters of a PlannerSession (True: iso = 0, the exact upper bounds).
+    (Its `volume_depth` argument: raycast.depth_params, here as _depth_params.)"""
+    return checked_params('mesh', mesh, MESH_DEFAULTS)
 
 
 def real_volume_origin():
     """World position of voxel (0,0,0)'s centre of run_real's volume: the lattice origin of its ray cast."""
-    return np.asarray(REAL_BBOX3D[0], np.float64) + 0.5 * REAL_VOXEL_SIZE
+    return volume_origin(REAL_BBOX3D[0], REAL_VOXEL_SIZE)
 
 
 def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, mesh=False,
@@ -163,12 +127,13 @@ def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, sur
     """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud
     (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True);  mesh: plan_real's, with the
     triangle mesh of the volume's iso-surface in the graph;  volume_depth: plan_real's, with the ray cast of the volume in the graph)."""
-    if _depth_params(volume_depth) is not None:
-        kw = dict(kw, volume_depth=dict(_depth_params(volume_depth), origin=tuple(real_volume_origin())))
+    vd, mp = _depth_params(volume_depth), _mesh_params(mesh)
+    if vd is not None:
+        kw = dict(kw, volume_depth=dict(vd, origin=tuple(real_volume_origin())))
     if normals:
         kw = dict(kw, surface_normals=True)
-    if _mesh_params(mesh) is not None:
-        kw = dict(kw, surface_mesh=_mesh_params(mesh))
+    if mp is not None:
+        kw = dict(kw, surface_mesh=mp)
     return PlannerSession(net, n_views, src_hw, img_wh, max_grasps=max_grasps, voxel_size=REAL_VOXEL_SIZE,
                           surface=dict(rg=tuple(surface_rg)), order='score' if order == 'score' else 'index', top_k=top_k,
                           **GRASP_UTILS_PROCESS, **kw)
@@ -200,7 +165,7 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     real_session(volume_depth=...).  Grasps, cloud and mesh do not depend on it."""
     if order not in ('permuted', 'score'):
         raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
-    vd = _depth_params(volume_depth)
+    vd, mp = _depth_params(volume_depth), _mesh_params(mesh)
     ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
     V = ext.shape[0]
     if V <= REAL_QUE_ID:
@@ -214,9 +179,8 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         sp, su = session.selector_params, session.surface_params
         want = dict(GRASP_UTILS_PROCESS, order=sel_order, top_k=top_k)
         if session.net is not net or su is None or tuple(su['rg']) != tuple(surface_rg) or any(sp[k] != v for k, v in want.items()) \
-                or session.voxel_size != REAL_VOXEL_SIZE or bool(normals) != bool(getattr(session, 'surface_normals', False)) \
-                or _mesh_params(mesh) != getattr(session, 'mesh_params', None) \
-                or not _same_depth_params(vd, getattr(session, 'volume_depth_params', None)):
+                or session.voxel_size != REAL_VOXEL_SIZE or bool(normals) != session.surface_normals \
+                or mp != session.mesh_params or not _same_depth_params(vd, session.volume_depth_params):
             raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range, normals, mesh or '
                              'volume_depth (build it with planner.real_session)')
         g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
@@ -233,31 +197,25 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         imgs = (frames.astype(np.float32) / 255).transpose([0, 3, 1, 2])                                  # color_map_forward, grasp_utils.py:134
         selector = GraspSelector(dev)
         call = lambda vol, q, r, w, **kw: selector(vol, q, r, w, **{**kw, **GRASP_UTILS_PROCESS})
-        was = torch.backends.cudnn.deterministic                  # the solvers a PlannerSession records: the same frames, the same bits
-        torch.backends.cudnn.deterministic = True
-        try:
+        with deterministic_convolutions():                        # the solvers a PlannerSession records: the same frames, the same bits
             g, dt = plan(net, imgs, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, selector=call, voxel_size=REAL_VOXEL_SIZE,
                          tsdf_thres_high=GRASP_UTILS_PROCESS['tsdf_thres_high'], tsdf_thres_low=GRASP_UTILS_PROCESS['tsdf_thres_low'],
                          order=sel_order, top_k=top_k, return_volumes=True, que_id=REAL_QUE_ID)
-        finally:
-            torch.backends.cudnn.deterministic = was
         tsdf_vol = g.pop('volumes')[0]
         grad = None
         if normals:                                               # the volume's cameras again: the forward keeps no feature maps
             grad = _volume_gradient(net, imgs, ext, Ks, dev)
-        res = SurfaceExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), rg=surface_rg,                # grasp_utils.py:149
-                                    **({'gradient': grad} if normals else {}))
+        res = SurfaceExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), rg=surface_rg, gradient=grad)     # grasp_utils.py:149
         cloud = surface_from_extraction(res, 0)
-        if _mesh_params(mesh) is not None:
-            res = MeshExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), **_mesh_params(mesh), scale=REAL_VOXEL_SIZE,
-                                     **({'gradient': grad} if normals else {}))
+        if mp is not None:
+            res = MeshExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), **mp, scale=REAL_VOXEL_SIZE, gradient=grad)
             cloud['mesh'] = mesh_from_extraction(res, 0)
         if vd is not None:
             K = Ks[0] if vd['intrinsic'] is None else vd['intrinsic']
             poses = ext[:, :3, :] if vd['extrinsics'] is None else vd['extrinsics']
             res = VolumeRaycaster(dev)(torch.as_tensor(tsdf_vol, device=dev), poses, np.repeat(K[None], len(poses), 0),
                                        frames.shape[1:3] if vd['hw'] is None else vd['hw'], origin=real_volume_origin(), scale=REAL_VOXEL_SIZE,
-                                       iso=vd['iso'], step=vd['step'], bisections=vd['bisections'], **({'gradient': grad} if normals else {}))
+                                       iso=vd['iso'], step=vd['step'], bisections=vd['bisections'], gradient=grad)
             cloud.update(images_from_raycast(res, 0))
     tsdf_vol = np.asarray(tsdf_vol).reshape(tsdf_vol.shape[-3:])
     n = len(g['score'])
@@ -273,19 +231,11 @@ def _volume_gradient(net, imgs, ext, Ks, dev):
     """The SDF gradient volume [1,R,R,R,3] of run_real's scene from the resized float images (the backbones run again: the eager
     forward of plan() hands back its outputs, not its feature maps; a session computes both in one graph)."""
     nr = net.nr_net
-    t = lambda a: torch.as_tensor(np.array(a, np.float32), device=dev)
-    V = imgs.shape[0]
-    ref = {'imgs': t(imgs), 'poses': t(ext[:, :3, :]), 'Ks': t(Ks), 'depth_range': t(np.broadcast_to(np.float32(REAL_DEPTH_RANGE), (V, 2))),
-           'bbox3d': t(REAL_BBOX3D)}
-    was = torch.backends.cudnn.deterministic
-    torch.backends.cudnn.deterministic = True
-    try:
-        with torch.no_grad():
-            ref['img_feats'] = nr.image_encoder(ref['imgs'])
-            ref['ray_feats'] = nr.vis_encoder(nr.init_net(ref, dict(ref), False), ref['img_feats'])
-            return nr.sample_volume_gradient(ref)
-    finally:
-        torch.backends.cudnn.deterministic = was
+    ref = _scene(dev, imgs, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D)
+    with deterministic_convolutions(), torch.no_grad():
+        ref['img_feats'] = nr.image_encoder(ref['imgs'])
+        ref['ray_feats'] = nr.vis_encoder(nr.init_net(ref, dict(ref), False), ref['img_feats'])
+        return nr.sample_volume_gradient(ref)
 
 
 # ---- the depth route (ref: src/gd/detection.py:13-40, the VGN baseline) ------------------------------------------------------
@@ -354,10 +304,7 @@ class _Rotation:
         return self._q.copy()
 
     def as_matrix(self):
-        x, y, z, w = self._q
-        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                         [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                         [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+        return rotation_matrix(self._q)
 
 
 class _Pose:

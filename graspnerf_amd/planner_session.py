@@ -6,25 +6,138 @@ render pass, no valid-ratio read-back.  A plan is two pinned host->device copies
 
 Limits: one scene per plan, a fixed view count, frame size and selector parameters per session (forward_scenes is the batched
 route); the model's parameters may change between plans (the graph is captured again when they did)."""
-import inspect
+import contextlib
 import time
 
 import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import GraspSelector, MeshExtractor, SurfaceExtractor, grasps_from_selection, mesh_bounds, unit_normals
+from .grasp_post import MESH_DEFAULTS, SELECTOR_DEFAULTS, SURFACE_DEFAULTS, GraspSelector, MeshExtractor, SurfaceExtractor, checked_params, \
+    grasps_from_selection, mesh_bounds, mesh_from_rows, mesh_rows, surface_from_rows, surface_rows
 from .ingest import DeviceIngest
-from .raycast import RAYCAST_DEFAULTS, VolumeRaycaster
+from .raycast import VolumeRaycaster, depth_params, images_from_rows, raycast_rows, volume_origin
 
-_SELECTOR_DEFAULTS = {k: p.default for k, p in inspect.signature(GraspSelector.__call__).parameters.items()
-                      if p.default is not inspect.Parameter.empty}
-_SURFACE_DEFAULTS = {k: p.default for k, p in inspect.signature(SurfaceExtractor.__call__).parameters.items()
-                     if p.default is not inspect.Parameter.empty and k != 'gradient'}      # (the gradient volume is the session's: surface_normals)
-_MESH_DEFAULTS = dict(iso=0.0, max_vertices=None, max_faces=None)
-_DEPTH_DEFAULTS = dict(extrinsics=None, intrinsic=None, hw=None, origin=(-0.15 + 0.5 * 0.3 / 40, -0.15 + 0.5 * 0.3 / 40, -0.0503 + 0.5 * 0.3 / 40),
-                       **RAYCAST_DEFAULTS)
 _SEG = 64                                                    # floats: every camera block starts on a 256-byte boundary
+PLAN_BBOX3D = ((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497))       # the planner's workspace box (main.py:91): plan()'s default
+
+
+@contextlib.contextmanager
+def deterministic_convolutions(on=True):
+    """MIOpen's deterministic solvers for the convolutions that pick their solver inside the block (its default solvers for some of the
+    strided layers sum in arrival order); on=False leaves the switch as it is."""
+    was = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = was or on
+    try:
+        yield
+    finally:
+        torch.backends.cudnn.deterministic = was
+
+
+# ---- the optional products of the volume ---------------------------------------------------------------------------------------------
+# A product is one further output of the session's graph.  It owns (1) its normalised parameters, (2) its extractor, its pinned read-back
+# buffers and the number of count words it appends to the packed selection, (3) record(): its step of the captured forward, and (4)
+# fetch() / result(): the sized copies of one plan's rows and, after the session's one wait, the numpy dict -- through the same
+# *_rows / *_from_rows pair as the eager route (grasp_post.py, raycast.py).  PlannerSession builds the list `products` from its keywords
+# and names no product anywhere else; a new one is a class here, a keyword and one line in that list.
+class _Pinned:
+    """Pinned host twins of the rows a product reads back: name=(shape, dtype)."""
+
+    def __init__(self, **rows):
+        self.buf = {k: torch.zeros(*shape, dtype=dtype, pin_memory=True) for k, (shape, dtype) in rows.items()}
+
+    def fetch(self, rows):
+        """Device rows -> the heads of their twins, not waited for."""
+        self.rows = {k: self.buf[k][:len(v)] for k, v in rows.items()}
+        for k, v in rows.items():
+            self.rows[k].copy_(v, non_blocking=True)
+
+    def host(self, *kept):
+        """The fetched rows as numpy.  kept: the rows the builder hands on as they are -- copied, the next plan rewrites the buffers."""
+        return {k: v.numpy().copy() if k in kept else v.numpy() for k, v in self.rows.items()}
+
+
+def _gradient_rows(normals, *shape):
+    return {'gradient': (shape, torch.float32)} if normals else {}
+
+
+class _Cloud:
+    """The surface cloud: one count word; the index rows (the colours in value-map mode, the gradient rows with normals) are read back,
+    the float64 points stay on the device and are recomputed on the host as index * scale, a fixed colour is known on the host."""
+    out, attr, words = 'surface', 'cloud', 1
+
+    def __init__(self, params, R, normals, dev):
+        self.params, self.extract = params, SurfaceExtractor(dev)
+        n = R ** 3 if params['max_points'] is None else int(params['max_points'])
+        self.pinned = _Pinned(index=((n, 3), torch.int32), colors=((n, 3), torch.float32), **_gradient_rows(normals, n, 3))
+
+    def record(self, vol, grad, cams):
+        return self.extract(vol, **self.params, gradient=grad)
+
+    def fetch(self, res, counts):
+        rows = surface_rows(res, 0, *counts)
+        del rows['points']
+        if self.params['color'] is not None:
+            del rows['colors']
+        self.pinned.fetch(rows)
+
+    def result(self):
+        rows = self.pinned.host('gradient')
+        n = len(rows['index'])
+        rows['points'] = rows['index'].astype(np.float64) * float(self.params['scale'])
+        if 'colors' not in rows:
+            rows['colors'] = np.array([self.params['color']], np.float64).repeat(n, axis=0)
+        return {'count': n, **surface_from_rows(rows)}
+
+
+class _Mesh:
+    """The triangle mesh of the iso-surface, in the cloud's frame (origin 0, the cloud's scale): two count words, vertices and
+    triangles; the stored vertex, face (and gradient) rows are read back."""
+    out, attr, words = 'mesh', 'mesh', 2
+
+    def __init__(self, params, R, normals, dev, scale):
+        self.params, self.scale, self.extract = params, scale, MeshExtractor(dev)
+        nv, nf = (b if m is None else int(m) for b, m in zip(mesh_bounds(R), (params['max_vertices'], params['max_faces'])))
+        self.pinned = _Pinned(vertices=((nv, 3), torch.float64), faces=((nf, 3), torch.int32), **_gradient_rows(normals, nv, 3))
+
+    def record(self, vol, grad, cams):
+        return self.extract(vol, **self.params, scale=self.scale, gradient=grad)
+
+    def fetch(self, res, counts):
+        self.pinned.fetch(mesh_rows(res, 0, *counts))
+
+    def result(self):
+        return mesh_from_rows(self.pinned.host('vertices', 'gradient'))
+
+
+class _DepthImages:
+    """The ray cast of the volume: no count word, the whole images are read back.  Without cameras of its own it reads the plan's from
+    the session's device block, which every plan uploads anyway; other cameras are the session's, uploaded once."""
+    out, attr, words = 'volume_depth', 'volume_images', 0
+
+    def __init__(self, params, n_views, hw, voxel_size, normals, dev):
+        self.params, self.scale, self.cast = params, voxel_size, VolumeRaycaster(dev)
+        self.hw = hw if params['hw'] is None else params['hw']
+        nv = n_views if params['extrinsics'] is None else len(params['extrinsics'])
+        up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+        self.poses = up(params['extrinsics'])
+        self.Ks = up(None if params['intrinsic'] is None else np.repeat(params['intrinsic'][None], nv, 0))
+        self.pinned = _Pinned(depth=((nv, *self.hw), torch.float32), **_gradient_rows(normals, nv, *self.hw, 3))
+
+    def record(self, vol, grad, cams):
+        p = self.params
+        poses = cams['poses'] if self.poses is None else self.poses
+        Ks = cams['Ks'] if self.Ks is None else self.Ks
+        if Ks.shape[0] != poses.shape[0]:                    # the plan's own intrinsics (one per view, all equal on this route) for other cameras
+            Ks = Ks[:1].expand(poses.shape[0], 3, 3)
+        return self.cast(vol, poses, Ks, self.hw, origin=p['origin'], scale=self.scale, iso=p['iso'], step=p['step'],
+                         bisections=p['bisections'], gradient=grad)
+
+    def fetch(self, res, counts):
+        self.pinned.fetch(raycast_rows(res, 0))
+
+    def result(self):
+        return images_from_rows(self.pinned.host('depth'))
 
 
 class PlannerSession:
@@ -68,21 +181,10 @@ class PlannerSession:
             raise ValueError("graph capture cannot read the valid ratio back on every call: unset cfg['warn_low_valid_ratio']")
         if not cfg.get('sample_volume', False):
             raise ValueError("the planner needs cfg['sample_volume'] = True")
-        unknown = sorted(set(selector_params) - set(_SELECTOR_DEFAULTS))
-        if unknown:
-            raise TypeError(f'unknown selector parameters {unknown}; GraspSelector takes {sorted(_SELECTOR_DEFAULTS)}')
-        if surface is not None:
-            unknown = sorted(set(surface) - set(_SURFACE_DEFAULTS))
-            if unknown:
-                raise TypeError(f'unknown surface parameters {unknown}; SurfaceExtractor takes {sorted(_SURFACE_DEFAULTS)}')
-        if surface_mesh is not None:
-            unknown = sorted(set(surface_mesh) - set(_MESH_DEFAULTS))
-            if unknown:
-                raise TypeError(f'unknown surface_mesh parameters {unknown}; it takes {sorted(_MESH_DEFAULTS)}')
-        if volume_depth is not None:
-            unknown = sorted(set(volume_depth) - set(_DEPTH_DEFAULTS))
-            if unknown:
-                raise TypeError(f'unknown volume_depth parameters {unknown}; it takes {sorted(_DEPTH_DEFAULTS)}')
+        self.selector_params = checked_params('selector', selector_params, SELECTOR_DEFAULTS)
+        self.surface_params, self.surface_normals = checked_params('surface', surface, SURFACE_DEFAULTS), bool(surface_normals)
+        self.mesh_params = checked_params('mesh', surface_mesh, MESH_DEFAULTS)
+        self.volume_depth_params = depth_params(volume_depth, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise _lib.GnrError('PlannerSession needs the model on a ROCm GPU; there is no CPU fallback')
@@ -93,7 +195,6 @@ class PlannerSession:
         self.n_views, self.src_hw, self.img_wh, self.channels = int(n_views), (int(src_hw[0]), int(src_hw[1])), (W, H), int(channels)
         self.max_grasps, self.voxel_size, self.warmup = int(max_grasps), float(voxel_size), int(warmup)
         self.deterministic = bool(deterministic)
-        self.selector_params = {**_SELECTOR_DEFAULTS, **selector_params}
         self.ingest = DeviceIngest(dev)
         self.selector = GraspSelector(dev, max_grasps=self.max_grasps)
         V, M = self.n_views, self.max_grasps
@@ -114,46 +215,20 @@ class PlannerSession:
         self.images = torch.zeros(V, 3, H, W, dtype=torch.float32, device=dev)       # the ingested frames of the last plan
         # the selection, packed for one read-back: count | index [M,3] | score [M] | quat [M,4] | width [M], 4-byte words
         # (+ the cloud's row count, when the session extracts one; + the mesh's vertex and triangle counts, likewise)
-        self.surface_params = None if surface is None else {**_SURFACE_DEFAULTS, **surface}
-        self.surface_normals = bool(surface_normals)
-        self.mesh_params = None if surface_mesh is None else {**_MESH_DEFAULTS, **surface_mesh}
-        words = 1 + 9 * M + (0 if surface is None else 1) + (0 if surface_mesh is None else 2)
+        R, normals = int(cfg['volume_resolution']), self.surface_normals
+        self.products = []                                   # in the order of their count words and of their copies
+        if self.surface_params is not None:
+            self.products.append(_Cloud(self.surface_params, R, normals, dev))
+        if self.mesh_params is not None:
+            self.products.append(_Mesh(self.mesh_params, R, normals, dev, (self.surface_params or SURFACE_DEFAULTS)['scale']))
+        if self.volume_depth_params is not None:
+            self.products.append(_DepthImages(self.volume_depth_params, V, (H, W), self.voxel_size, normals, dev))
+        words = 1 + 9 * M
+        for p in self.products:
+            p.at, words = words, words + p.words
         self._d_out = torch.zeros(words, dtype=torch.int32, device=dev)
         self._h_out = torch.zeros(words, dtype=torch.int32, pin_memory=True)
-        self.selection = self.cloud = self.mesh = None
-        if surface is not None:
-            R = int(cfg['volume_resolution'])
-            self.surface = SurfaceExtractor(dev)
-            self._surface_rows = R ** 3 if self.surface_params['max_points'] is None else int(self.surface_params['max_points'])
-            self._h_surf_index = torch.zeros(self._surface_rows, 3, dtype=torch.int32, pin_memory=True)
-            self._h_surf_colors = torch.zeros(self._surface_rows, 3, dtype=torch.float32, pin_memory=True)
-            if self.surface_normals:
-                self._h_surf_grad = torch.zeros(self._surface_rows, 3, dtype=torch.float32, pin_memory=True)
-        if surface_mesh is not None:
-            bv, bf = mesh_bounds(int(cfg['volume_resolution']))
-            mp = self.mesh_params
-            self.mesher = MeshExtractor(dev)
-            self._mesh_rows = (bv if mp['max_vertices'] is None else int(mp['max_vertices']), bf if mp['max_faces'] is None else int(mp['max_faces']))
-            self._h_mesh_vertices = torch.zeros(self._mesh_rows[0], 3, dtype=torch.float64, pin_memory=True)
-            self._h_mesh_faces = torch.zeros(self._mesh_rows[1], 3, dtype=torch.int32, pin_memory=True)
-            if self.surface_normals:
-                self._h_mesh_grad = torch.zeros(self._mesh_rows[0], 3, dtype=torch.float32, pin_memory=True)
-        self.volume_depth_params = None if volume_depth is None else {**_DEPTH_DEFAULTS, **volume_depth}
-        self.volume_images = None
-        if volume_depth is not None:
-            vd = self.volume_depth_params
-            self.raycaster = VolumeRaycaster(dev)
-            dh, dw = (H, W) if vd['hw'] is None else (int(vd['hw'][0]), int(vd['hw'][1]))
-            nv = V if vd['extrinsics'] is None else len(vd['extrinsics'])
-            self._depth_hw = (dh, dw)
-            # other cameras than the plan's own are the session's: uploaded once
-            self._depth_poses = None if vd['extrinsics'] is None else \
-                torch.from_numpy(np.ascontiguousarray(np.asarray(vd['extrinsics'], np.float32)[:, :3, :])).to(dev)
-            self._depth_Ks = None if vd['intrinsic'] is None else \
-                torch.from_numpy(np.repeat(np.asarray(vd['intrinsic'], np.float32).reshape(1, 3, 3), nv, 0)).to(dev)
-            self._h_depth = torch.zeros(nv, dh, dw, dtype=torch.float32, pin_memory=True)
-            if self.surface_normals:
-                self._h_depth_grad = torch.zeros(nv, dh, dw, 3, dtype=torch.float32, pin_memory=True)
+        self.selection = self.cloud = self.mesh = self.volume_images = None
         self.captures = 0
         self._set_example_cameras()
         self._capture()
@@ -166,7 +241,7 @@ class PlannerSession:
         self._h['poses'][:] = ring_cameras(self.n_views).astype(np.float32)[:, :3, :]
         self._h['Ks'][:] = np.float32([[0.7 * W, 0, 0.5 * W], [0, 0.7 * W, 0.5 * H], [0, 0, 1]])
         self._h['depth_range'][:] = np.float32([0.2, 0.8])
-        self._h['bbox3d'][:] = np.float32([[-0.15, -0.15, -0.0503], [0.15, 0.15, 0.2497]])
+        self._h['bbox3d'][:] = np.float32(PLAN_BBOX3D)
         self._d_cam.copy_(self._h_cam)
 
     def _forward(self):
@@ -186,23 +261,10 @@ class PlannerSession:
             o[a:b].copy_(sel[k].reshape(-1).view(torch.int32))
         out = {'volume': vol, 'qual': q, 'rot': r, 'width': w, 'sel_qual': sel['qual']}
         grad = nr.sample_volume_gradient(ref, _prep=prep) if self.surface_normals else None
-        if self.surface_params is not None:
-            out['surface'] = self.surface(vol, **self.surface_params, **({'gradient': grad} if self.surface_normals else {}))
-            o[1 + 9 * M:2 + 9 * M].copy_(out['surface']['count'])
-        if self.mesh_params is not None:
-            at = 1 + 9 * M + (0 if self.surface_params is None else 1)
-            out['mesh'] = self.mesher(vol, **self.mesh_params, scale=(self.surface_params or _SURFACE_DEFAULTS)['scale'],
-                                      **({'gradient': grad} if self.surface_normals else {}))
-            o[at:at + 2].copy_(out['mesh']['count'].reshape(-1))
-        if self.volume_depth_params is not None:
-            vd = self.volume_depth_params
-            poses = self._d['poses'] if self._depth_poses is None else self._depth_poses
-            Ks = self._d['Ks'] if self._depth_Ks is None else self._depth_Ks
-            if Ks.shape[0] != poses.shape[0]:                # the plan's own intrinsics (one per view, all equal on this route) for other cameras
-                Ks = Ks[:1].expand(poses.shape[0], 3, 3)
-            out['volume_depth'] = self.raycaster(vol, poses, Ks, self._depth_hw, origin=vd['origin'], scale=self.voxel_size, iso=vd['iso'],
-                                                 step=vd['step'], bisections=vd['bisections'],
-                                                 **({'gradient': grad} if self.surface_normals else {}))
+        for p in self.products:
+            out[p.out] = p.record(vol, grad, self._d)
+            if p.words:
+                o[p.at:p.at + p.words].copy_(out[p.out]['count'].reshape(-1))
         return out
 
     def _state(self):
@@ -218,9 +280,7 @@ class PlannerSession:
     def _capture(self):
         self._params = list(self.net.parameters())
         self.graph = self._out = None                        # the previous capture's pool goes back first
-        was = torch.backends.cudnn.deterministic             # read when a convolution picks its solver: warm-up and capture
-        torch.backends.cudnn.deterministic = was or self.deterministic
-        try:
+        with deterministic_convolutions(self.deterministic):  # read when a convolution picks its solver: warm-up and capture
             s = torch.cuda.Stream(self.device)
             s.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(s), torch.no_grad():
@@ -230,8 +290,6 @@ class PlannerSession:
             g = torch.cuda.CUDAGraph()
             with torch.no_grad(), torch.cuda.graph(g):
                 out = self._forward()
-        finally:
-            torch.backends.cudnn.deterministic = was
         self.graph, self._out, self._captured = g, out, self._state()
         self.captures += 1
 
@@ -263,54 +321,13 @@ class PlannerSession:
         """The stored rows of the cloud and of the mesh, sized by the counts that came with the selection: one copy of the cloud's index
         (and of its colours in value-map mode, of its gradient rows with normals), one each of the mesh's vertex, face (and gradient)
         rows, the volume's depth images when the session casts them, then one wait."""
-        at = 1 + 9 * self.max_grasps
-        count = nv = nf = None
-        if self.surface_params is not None:
-            count, at = int(h[at]), at + 1
-            if count > self._surface_rows:
-                raise _lib.GnrError(f'{count} surface voxels but the buffers hold {self._surface_rows}: raise surface max_points')
-            sp, surf = self.surface_params, self._out['surface']
-            self._h_surf_index[:count].copy_(surf['index'][0, :count], non_blocking=True)
-            if sp['color'] is None:
-                self._h_surf_colors[:count].copy_(surf['colors'][0, :count], non_blocking=True)
-            if self.surface_normals:
-                self._h_surf_grad[:count].copy_(surf['gradient'][0, :count], non_blocking=True)
-        if self.mesh_params is not None:
-            nv, nf = int(h[at]), int(h[at + 1])
-            if nv > self._mesh_rows[0] or nf > self._mesh_rows[1]:
-                raise _lib.GnrError(f'{nv} mesh vertices and {nf} triangles but the buffers hold {self._mesh_rows[0]} and '
-                                    f'{self._mesh_rows[1]}: raise surface_mesh max_vertices / max_faces')
-            mesh = self._out['mesh']
-            self._h_mesh_vertices[:nv].copy_(mesh['vertices'][0, :nv], non_blocking=True)
-            self._h_mesh_faces[:nf].copy_(mesh['faces'][0, :nf], non_blocking=True)
-            if self.surface_normals:
-                self._h_mesh_grad[:nv].copy_(mesh['gradient'][0, :nv], non_blocking=True)
-        if self.volume_depth_params is not None:
-            self._h_depth.copy_(self._out['volume_depth']['depth'][0], non_blocking=True)
-            if self.surface_normals:
-                self._h_depth_grad.copy_(self._out['volume_depth']['gradient'][0], non_blocking=True)
+        for p in self.products:
+            p.fetch(self._out[p.out], h[p.at:p.at + p.words].tolist())
         st.synchronize()
-        if self.volume_depth_params is not None:
-            self.volume_images = {'volume_depth': self._h_depth.numpy().copy()}
-            if self.surface_normals:
-                g = self._h_depth_grad.numpy()
-                self.volume_images['volume_depth_normals'] = unit_normals(g).reshape(g.shape)
-        if count is not None:
-            index = self._h_surf_index[:count].numpy().astype(np.int64)
-            colors = self._h_surf_colors[:count].numpy().astype(np.float64) if sp['color'] is None else \
-                np.array([sp['color']], np.float64).repeat(count, axis=0)
-            self.cloud = {'count': count, 'index': index, 'points': index.astype(np.float64) * float(sp['scale']), 'colors': colors}
-            if self.surface_normals:
-                self.cloud['gradient'] = self._h_surf_grad[:count].numpy().copy()
-                self.cloud['normals'] = unit_normals(self.cloud['gradient'])
-        if nv is not None:
-            self.mesh = {'vertices': self._h_mesh_vertices[:nv].numpy().copy(), 'faces': self._h_mesh_faces[:nf].numpy().astype(np.int64)}
-            if self.surface_normals:
-                self.mesh['gradient'] = self._h_mesh_grad[:nv].numpy().copy()
-                self.mesh['normals'] = unit_normals(self.mesh['gradient'])
+        for p in self.products:
+            setattr(self, p.attr, p.result())
 
-    def plan(self, frames_u8, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497)),
-             seed=None, return_volumes=False):
+    def plan(self, frames_u8, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=PLAN_BBOX3D, seed=None, return_volumes=False):
         """planner.plan() from raw frames: frames_u8 [V,h,w,c] uint8 (array, list of arrays, or a device tensor);
         extrinsics [V,3|4,4] world->camera; intrinsics [V,3,3] of the RESIZED images; depth_range [2] or [V,2].
         -> (grasps dict: pos, quat, width, score, index (+ volumes); seconds from before the first copy to after the read-back)."""
@@ -337,7 +354,7 @@ class PlannerSession:
         self.selection = {'count': h[0:1], 'index': h[1:1 + 3 * M].view(1, M, 3), 'score': f(1 + 3 * M, 1 + 4 * M),
                           'quat': f(1 + 4 * M, 1 + 8 * M, 4), 'width': f(1 + 8 * M, 1 + 9 * M),
                           'order': self.selector_params['order'], 'top_k': self.selector_params['top_k']}
-        if self.surface_params is not None or self.mesh_params is not None or self.volume_depth_params is not None:
+        if self.products:
             self._read_rows(h, st)
             dt = time.time() - t0
         grasps = grasps_from_selection(self.selection, 0, self.voxel_size, seed)

@@ -7,21 +7,52 @@ import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import unit_normals
+from .grasp_post import DeviceOp, checked_params, expand_cameras, gradient_batch, unit_normals, volume_batch
 
 RAYCAST_DEFAULTS = dict(iso=0.0, step=0.5, bisections=4)
 
 
-class VolumeRaycaster:
+def volume_origin(bbox_lo, voxel_size):
+    """World position of voxel (0,0,0)'s centre of the volume sampled over the box that starts at bbox_lo: the lattice origin of its
+    ray cast (float64)."""
+    return np.asarray(bbox_lo, np.float64) + 0.5 * voxel_size
+
+
+def depth_params(volume_depth, **more):
+    """A plan's `volume_depth` argument -> None, or the ray cast's parameters (True: the plan's own cameras and image size, iso = 0,
+    half-voxel steps, four bisections);  extrinsics -> float32 [V',3,4], intrinsic -> float32 [3,3], hw -> (h, w).  more: further keys
+    the caller takes, with their defaults (a session's `origin`)."""
+    out = checked_params('volume_depth', volume_depth, {'extrinsics': None, 'intrinsic': None, 'hw': None, **RAYCAST_DEFAULTS, **more})
+    if out is None:
+        return None
+    if out['extrinsics'] is not None:
+        ext = np.stack([np.asarray(e, np.float32) for e in out['extrinsics']], 0)
+        if ext.ndim != 3 or ext.shape[1:] not in ((3, 4), (4, 4)):
+            raise ValueError(f'volume_depth extrinsics must be V world->camera [3|4,4], got {ext.shape}')
+        out['extrinsics'] = np.ascontiguousarray(ext[:, :3, :])
+    if out['intrinsic'] is not None:
+        out['intrinsic'] = np.ascontiguousarray(np.asarray(out['intrinsic'], np.float32).reshape(3, 3))
+    if out['hw'] is not None:
+        out['hw'] = (int(out['hw'][0]), int(out['hw'][1]))
+    out['iso'], out['step'], out['bisections'] = float(out['iso']), float(out['step']), int(out['bisections'])
+    return out
+
+
+def same_depth_params(a, b):
+    """Whether two depth_params results ask for the same images (b may hold further keys)."""
+    if a is None or b is None:
+        return a is None and b is None
+    same = lambda x, y: (x is None and y is None) if (x is None or y is None) else np.array_equal(x, y)
+    return all(same(a[k], b.get(k)) for k in a)
+
+
+class VolumeRaycaster(DeviceOp):
     """The depth images [B,V,h,w] of the iso-surface vol = iso of B volumes from V cameras each; with a gradient volume also the
     gradient images [B,V,h,w,3].  The output buffers are kept per shape and written again by the next call of that shape, so their
     addresses are stable for a captured graph."""
 
     def __init__(self, device='cuda:0'):
-        self.L = _lib.lib()
-        if not torch.cuda.is_available():
-            raise _lib.GnrError('the HIP volume ray cast needs a ROCm GPU; there is no CPU fallback')
-        self.device = torch.device(device)
+        super().__init__(device, 'volume ray cast')
         self._out = {}
 
     def __call__(self, vol, poses, Ks, hw, *, origin, scale, iso=0.0, step=0.5, bisections=4, near=0.0, far=float('inf'), gradient=None):
@@ -31,26 +62,15 @@ class VolumeRaycaster:
         gradient volume [B,R,R,R,3] is given: its rows interpolated to the hit points, not normalised, 0 on a miss}.
         The tensors are this object's: the next call with the same shape writes them again."""
         d = self.device
-        vol = torch.as_tensor(vol, dtype=torch.float32, device=d).contiguous()
-        R = vol.shape[-1]
-        if vol.dim() < 3 or tuple(vol.shape[-3:]) != (R, R, R) or vol.numel() % R ** 3:
-            raise ValueError(f'vol must be [B,R,R,R], got {tuple(vol.shape)}')
-        B = vol.numel() // R ** 3
+        vol, B, R = volume_batch(vol, d)
         poses = torch.as_tensor(poses, dtype=torch.float32, device=d)
         Ks = torch.as_tensor(Ks, dtype=torch.float32, device=d)
         if poses.dim() not in (3, 4) or tuple(poses.shape[-2:]) != (3, 4) or Ks.dim() not in (3, 4) or tuple(Ks.shape[-2:]) != (3, 3):
             raise ValueError(f'poses must be [B,V,3,4] and Ks [B,V,3,3], got {tuple(poses.shape)} and {tuple(Ks.shape)}')
         V = poses.shape[-3]
-        try:
-            poses, Ks = poses.expand(B, V, 3, 4).contiguous(), Ks.expand(B, V, 3, 3).contiguous()
-        except RuntimeError:
-            raise ValueError(f'cameras {tuple(poses.shape)} / {tuple(Ks.shape)} do not fit {B} scene(s) of {V} view(s)') from None
+        poses, Ks = (c.contiguous() for c in expand_cameras(poses, Ks, B, V))
         h, w = int(hw[0]), int(hw[1])
-        g = None
-        if gradient is not None:
-            g = torch.as_tensor(gradient, dtype=torch.float32, device=d).contiguous()
-            if tuple(g.shape) != (B, R, R, R, 3):
-                raise ValueError(f'gradient must be [{B},{R},{R},{R},3], got {tuple(g.shape)}')
+        g = gradient_batch(gradient, B, R, d)
         key = (B, V, h, w, g is not None)
         out = self._out.get(key)
         if out is None:
@@ -62,20 +82,28 @@ class VolumeRaycaster:
                                   near_s=float(near), far_s=float(far))
         p.origin[:] = [float(c) for c in origin]
         rc = self.L.gnr_volume_raycast_fwd(C.byref(p), vol.data_ptr(), None if g is None else g.data_ptr(), poses.data_ptr(), Ks.data_ptr(),
-                                           out['depth'].data_ptr(), None if g is None else out['gradient'].data_ptr(),
-                                           C.c_void_p(torch.cuda.current_stream(d).cuda_stream))
+                                           out['depth'].data_ptr(), None if g is None else out['gradient'].data_ptr(), self._stream())
         _lib.check(rc, 'gnr_volume_raycast_fwd')
         return dict(out)
 
 
-def images_from_raycast(res, b=0):
-    """Scene b of a VolumeRaycaster result -> numpy dict: `volume_depth` [V,h,w] float32; a result with `gradient` adds
-    `volume_depth_normals` [V,h,w,3] float64 = g / |g| computed on the host like the cloud's (a miss stays zero)."""
-    out = {'volume_depth': res['depth'][b].cpu().numpy()}
-    if 'gradient' in res:
-        g = res['gradient'][b].cpu().numpy()
-        out['volume_depth_normals'] = unit_normals(g).reshape(g.shape)
+def raycast_rows(res, b):
+    """The device images of scene b of a VolumeRaycaster result."""
+    return {k: res[k][b] for k in ('depth', 'gradient') if k in res}
+
+
+def images_from_rows(rows):
+    """raycast_rows on the host (numpy) -> `volume_depth` [V,h,w] float32; with `gradient` also `volume_depth_normals` [V,h,w,3]
+    float64 = g / |g| computed on the host like the cloud's (a miss stays zero)."""
+    out = {'volume_depth': rows['depth']}
+    if 'gradient' in rows:
+        out['volume_depth_normals'] = unit_normals(rows['gradient']).reshape(rows['gradient'].shape)
     return out
+
+
+def images_from_raycast(res, b=0):
+    """Scene b of a VolumeRaycaster result -> numpy dict (images_from_rows)."""
+    return images_from_rows({k: v.cpu().numpy() for k, v in raycast_rows(res, b).items()})
 
 
 def depth_mae(depth, true_depth):

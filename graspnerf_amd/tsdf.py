@@ -11,25 +11,23 @@ import numpy as np
 import torch
 
 from . import _lib
+from .grasp_post import DeviceOp, expand_cameras
 
 
-def _rotation_from_quat(q):
-    """scipy's Rotation.from_quat(q).as_matrix() for (x, y, z, w), float64."""
-    x, y, z, w = np.asarray(q, np.float64) / np.linalg.norm(q)
+def rotation_matrix(q):
+    """scipy's Rotation.from_quat(q).as_matrix() of a UNIT quaternion (x, y, z, w), float64; the caller normalises."""
+    x, y, z, w = q
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
                      [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-class TSDFVolume:
+class TSDFVolume(DeviceOp):
     """Integration of posed depth images into B truncated signed distance volumes of `resolution`^3 voxels over the cube
     [origin, origin + size]^3; perception.py's TSDFVolume(size, resolution) is B = 1 with the origin at zero."""
 
     def __init__(self, size, resolution, B=1, origin=(0.0, 0.0, 0.0), device='cuda:0', sdf_trunc=None, depth_scale=1.0, depth_trunc=2.0):
-        self.L = _lib.lib()
-        if not torch.cuda.is_available():
-            raise _lib.GnrError('the HIP TSDF fusion needs a ROCm GPU; there is no CPU fallback')
-        self.device = torch.device(device)
+        super().__init__(device, 'TSDF fusion')
         self.size, self.resolution, self.B = float(size), int(resolution), int(B)
         self.voxel_size = self.size / self.resolution
         self.sdf_trunc = 4 * self.voxel_size if sdf_trunc is None else float(sdf_trunc)
@@ -42,9 +40,6 @@ class TSDFVolume:
         self.tsdf = torch.empty(self.B, R, R, R, device=self.device)
         self.weight = torch.empty(self.B, R, R, R, device=self.device)
         self.reset()
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def reset(self):
         _lib.check(self.L.gnr_tsdf_reset(self.B, self.resolution, self.tsdf.data_ptr(), self.weight.data_ptr(), self._stream()), 'gnr_tsdf_reset')
@@ -71,7 +66,6 @@ class TSDFVolume:
     def _cameras(self, intrinsic, extrinsic, V):
         """-> Ks [B,V,3,3], poses [B,V,3,4] float32 on the device.  Device tensors stay on the device (nothing waits for the host:
         a fusion from device tensors can be captured in a graph)."""
-        B = self.B
         if all(hasattr(intrinsic, k) for k in ('fx', 'fy', 'cx', 'cy')):                   # perception.CameraIntrinsic
             intrinsic = [[intrinsic.fx, 0.0, intrinsic.cx], [0.0, intrinsic.fy, intrinsic.cy], [0.0, 0.0, 1.0]]
         K = intrinsic if torch.is_tensor(intrinsic) else torch.from_numpy(np.asarray(intrinsic, np.float32))
@@ -82,17 +76,13 @@ class TSDFVolume:
             E = np.asarray(E, np.float64)
             if E.shape[-1] == 7 and E.shape[-2:] not in ((4, 4), (3, 4)):                  # Transform.to_list(): [qx,qy,qz,qw,tx,ty,tz]
                 flat = E.reshape(-1, 7)
-                E = np.stack([np.concatenate([_rotation_from_quat(e[:4]), e[4:, None]], 1) for e in flat]).reshape(E.shape[:-1] + (3, 4))
+                E = np.stack([np.concatenate([rotation_matrix(e[:4] / np.linalg.norm(e[:4])), e[4:, None]], 1) for e in flat]).reshape(E.shape[:-1] + (3, 4))
             E = torch.from_numpy(np.ascontiguousarray(E, np.float32))
         if E.shape[-2:] == (4, 4):
             E = E[..., :3, :]
         elif E.shape[-2:] != (3, 4):
             raise ValueError(f'extrinsic must be [..,4,4], [..,3,4] or [..,7], got {tuple(E.shape)}')
-        try:
-            K, E = K.expand(B, V, 3, 3), E.expand(B, V, 3, 4)
-        except RuntimeError:
-            raise ValueError(f'cameras {tuple(K.shape)} / {tuple(E.shape)} do not fit {B} scene(s) of {V} view(s)') from None
-        return K.to(self.device, torch.float32).contiguous(), E.to(self.device, torch.float32).contiguous()
+        return tuple(c.to(self.device, torch.float32).contiguous() for c in expand_cameras(K, E, self.B, V))
 
     def integrate(self, depth, intrinsic, extrinsic):
         """depth [h,w], [V,h,w] or [B,V,h,w], float32 or uint16 (numpy or device tensor), in units of 1 / depth_scale metres;

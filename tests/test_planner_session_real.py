@@ -46,7 +46,7 @@ def ctx():
     vol = planner.plan_real(net, A, **cam)[2]
     rg = (float(np.percentile(vol, 40)), float(np.percentile(vol, 60)))
     print(f'eager volume: min {vol.min():.4f} max {vol.max():.4f}, surface range {rg}')
-    return dict(net=net, cam=cam, A=A, B=B, rg=rg)
+    return dict(net=net, cam=cam, A=A, B=B, rg=rg, iso=float(np.float32(np.median(vol))))
 
 
 def _equal_plans(got, want, what):
@@ -110,6 +110,30 @@ def test_permuted_session_and_value_map_colours(ctx):
     assert col.cloud['count'] == c and len(np.unique(want['colors'])) > 100
     for k in ('index', 'points', 'colors'):
         assert same(col.cloud[k], want[k]), k
+
+
+def test_every_product_in_one_graph(ctx):
+    """Cloud with normals, mesh and depth images in ONE session: the count words of the cloud (1) and of the mesh (2) follow the
+    selection in that order, and the sized copies follow in the same order.  Every output of the first and third plan is bitwise the
+    eager plan_real's with the same three switches; the plan between them is another scene's."""
+    net, cam, A, B, rg, iso = (ctx[k] for k in ('net', 'cam', 'A', 'B', 'rg', 'iso'))
+    kw = dict(order='score', top_k=TOP_K, surface_rg=rg, normals=True, mesh=dict(iso=iso), volume_depth=dict(iso=iso))
+    sess = planner.real_session(net, V, HW, HW[::-1], max_grasps=MAX_GRASPS, **kw)
+    assert sess.captures == 1 and sess._d_out.numel() == 1 + 9 * MAX_GRASPS + 1 + 2
+    eA, eB = planner.plan_real(net, A, **cam, **kw), planner.plan_real(net, B, **cam, **kw)
+    m, img = eA[3]['mesh'], eA[3]['volume_depth']
+    assert len(m['vertices']) > 100 and len(m['faces']) > 100 and (img > 0).sum() > 100, 'the level set is too small to show anything'
+    plans = [planner.plan_real(net, f, **cam, **kw, session=sess) for f in (A, B, A)]
+    assert sess.captures == 1
+    for what, got, want in (('A', plans[0], eA), ('B', plans[1], eB), ('A, second replay', plans[2], eA)):
+        _equal_plans(got, want, what)
+        assert sorted(got[3]) == sorted([*want[3], 'count']), what                        # (a session's cloud also says its row count)
+        for k in ('gradient', 'normals', 'volume_depth', 'volume_depth_normals'):
+            assert same(got[3][k], want[3][k]), (what, k)
+        assert sorted(got[3]['mesh']) == sorted(want[3]['mesh']) == ['faces', 'gradient', 'normals', 'vertices'], what
+        for k in want[3]['mesh']:
+            assert same(got[3]['mesh'][k], want[3]['mesh'][k]), (what, 'mesh', k)
+    assert not same(eA[2], eB[2]) and not same(eA[3]['volume_depth'], eB[3]['volume_depth'])
 
 
 def test_session_without_the_new_arguments_is_todays_session(ctx):

@@ -64,6 +64,57 @@ def pct(x, p):
     return float(np.percentile(np.asarray(x) * 1e3, p))
 
 
+def synthetic_net(real=True):
+    """The synthetic checkpoint with a quality bias that leaves survivors; real: widths inside the 0..12 grasp_utils.process keeps."""
+    shapes = {k: tuple(v.shape) for k, v in GraspNeRF(dict(CFG)).state_dict().items()}
+    sd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth_state_dict(shapes).items()}
+    sd['vgn_net.conv_qual.bias'] = sd['vgn_net.conv_qual.bias'] + 2.5
+    if real:
+        sd['vgn_net.conv_width.bias'] = sd['vgn_net.conv_width.bias'] + 5.0
+    return planner.load_model(dict(CFG), sd)
+
+
+def session_legs(calls, legs, warmup=5):
+    """The real-robot plan through planner.real_session with and without one further output in the session's graph (tools/time_mesh.py,
+    tools/time_raycast.py): leg a, the ranked top-10 and the cloud; legs b and c, `legs(iso)` -> {name: further keywords of real_session
+    and plan_real} with iso the synthetic checkpoint's median level.  Host clock around the whole call, alternating.
+    -> (the result dict: shape, percentiles per leg, b / c minus a;  the last output of every leg;  iso)."""
+    net = synthetic_net()
+    hw = (IMG_WH[1], IMG_WH[0])
+    frames = np.random.default_rng(0).integers(0, 256, (V, *hw, 3), dtype=np.uint8)
+    poses = ring_cameras(V)
+    K = np.float32([[357.048, 0, 255.8], [0, 357.048, 143.8], [0, 0, 1]])
+    vol = planner.plan_real(net, frames, poses, K)[2]
+    rg = (float(np.percentile(vol, 40)), float(np.percentile(vol, 60)))
+    iso = float(np.float32(np.median(vol)))
+    kw = dict(order='score', top_k=10, surface_rg=rg)
+    a = 'a_session_ranked_top10_and_cloud'
+    legs = {a: {}, **legs(iso)}
+    sess = {k: planner.real_session(net, V, hw, IMG_WH, **kw, **m) for k, m in legs.items()}
+
+    def run(k):
+        t0 = time.perf_counter()
+        out = planner.plan_real(net, frames, poses, K, **kw, **legs[k], session=sess[k])
+        return time.perf_counter() - t0, out
+
+    for _ in range(warmup):
+        last = {k: run(k)[1] for k in legs}
+    times = {k: [] for k in legs}
+    for _ in range(calls):                                                   # alternating: the legs see the same machine state
+        for k in legs:
+            times[k].append(run(k)[0])
+    res = {'shape': {'views': V, 'frames_hw': hw, 'volume_resolution': 40, 'weights': 'synthetic'}, 'calls': calls, 'warmup': warmup,
+           'unit': 'ms, host clock around the whole plan_real(session=...) call (ends in a device synchronisation)',
+           'device': torch.cuda.get_device_name(0)}
+    for k, t in times.items():
+        res[k] = {q: pct(t, p) for q, p in (('p10', 10), ('p50', 50), ('p90', 90))}
+    res['same_grasps_and_cloud'] = bool(all(np.array_equal(last[k][0]['index'], last[a][0]['index']) and
+                                            np.array_equal(last[k][3]['index'], last[a][3]['index']) for k in legs))
+    b, c = list(legs)[1:]
+    res['b_minus_a_p50'], res['c_minus_a_p50'] = res[b]['p50'] - res[a]['p50'], res[c]['p50'] - res[a]['p50']
+    return res, last, iso
+
+
 def host_real_route(tsdf, qual, rot, width, top_k, rg):
     """grasp_utils.process + select + sim_grasp's ranking + extract_surface_points_from_volume on the host, as the reference runs
     them (scipy.ndimage; grasp_utils.py:40-105, draw_utils.py:355-377)."""
@@ -195,12 +246,7 @@ def main():
     a.out = a.out or os.path.join(ROOT, 'profiles', 'planner_session_real.json' if a.real else 'planner_session.json')
     if not torch.cuda.is_available():
         sys.exit('time_planner.py measures on a ROCm GPU; there is nothing to time without one')
-    shapes = {k: tuple(v.shape) for k, v in GraspNeRF(dict(CFG)).state_dict().items()}
-    sd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth_state_dict(shapes).items()}
-    sd['vgn_net.conv_qual.bias'] = sd['vgn_net.conv_qual.bias'] + 2.5
-    if a.real:
-        sd['vgn_net.conv_width.bias'] = sd['vgn_net.conv_width.bias'] + 5.0     # inside the 0..12 grasp_utils.process keeps
-    net = planner.load_model(dict(CFG), sd)
+    net = synthetic_net(a.real)
     if a.real:
         return main_real(a, net)
     rng = np.random.default_rng(0)

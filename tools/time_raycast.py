@@ -61,44 +61,11 @@ def kernels(a):
 
 def session(a):
     import time_planner as TP
-    shapes = {k: tuple(v.shape) for k, v in TP.GraspNeRF(dict(TP.CFG)).state_dict().items()}
-    sd = {k: torch.from_numpy(np.asarray(v)) for k, v in TP.synth_state_dict(shapes).items()}
-    sd['vgn_net.conv_qual.bias'] = sd['vgn_net.conv_qual.bias'] + 2.5
-    sd['vgn_net.conv_width.bias'] = sd['vgn_net.conv_width.bias'] + 5.0
-    net = planner.load_model(dict(TP.CFG), sd)
-    V, hw = 6, (TP.IMG_WH[1], TP.IMG_WH[0])
-    frames = np.random.default_rng(0).integers(0, 256, (V, *hw, 3), dtype=np.uint8)
-    poses = TP.ring_cameras(V)
-    vol = planner.plan_real(net, frames, poses, K)[2]
-    rg = (float(np.percentile(vol, 40)), float(np.percentile(vol, 60)))
-    iso = float(np.float32(np.median(vol)))
-    kw = dict(order='score', top_k=10, surface_rg=rg)
-    legs = {'a_session_ranked_top10_and_cloud': {}, 'b_with_volume_depth_iso0': dict(volume_depth=True),
-            'c_with_volume_depth_at_the_median': dict(volume_depth=dict(iso=iso))}
-    sess = {k: planner.real_session(net, V, hw, TP.IMG_WH, **kw, **m) for k, m in legs.items()}
-
-    def run(k):
-        t0 = time.perf_counter()
-        out = planner.plan_real(net, frames, poses, K, **kw, **legs[k], session=sess[k])
-        return time.perf_counter() - t0, out
-
-    for _ in range(5):
-        last = {k: run(k)[1] for k in legs}
-    times = {k: [] for k in legs}
-    for _ in range(a.calls):                                                 # alternating: the legs see the same machine state
-        for k in legs:
-            times[k].append(run(k)[0])
-    res = {'shape': {'views': V, 'frames_hw': hw, 'volume_resolution': 40, 'weights': 'synthetic', 'depth_images': [V, *hw]}, 'calls': a.calls, 'warmup': 5,
-           'unit': 'ms, host clock around the whole plan_real(session=...) call (ends in a device synchronisation)',
-           'device': torch.cuda.get_device_name(0)}
-    for k, t in times.items():
-        res[k] = {q: TP.pct(t, p) for q, p in (('p10', 10), ('p50', 50), ('p90', 90))}
+    res, last, _ = TP.session_legs(a.calls, lambda iso: {'b_with_volume_depth_iso0': dict(volume_depth=True),
+                                                         'c_with_volume_depth_at_the_median': dict(volume_depth=dict(iso=iso))})
+    res['shape']['depth_images'] = [TP.V, *res['shape']['frames_hw']]
     res['hit_share_iso0'] = round(float((last['b_with_volume_depth_iso0'][3]['volume_depth'] > 0).mean()), 4)
     res['hit_share_at_the_median'] = round(float((last['c_with_volume_depth_at_the_median'][3]['volume_depth'] > 0).mean()), 4)
-    res['same_grasps_and_cloud'] = bool(all(np.array_equal(last[k][0]['index'], last['a_session_ranked_top10_and_cloud'][0]['index']) and
-                                            np.array_equal(last[k][3]['index'], last['a_session_ranked_top10_and_cloud'][3]['index']) for k in legs))
-    res['b_minus_a_p50'] = res['b_with_volume_depth_iso0']['p50'] - res['a_session_ranked_top10_and_cloud']['p50']
-    res['c_minus_a_p50'] = res['c_with_volume_depth_at_the_median']['p50'] - res['a_session_ranked_top10_and_cloud']['p50']
     return res
 
 
