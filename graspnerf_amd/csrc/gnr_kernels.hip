@@ -706,6 +706,77 @@ DEV Taps make_taps(float u, float v, float sx, float sy, float off, int fh, int 
 // Measured negative, not in the sources (docs/experiments/coop_proj.patch; docs/lab_notebook.md "Removed switches"): the four lanes
 // of a point sharing the projection, one axis of one map each, exchanged through ds_bpermute_b32 -- 41 vector instructions per view
 // fewer and the same time: the exchange puts an LDS round trip at the head of each view's dependency chain.
+// What the inference instantiations of k_chain do instead splits the work BY VIEW (DESIGN.md 4.3 "one owner per (point, view)";
+// profiles/view_owner_ab.json): lane group g = v & 3 of a point owns view v and runs the projection (project_view<false>: two IEEE
+// divisions, the in-image test) and both tap computations for it ONCE; every lane fetches the finished records of ALL views before
+// the view loop, and a record waits in the state queue's row of its view (k_chain, phase 1), so nothing in a view's body waits for
+// an exchange and the records take no register of their own.
+
+// ---- the record of one (point, view) pair, 7 dwords.  Every packing is exact:
+//   fo       f.o00 << 1 | (m != 0)                      (o00 >= 0)
+//   fx, fy   wx1, wy1 of the feature-map taps; the sign bit says "x1i != x0i" / "y1i != y0i" (wx1, wy1 are px - floor(px) of a px >= 0:
+//            +0 or positive, so the sign bit is free; o01 = o00 + (x1i - x0i), o10 = o00 + (y1i - y0i) * fw as integers)
+//   io, ix, iy  the same of the full-resolution image taps
+//   z        as project_view leaves it
+// tap_axes + taps_of are make_taps cut in two, statement for statement (the weights are the same products of the same operands), and
+// everything in front of them is written with explicit roundings (__fmaf_rn, __fdiv_rn), so the record's values are the per-lane
+// code's bit for bit wherever the compiler puts them.  NOT in the record: the direction terms dd[] of project_view<true>.  They
+// are plain a * b + c expressions, which the compiler contracts into FMAs or not depending on the code around them (measured: an
+// owner's dd[1] came out fused where the per-lane code rounds the product first, 1 ulp apart), and the training forwards must keep
+// the inference launch's bits (tests/test_torch_ops.py): every lane computes them in the view's body as before.
+struct ViewRec {
+    int fo, io; float fx, fy, ix, iy, z;
+    static constexpr int N = 7;
+    template <int SWN> DEV void to_row(float (&row)[SWN]) const {          // (raw bits: a queue row is only ever moved)
+        row[0] = __int_as_float(fo); row[1] = __int_as_float(io); row[2] = fx; row[3] = fy; row[4] = ix; row[5] = iy; row[6] = z;
+    }
+    template <int SWN> DEV void from_row(const float (&row)[SWN]) {
+        fo = __float_as_int(row[0]); io = __float_as_int(row[1]); fx = row[2]; fy = row[3]; ix = row[4]; iy = row[5]; z = row[6];
+    }
+};
+// (xmax, ymax: (float)(fw - 1), (float)(fh - 1), converted once by the caller)
+DEV void tap_axes(float u, float v, float sx, float sy, float off, int fh, int fw, float ymax, float xmax, int& o00, float& x, float& y) {
+    float px = fmaf(u, sx, off), py = fmaf(v, sy, off);
+    px = fminf(fmaxf(px, 0.f), xmax);
+    py = fminf(fmaxf(py, 0.f), ymax);
+    const float x0 = floorf(px), y0 = floorf(py);
+    const float wx1 = px - x0, wy1 = py - y0;
+    const int x0i = (int)x0, y0i = (int)y0;
+    const int x1i = min(x0i + 1, fw - 1), y1i = min(y0i + 1, fh - 1);
+    o00 = y0i * fw + x0i;
+    x = __int_as_float(__float_as_int(wx1) | (x1i != x0i ? (int)0x80000000 : 0));
+    y = __int_as_float(__float_as_int(wy1) | (y1i != y0i ? (int)0x80000000 : 0));
+}
+DEV Taps taps_of(int o00, float x, float y, int fw) {
+    const int dx = (int)((unsigned)__float_as_int(x) >> 31), dy = (__float_as_int(y) >> 31) & fw;
+    const float wx1 = fabsf(x), wy1 = fabsf(y), wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+    Taps t;
+    t.o00 = o00; t.o01 = o00 + dx; t.o10 = o00 + dy; t.o11 = o00 + dy + dx;
+    t.w00 = wx0 * wy0; t.w01 = wx1 * wy0; t.w10 = wx0 * wy1; t.w11 = wx1 * wy1;
+    return t;
+}
+// the owner's side: vp is the LANE's view (per lane group), everything else as in the view loop
+struct ViewRecConsts { float fsx, fsy, fymax, fxmax, iymax, ixmax; };      // wave-uniform, in scalar registers (k_chain)
+DEV ViewRec make_view_rec(const float* __restrict__ vp, const float (&p)[3], int H, int W, int fh, int fw, const ViewRecConsts& c) {
+    const float qd[3] = {0.f, 0.f, 0.f};
+    ViewGeom vg;
+    project_view<false>(vp, p, qd, H, W, vg);
+    ViewRec o;
+    int fo;
+    tap_axes(vg.u, vg.v, c.fsx, c.fsy, -0.5f, fh, fw, c.fymax, c.fxmax, fo, o.fx, o.fy);
+    tap_axes(vg.u, vg.v, 1.f, 1.f, 0.f, H, W, c.iymax, c.ixmax, o.io, o.ix, o.iy);
+    o.fo = (fo << 1) | (vg.m != 0.f ? 1 : 0);
+    o.z = vg.z;
+    return o;
+}
+// every lane's side: the record of the lane at byte address bp (ds_bpermute_b32: the LDS crossbar, no LDS allocation)
+DEV ViewRec fetch_view_rec(const ViewRec& o, int bp) {
+    auto x = [&](float f) { return __int_as_float(__builtin_amdgcn_ds_bpermute(bp, __float_as_int(f))); };
+    ViewRec n;
+    n.fo = __builtin_amdgcn_ds_bpermute(bp, o.fo); n.io = __builtin_amdgcn_ds_bpermute(bp, o.io);
+    n.fx = x(o.fx); n.fy = x(o.fy); n.ix = x(o.ix); n.iy = x(o.iy); n.z = x(o.z);
+    return n;
+}
 
 constexpr int SW = 20;     // per-view state width: X[9] E[8] gate m rgb  /  H2[8] v2 c . . . rgb
 // The per-view state lives in registers, so its rows need static indices while the view loops stay rolled (code size): the
@@ -887,6 +958,7 @@ __global__ __launch_bounds__(kChainThreads, kChainMinBlocks) void k_chain(ChainA
         if (a.range_flag && (__builtin_nontemporal_load(a.range_flag) & 5u) != 0u) return;
     }
     bool range_tripped = false;                           // wave-uniform
+    constexpr bool OWN = !SAVE;                            // one owner per (point, view): ViewRec above (the training forwards keep the per-lane projection)
     constexpr bool EP = SP && !SAVE;                       // e1 travels between the view loops as its fp16 pair (the training saves keep fp32)
     // (in the pair kernels the slots LO(pk::RDF2), LO(pk::RGB2) and pk::ST_AT_RGB1X hold the STACKED fragments, not the fp32 ones: pk::stage_src4)
 #define LO(o) (SP ? pk::c16_off(o) : (o))                  /* offset of a CHAIN-section name inside the staged image */                    // fp16-pair layers on the f16 matrix cores (C16 image) / fp32 MFMA (CHAIN image)
@@ -921,6 +993,10 @@ __global__ __launch_bounds__(kChainThreads, kChainMinBlocks) void k_chain(ChainA
     const int ntiles = a.B * tps;
     constexpr int REC = RENDER ? REC_RAY : REC_VOL;
     const float fsx = (float)a.fw / (float)(a.W - 1), fsy = (float)a.fh / (float)(a.H - 1);
+    // OWN: what the owners' code needs of the launch's constants, as scalars (the same values: a readfirstlane of a uniform float) --
+    // left in vector registers they are live over the whole tile loop for a use once per tile, and spill
+    auto uni = [](float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
+    const ViewRecConsts rc = {uni(fsx), uni(fsy), uni((float)(a.fh - 1)), uni((float)(a.fw - 1)), uni((float)(a.H - 1)), uni((float)(a.W - 1))};
 
     // XCD-aware tile order: workgroup b runs on XCD b % 8 (observed dispatch order; only speed depends on
     // it).  Each XCD sweeps its own contiguous eighth of the tile list, so consecutive tiles (= neighbouring
@@ -1030,8 +1106,24 @@ __global__ __launch_bounds__(kChainThreads, kChainMinBlocks) void k_chain(ChainA
         // 36 -> 52 / 40 B on the inference volume launch; docs/lab_notebook.md "Removed switches".)
         auto phase1 = [&](auto& Q, const int v0) __attribute__((always_inline)) {
           constexpr int NQ = (int)(sizeof(Q) / sizeof(Q[0]));
+          // OWN: the records of all views, before the loop and in rounds of four views: lane group g computes the record of view
+          // w0 + g (a group without a view of its own repeats the last one; nobody fetches it), every lane fetches the round's records,
+          // and the next round reuses the owners' registers.  A record waits in the queue row its view's results will NOT need: row w
+          // is empty (zeros) until w views have left the front, and it is the FRONT row when view w starts -- so the records cost no
+          // register beyond the queue, and the queue's moves carry them to a static index while the loop stays rolled.
+          if constexpr (OWN) {
+              static_assert(NQ == V && ViewRec::N <= SW, "the records of all views wait in the rows of one queue");
+#pragma unroll
+              for (int w0 = 0; w0 < V; w0 += 4) {
+                  const ViewRec own = make_view_rec(a.viewp + (b * V + min(w0 + g, V - 1)) * VIEWP_FLOATS, p, a.H, a.W, a.fh, a.fw, rc);
+#pragma unroll
+                  for (int w = w0; w < (w0 + 4 < V ? w0 + 4 : V); ++w) fetch_view_rec(own, (r | ((w & 3) << 4)) << 2).to_row(Q[w]);
+              }
+          }
 #pragma unroll 1
           for (int v = v0; v < v0 + NQ; ++v) {
+            ViewRec cur;
+            if constexpr (OWN) cur.from_row(Q[0]);          // this view's record: the front row, before the queue advances
 #if !(GNR_ABLATE & 1)
 #pragma unroll
             for (int k = 0; k < NQ - 1; ++k)
@@ -1047,9 +1139,17 @@ __global__ __launch_bounds__(kChainThreads, kChainMinBlocks) void k_chain(ChainA
 #if GNR_ABLATE & 2
             vg = vg0; t = t0; ti = ti0;
 #else
-            project_view<true>(vp, p, qd, a.H, a.W, vg);
-            t = make_taps(vg.u, vg.v, fsx, fsy, -0.5f, a.fh, a.fw);
-            ti = make_taps(vg.u, vg.v, 1.f, 1.f, 0.f, a.H, a.W);
+            if constexpr (OWN) {
+                project_view<true>(vp, p, qd, a.H, a.W, vg);             // for dd[] alone, as in phase 2 (see ViewRec); the rest is the record's
+                vg.m = (cur.fo & 1) ? 1.f : 0.f;
+                vg.z = cur.z;
+                t = taps_of((int)((unsigned)cur.fo >> 1), cur.fx, cur.fy, a.fw);
+                ti = taps_of(cur.io, cur.ix, cur.iy, a.W);
+            } else {
+                project_view<true>(vp, p, qd, a.H, a.W, vg);
+                t = make_taps(vg.u, vg.v, fsx, fsy, -0.5f, a.fh, a.fw);
+                ti = make_taps(vg.u, vg.v, 1.f, 1.f, 0.f, a.H, a.W);
+            }
 #endif
             const float m = vg.m;
             msum += m;
