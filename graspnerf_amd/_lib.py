@@ -87,6 +87,12 @@ class GnrRaycastParams(C.Structure):
 GNR_RAYCAST_MAX_SAMPLES = 65536
 
 
+class GnrSurfaceColorParams(C.Structure):
+    _fields_ = [('B', C.c_int), ('V', C.c_int), ('H', C.c_int), ('W', C.c_int), ('R', C.c_int), ('iso', C.c_float), ('scale', C.c_double),
+                ('origin', C.c_double * 3), ('point_offset', C.c_double * 3), ('step', C.c_double), ('bias', C.c_double),
+                ('cos_min', C.c_double), ('fill', C.c_float * 3)]
+
+
 class GnrError(RuntimeError):
     pass
 
@@ -272,6 +278,10 @@ def lib():
     L.gnr_surface_mesh_fwd.restype = C.c_int
     L.gnr_volume_raycast_fwd.argtypes = [C.POINTER(GnrRaycastParams)] + [C.c_void_p] * 7
     L.gnr_volume_raycast_fwd.restype = C.c_int
+    L.gnr_surface_color_points_fwd.argtypes = [C.POINTER(GnrSurfaceColorParams)] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 7
+    L.gnr_surface_color_points_fwd.restype = C.c_int
+    L.gnr_surface_color_pixels_fwd.argtypes = [C.POINTER(GnrSurfaceColorParams)] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 7
+    L.gnr_surface_color_pixels_fwd.restype = C.c_int
     L.gnr_tsdf_reset.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnr_tsdf_reset.restype = C.c_int
     L.gnr_tsdf_integrate.argtypes = [C.POINTER(GnrTsdfParams)] + [C.c_void_p] * 7
@@ -336,7 +346,7 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd',
             'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd',
             'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid', 'gnr_surface_mesh_workspace_bytes', 'gnr_surface_mesh_fwd',
-            'gnr_volume_raycast_fwd',
+            'gnr_volume_raycast_fwd', 'gnr_surface_color_points_fwd', 'gnr_surface_color_pixels_fwd',
             'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 

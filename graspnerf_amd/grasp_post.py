@@ -79,6 +79,9 @@ def _call_defaults(cls, *skip):
     return {k: p.default for k, p in inspect.signature(cls.__call__).parameters.items() if p.default is not inspect.Parameter.empty and k not in skip}
 
 
+VIEW_KEYS = ('view_colors', 'view_weight', 'view_mask')     # what surface_color.SurfaceColorizer.points adds to an extractor's result
+
+
 def _host(rows):
     return {k: v.cpu().numpy() for k, v in rows.items()}
 
@@ -199,17 +202,20 @@ def surface_rows(res, b, n):
     scene has voxels in range."""
     if n > res['index'].shape[1]:
         raise _lib.GnrError(f'{n} surface voxels but the buffers hold {res["index"].shape[1]}: raise max_points')
-    return {k: res[k][b, :n] for k in ('index', 'points', 'colors', 'gradient') if k in res}
+    return {k: res[k][b, :n] for k in ('index', 'points', 'colors', 'gradient', *VIEW_KEYS) if k in res}
 
 
 def surface_from_rows(rows):
     """surface_rows on the host (numpy) -> the cloud: `index` [N,3] int64, `points` [N,3] float64 (metres), `colors` [N,3] float64 (what
     open3d's Vector3dVector holds); with `gradient` [N,3] float32 (the device's rows) also `normals` [N,3] float64 = g / |g| computed
-    here on the host (the convention of `points` = index * scale); a zero row stays zero."""
+    here on the host (the convention of `points` = index * scale); a zero row stays zero.  The view colours of a result that
+    SurfaceColorizer.points completed (VIEW_KEYS: `view_colors` [N,3] float32, `view_weight` [N] float32, `view_mask` [N] int32) pass
+    as they are."""
     out = {'index': rows['index'].astype(np.int64), 'points': rows['points'], 'colors': rows['colors'].astype(np.float64)}
     if 'gradient' in rows:
         out['gradient'] = rows['gradient']
         out['normals'] = unit_normals(out['gradient'])
+    out.update({k: rows[k] for k in VIEW_KEYS if k in rows})
     return out
 
 
@@ -275,16 +281,18 @@ def mesh_rows(res, b, nv, nf):
         raise _lib.GnrError(f'{nv} mesh vertices but the buffers hold {res["vertices"].shape[1]}: raise max_vertices')
     if nf > res['faces'].shape[1]:
         raise _lib.GnrError(f'{nf} mesh triangles but the buffers hold {res["faces"].shape[1]}: raise max_faces')
-    return {k: res[k][b, :nf if k == 'faces' else nv] for k in ('vertices', 'faces', 'gradient') if k in res}
+    return {k: res[k][b, :nf if k == 'faces' else nv] for k in ('vertices', 'faces', 'gradient', *VIEW_KEYS) if k in res}
 
 
 def mesh_from_rows(rows):
     """mesh_rows on the host (numpy) -> the mesh: `vertices` [N,3] float64, `faces` [F,3] int64; with `gradient` [N,3] float32 (the
-    device's rows) also `normals` [N,3] float64 = g / |g| (unit_normals, as for the cloud)."""
+    device's rows) also `normals` [N,3] float64 = g / |g| (unit_normals, as for the cloud); the view colours at the vertices
+    (VIEW_KEYS) pass as they are."""
     out = {'vertices': rows['vertices'], 'faces': rows['faces'].astype(np.int64)}
     if 'gradient' in rows:
         out['gradient'] = rows['gradient']
         out['normals'] = unit_normals(out['gradient'])
+    out.update({k: rows[k] for k in VIEW_KEYS if k in rows})
     return out
 
 
@@ -297,7 +305,8 @@ def write_ply(path, points, colors, normals=None, faces=None):
     """A point cloud as an ASCII PLY 1.0 file (draw_utils.py:382 writes open3d's): x y z as float64, colours in [0, 1] as uchar;
     normals [N,3]: nx ny nz as float64 between them (open3d's property order).  faces [F,3]: the points are a mesh's vertices and
     the file gains `element face F` with `property list uchar int vertex_indices` and a row "3 i j k" per triangle.  Without
-    normals and faces the file is what it was before."""
+    normals and faces the file is what it was before.  The view colours of a plan go in as they are: colors=cloud['view_colors'],
+    or a mesh's vertices with colors=mesh['view_colors']."""
     points, colors = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(colors, np.float64).reshape(-1, 3)
     if len(points) != len(colors):
         raise ValueError(f'{len(points)} points but {len(colors)} colours')

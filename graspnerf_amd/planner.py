@@ -17,6 +17,7 @@ from .grasp_post import GRASP_UTILS_PROCESS, MESH_DEFAULTS, GraspSelector, MeshE
 from .ingest import axis_tables
 from .planner_session import PLAN_BBOX3D, PlannerSession, deterministic_convolutions
 from .raycast import VolumeRaycaster, depth_params as _depth_params, images_from_raycast, same_depth_params as _same_depth_params, volume_origin
+from .surface_color import SurfaceColorizer, cloud_level, color_params as _color_params, march_params, same_color_params as _same_color_params
 from .tsdf import create_tsdf, rotation_matrix
 
 
@@ -123,11 +124,14 @@ def real_volume_origin():
 
 
 def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, mesh=False,
-                 volume_depth=False, **kw):
+                 volume_depth=False, view_colors=False, **kw):
     """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud
     (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True);  mesh: plan_real's, with the
-    triangle mesh of the volume's iso-surface in the graph;  volume_depth: plan_real's, with the ray cast of the volume in the graph)."""
-    vd, mp = _depth_params(volume_depth), _mesh_params(mesh)
+    triangle mesh of the volume's iso-surface in the graph;  volume_depth: plan_real's, with the ray cast of the volume in the graph;
+    view_colors: plan_real's, with the colouring of each of these from the plan's frames in the graph)."""
+    vd, mp, cp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors)
+    if cp is not None:
+        kw = dict(kw, view_colors=dict(cp, origin=tuple(real_volume_origin())))
     if vd is not None:
         kw = dict(kw, volume_depth=dict(vd, origin=tuple(real_volume_origin())))
     if normals:
@@ -140,7 +144,7 @@ def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, sur
 
 
 def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None,
-              normals=False, mesh=False, volume_depth=False):
+              normals=False, mesh=False, volume_depth=False, view_colors=False):
     """`run_real` (grasp_utils.py:119-151) without its file output: one plan from camera frames.
     images: V >= 4 uint8 frames [h,w,3] (list or array); extrinsics: V world->camera [3|4,4]; intrinsic [3,3], the same for every view.
     run_real's workspace box, depth range (0.2, 0.8) and query view 3; grasp_utils.process's thresholds (GRASP_UTILS_PROCESS),
@@ -162,10 +166,20 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     centres at REAL_BBOX3D[0] + (i + 0.5) * REAL_VOXEL_SIZE; `intrinsic` is that of the frames the network sees); with normals=True also
     `volume_depth_normals` [V,h,w,3] float64, unit vectors, zero on a miss.  volume_depth=dict(extrinsics=..., intrinsic=..., hw=...,
     iso=..., step=..., bisections=...) chooses other cameras, another image size or level; a session must have been built with the same
-    real_session(volume_depth=...).  Grasps, cloud and mesh do not depend on it."""
+    real_session(volume_depth=...).  Grasps, cloud and mesh do not depend on it.
+    view_colors=True: colours from the plan's own frames (surface_color.SurfaceColorizer; the float frames the network sees, the plan's
+    cameras).  The cloud dict gains `view_colors` [N,3] float32 -- per point the mean of the bilinear taps of the views that see it,
+    weighted by the cosine between the volume's normal there and the direction to each camera; a view sees a point that projects into
+    its image, faces it, and whose way to the camera crosses no voxel below the surface level -- `view_weight` [N] float32 (the sum of
+    those cosines; 0: no view, the colour is `fill`) and `view_mask` [N] int32 (bit v: view v contributed); `mesh` (with mesh on) gains
+    the same three at its vertices, and with volume_depth on the dict gains `volume_color` [V',h,w,3] and `volume_color_weight` [V',h,w]
+    float32 beside `volume_depth`: from other cameras an image-based rendering of the scene.  view_colors=dict(step=..., bias=...,
+    cos_min=..., fill=...): the occlusion march's step and its start off the point in voxels (0.5, 1.5), the least cosine (0) and the
+    colour without a view (black); a session must have been built with the same real_session(view_colors=...).  `colors` and every
+    other key do not depend on it; grasp_post.write_ply takes colors=cloud['view_colors']."""
     if order not in ('permuted', 'score'):
         raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
-    vd, mp = _depth_params(volume_depth), _mesh_params(mesh)
+    vd, mp, cp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors)
     ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
     V = ext.shape[0]
     if V <= REAL_QUE_ID:
@@ -180,9 +194,10 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         want = dict(GRASP_UTILS_PROCESS, order=sel_order, top_k=top_k)
         if session.net is not net or su is None or tuple(su['rg']) != tuple(surface_rg) or any(sp[k] != v for k, v in want.items()) \
                 or session.voxel_size != REAL_VOXEL_SIZE or bool(normals) != session.surface_normals \
-                or mp != session.mesh_params or not _same_depth_params(vd, session.volume_depth_params):
-            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range, normals, mesh or '
-                             'volume_depth (build it with planner.real_session)')
+                or mp != session.mesh_params or not _same_depth_params(vd, session.volume_depth_params) \
+                or not _same_color_params(cp, session.view_color_params):
+            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range, normals, mesh, '
+                             'volume_depth or view_colors (build it with planner.real_session)')
         g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
         tsdf_vol, cloud = g.pop('volumes')[0], session.cloud
         if session.mesh_params is not None:
@@ -206,9 +221,18 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         if normals:                                               # the volume's cameras again: the forward keeps no feature maps
             grad = _volume_gradient(net, imgs, ext, Ks, dev)
         res = SurfaceExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), rg=surface_rg, gradient=grad)     # grasp_utils.py:149
+        if cp is not None:                                        # the frames the network saw, the plan's cameras, the volume's lattice
+            paint, origin = SurfaceColorizer(dev), real_volume_origin()
+            src = (torch.as_tensor(imgs, device=dev), ext[:, :3, :], Ks)
+            lattice = dict(march_params(cp), origin=origin, scale=REAL_VOXEL_SIZE)
+            res.update(paint.points(torch.as_tensor(tsdf_vol, device=dev), res['points'], res['count'], *src, point_offset=origin,
+                                    iso=cloud_level(surface_rg), **lattice))
         cloud = surface_from_extraction(res, 0)
         if mp is not None:
             res = MeshExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), **mp, scale=REAL_VOXEL_SIZE, gradient=grad)
+            if cp is not None:
+                res.update(paint.points(torch.as_tensor(tsdf_vol, device=dev), res['vertices'], res['count'], *src, point_offset=origin,
+                                        iso=mp['iso'], **lattice))
             cloud['mesh'] = mesh_from_extraction(res, 0)
         if vd is not None:
             K = Ks[0] if vd['intrinsic'] is None else vd['intrinsic']
@@ -216,6 +240,9 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
             res = VolumeRaycaster(dev)(torch.as_tensor(tsdf_vol, device=dev), poses, np.repeat(K[None], len(poses), 0),
                                        frames.shape[1:3] if vd['hw'] is None else vd['hw'], origin=real_volume_origin(), scale=REAL_VOXEL_SIZE,
                                        iso=vd['iso'], step=vd['step'], bisections=vd['bisections'], gradient=grad)
+            if cp is not None:
+                res.update(paint.pixels(torch.as_tensor(tsdf_vol, device=dev), res['depth'], poses, np.repeat(K[None], len(poses), 0), *src,
+                                        iso=vd['iso'], **lattice))
             cloud.update(images_from_raycast(res, 0))
     tsdf_vol = np.asarray(tsdf_vol).reshape(tsdf_vol.shape[-3:])
     n = len(g['score'])

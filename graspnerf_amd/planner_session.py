@@ -13,10 +13,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import MESH_DEFAULTS, SELECTOR_DEFAULTS, SURFACE_DEFAULTS, GraspSelector, MeshExtractor, SurfaceExtractor, checked_params, \
-    grasps_from_selection, mesh_bounds, mesh_from_rows, mesh_rows, surface_from_rows, surface_rows
+from .grasp_post import MESH_DEFAULTS, SELECTOR_DEFAULTS, SURFACE_DEFAULTS, VIEW_KEYS, GraspSelector, MeshExtractor, SurfaceExtractor, \
+    checked_params, grasps_from_selection, mesh_bounds, mesh_from_rows, mesh_rows, surface_from_rows, surface_rows
 from .ingest import DeviceIngest
-from .raycast import VolumeRaycaster, depth_params, images_from_rows, raycast_rows, volume_origin
+from .raycast import COLOR_KEYS, VolumeRaycaster, depth_params, images_from_rows, raycast_rows, volume_origin
+from .surface_color import SurfaceColorizer, cloud_level, color_params, march_params
 
 _SEG = 64                                                    # floats: every camera block starts on a 256-byte boundary
 PLAN_BBOX3D = ((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497))       # the planner's workspace box (main.py:91): plan()'s default
@@ -40,6 +41,8 @@ def deterministic_convolutions(on=True):
 # fetch() / result(): the sized copies of one plan's rows and, after the session's one wait, the numpy dict -- through the same
 # *_rows / *_from_rows pair as the eager route (grasp_post.py, raycast.py).  PlannerSession builds the list `products` from its keywords
 # and names no product anywhere else; a new one is a class here, a keyword and one line in that list.
+# The view colours (`colors`: a _Colors, or None) are no product of their own: each product colours its own rows in its record(), right
+# after the step that makes them, and reads the colours back with them.
 class _Pinned:
     """Pinned host twins of the rows a product reads back: name=(shape, dtype)."""
 
@@ -61,18 +64,41 @@ def _gradient_rows(normals, *shape):
     return {'gradient': (shape, torch.float32)} if normals else {}
 
 
+def _view_rows(colors, *shape):
+    if colors is None:
+        return {}
+    return dict(zip(VIEW_KEYS, ((shape + (3,), torch.float32), (shape, torch.float32), (shape, torch.int32))))
+
+
+class _Colors:
+    """What a product needs to colour its rows from the plan's views (surface_color.SurfaceColorizer): the march's parameters, the
+    volume's lattice (origin, voxel size) and a colouriser of its own, whose kept buffers are the product's."""
+
+    def __init__(self, params, voxel_size, dev):
+        self.origin, self.op = params['origin'], SurfaceColorizer(dev)
+        self.kw = dict(march_params(params), origin=params['origin'], scale=voxel_size)
+
+    def points(self, vol, res, key, images, cams, iso):
+        """An extractor's result, completed with the view colours of its rows `key` (in the frame with origin 0)."""
+        res.update(self.op.points(vol, res[key], res['count'], images, cams['poses'], cams['Ks'], point_offset=self.origin, iso=iso, **self.kw))
+        return res
+
+
 class _Cloud:
     """The surface cloud: one count word; the index rows (the colours in value-map mode, the gradient rows with normals) are read back,
     the float64 points stay on the device and are recomputed on the host as index * scale, a fixed colour is known on the host."""
     out, attr, words = 'surface', 'cloud', 1
 
-    def __init__(self, params, R, normals, dev):
-        self.params, self.extract = params, SurfaceExtractor(dev)
+    def __init__(self, params, R, normals, dev, colors=None):
+        self.params, self.extract, self.colors = params, SurfaceExtractor(dev), colors
         n = R ** 3 if params['max_points'] is None else int(params['max_points'])
-        self.pinned = _Pinned(index=((n, 3), torch.int32), colors=((n, 3), torch.float32), **_gradient_rows(normals, n, 3))
+        self.pinned = _Pinned(index=((n, 3), torch.int32), colors=((n, 3), torch.float32), **_gradient_rows(normals, n, 3), **_view_rows(colors, n))
 
-    def record(self, vol, grad, cams):
-        return self.extract(vol, **self.params, gradient=grad)
+    def record(self, vol, grad, cams, images):
+        res = self.extract(vol, **self.params, gradient=grad)
+        if self.colors is not None:                          # occluded below the middle of the cloud's range (0 for the real route's)
+            self.colors.points(vol, res, 'points', images, cams, cloud_level(self.params['rg']))
+        return res
 
     def fetch(self, res, counts):
         rows = surface_rows(res, 0, *counts)
@@ -82,7 +108,7 @@ class _Cloud:
         self.pinned.fetch(rows)
 
     def result(self):
-        rows = self.pinned.host('gradient')
+        rows = self.pinned.host('gradient', *VIEW_KEYS)
         n = len(rows['index'])
         rows['points'] = rows['index'].astype(np.float64) * float(self.params['scale'])
         if 'colors' not in rows:
@@ -95,19 +121,23 @@ class _Mesh:
     triangles; the stored vertex, face (and gradient) rows are read back."""
     out, attr, words = 'mesh', 'mesh', 2
 
-    def __init__(self, params, R, normals, dev, scale):
-        self.params, self.scale, self.extract = params, scale, MeshExtractor(dev)
+    def __init__(self, params, R, normals, dev, scale, colors=None):
+        self.params, self.scale, self.extract, self.colors = params, scale, MeshExtractor(dev), colors
         nv, nf = (b if m is None else int(m) for b, m in zip(mesh_bounds(R), (params['max_vertices'], params['max_faces'])))
-        self.pinned = _Pinned(vertices=((nv, 3), torch.float64), faces=((nf, 3), torch.int32), **_gradient_rows(normals, nv, 3))
+        self.pinned = _Pinned(vertices=((nv, 3), torch.float64), faces=((nf, 3), torch.int32), **_gradient_rows(normals, nv, 3),
+                              **_view_rows(colors, nv))
 
-    def record(self, vol, grad, cams):
-        return self.extract(vol, **self.params, scale=self.scale, gradient=grad)
+    def record(self, vol, grad, cams, images):
+        res = self.extract(vol, **self.params, scale=self.scale, gradient=grad)
+        if self.colors is not None:                          # (the count's stride is 2: vertices, triangles)
+            self.colors.points(vol, res, 'vertices', images, cams, self.params['iso'])
+        return res
 
     def fetch(self, res, counts):
         self.pinned.fetch(mesh_rows(res, 0, *counts))
 
     def result(self):
-        return mesh_from_rows(self.pinned.host('vertices', 'gradient'))
+        return mesh_from_rows(self.pinned.host('vertices', 'gradient', *VIEW_KEYS))
 
 
 class _DepthImages:
@@ -115,29 +145,34 @@ class _DepthImages:
     the session's device block, which every plan uploads anyway; other cameras are the session's, uploaded once."""
     out, attr, words = 'volume_depth', 'volume_images', 0
 
-    def __init__(self, params, n_views, hw, voxel_size, normals, dev):
-        self.params, self.scale, self.cast = params, voxel_size, VolumeRaycaster(dev)
+    def __init__(self, params, n_views, hw, voxel_size, normals, dev, colors=None):
+        self.params, self.scale, self.cast, self.colors = params, voxel_size, VolumeRaycaster(dev), colors
         self.hw = hw if params['hw'] is None else params['hw']
         nv = n_views if params['extrinsics'] is None else len(params['extrinsics'])
         up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
         self.poses = up(params['extrinsics'])
         self.Ks = up(None if params['intrinsic'] is None else np.repeat(params['intrinsic'][None], nv, 0))
-        self.pinned = _Pinned(depth=((nv, *self.hw), torch.float32), **_gradient_rows(normals, nv, *self.hw, 3))
+        color_rows = {} if colors is None else dict(zip(COLOR_KEYS, (((nv, *self.hw, 3), torch.float32), ((nv, *self.hw), torch.float32))))
+        self.pinned = _Pinned(depth=((nv, *self.hw), torch.float32), **_gradient_rows(normals, nv, *self.hw, 3), **color_rows)
 
-    def record(self, vol, grad, cams):
+    def record(self, vol, grad, cams, images):
         p = self.params
         poses = cams['poses'] if self.poses is None else self.poses
         Ks = cams['Ks'] if self.Ks is None else self.Ks
         if Ks.shape[0] != poses.shape[0]:                    # the plan's own intrinsics (one per view, all equal on this route) for other cameras
             Ks = Ks[:1].expand(poses.shape[0], 3, 3)
-        return self.cast(vol, poses, Ks, self.hw, origin=p['origin'], scale=self.scale, iso=p['iso'], step=p['step'],
-                         bisections=p['bisections'], gradient=grad)
+        res = self.cast(vol, poses, Ks, self.hw, origin=p['origin'], scale=self.scale, iso=p['iso'], step=p['step'],
+                        bisections=p['bisections'], gradient=grad)
+        if self.colors is not None:                          # the ray cast's own lattice and level; the sources are the plan's views
+            res.update(self.colors.op.pixels(vol, res['depth'], poses, Ks, images, cams['poses'], cams['Ks'],
+                                             **dict(self.colors.kw, origin=p['origin']), iso=p['iso']))
+        return res
 
     def fetch(self, res, counts):
         self.pinned.fetch(raycast_rows(res, 0))
 
     def result(self):
-        return images_from_rows(self.pinned.host('depth'))
+        return images_from_rows(self.pinned.host('depth', *COLOR_KEYS))
 
 
 class PlannerSession:
@@ -170,10 +205,18 @@ class PlannerSession:
     of plan()'s default box; the spacing is voxel_size).  The images are read back in the cloud's sized step, and self.volume_images
     holds the last plan's: `volume_depth` [V,h,w] float32 (metres, 0: no surface), with surface_normals=True also `volume_depth_normals`
     [V,h,w,3] float64.
+    view_colors = dict(step=..., bias=..., cos_min=..., fill=..., origin=...) ({} for the defaults; needs at least one of the products
+    above): the colouring of every product's rows from the plan's own frames (surface_color.SurfaceColorizer: the ingested float images
+    self.images, the plan's poses and Ks) is recorded in the graph, each right after the product whose rows it reads.  self.cloud and
+    self.mesh gain `view_colors` [N,3] float32, `view_weight` [N] float32 and `view_mask` [N] int32 (bit v: view v contributed),
+    self.volume_images gains `volume_color` [V',h,w,3] and `volume_color_weight` [V',h,w] float32; they are read back in the same sized
+    step as the rows they colour.  origin: the world position of voxel (0,0,0)'s centre and of the cloud's and the mesh's origin (the
+    default is that of plan()'s default box).  Occluders are the voxels below the product's own level: the middle of the cloud's range,
+    the mesh's iso, the ray cast's iso.
     A session built without any of these records the graph it always recorded."""
 
     def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
-                 surface=None, surface_normals=False, surface_mesh=None, volume_depth=None, **selector_params):
+                 surface=None, surface_normals=False, surface_mesh=None, volume_depth=None, view_colors=None, **selector_params):
         cfg = net.nr_net.cfg
         if surface_normals and surface is None:
             raise ValueError('surface_normals=True needs the surface cloud: pass surface=dict(...) ({} for its defaults)')
@@ -185,6 +228,9 @@ class PlannerSession:
         self.surface_params, self.surface_normals = checked_params('surface', surface, SURFACE_DEFAULTS), bool(surface_normals)
         self.mesh_params = checked_params('mesh', surface_mesh, MESH_DEFAULTS)
         self.volume_depth_params = depth_params(volume_depth, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
+        self.view_color_params = color_params(view_colors, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
+        if self.view_color_params is not None and self.surface_params is None and self.mesh_params is None and self.volume_depth_params is None:
+            raise ValueError('view_colors needs a product to colour: pass surface=, surface_mesh= or volume_depth=')
         dev = next(net.parameters()).device
         if dev.type != 'cuda':
             raise _lib.GnrError('PlannerSession needs the model on a ROCm GPU; there is no CPU fallback')
@@ -217,12 +263,13 @@ class PlannerSession:
         # (+ the cloud's row count, when the session extracts one; + the mesh's vertex and triangle counts, likewise)
         R, normals = int(cfg['volume_resolution']), self.surface_normals
         self.products = []                                   # in the order of their count words and of their copies
+        colors = (lambda: None) if self.view_color_params is None else (lambda: _Colors(self.view_color_params, self.voxel_size, dev))
         if self.surface_params is not None:
-            self.products.append(_Cloud(self.surface_params, R, normals, dev))
+            self.products.append(_Cloud(self.surface_params, R, normals, dev, colors()))
         if self.mesh_params is not None:
-            self.products.append(_Mesh(self.mesh_params, R, normals, dev, (self.surface_params or SURFACE_DEFAULTS)['scale']))
+            self.products.append(_Mesh(self.mesh_params, R, normals, dev, (self.surface_params or SURFACE_DEFAULTS)['scale'], colors()))
         if self.volume_depth_params is not None:
-            self.products.append(_DepthImages(self.volume_depth_params, V, (H, W), self.voxel_size, normals, dev))
+            self.products.append(_DepthImages(self.volume_depth_params, V, (H, W), self.voxel_size, normals, dev, colors()))
         words = 1 + 9 * M
         for p in self.products:
             p.at, words = words, words + p.words
@@ -262,7 +309,7 @@ class PlannerSession:
         out = {'volume': vol, 'qual': q, 'rot': r, 'width': w, 'sel_qual': sel['qual']}
         grad = nr.sample_volume_gradient(ref, _prep=prep) if self.surface_normals else None
         for p in self.products:
-            out[p.out] = p.record(vol, grad, self._d)
+            out[p.out] = p.record(vol, grad, self._d, imgs)
             if p.words:
                 o[p.at:p.at + p.words].copy_(out[p.out]['count'].reshape(-1))
         return out

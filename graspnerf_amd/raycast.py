@@ -87,17 +87,22 @@ class VolumeRaycaster(DeviceOp):
         return dict(out)
 
 
+COLOR_KEYS = ('color', 'color_weight')                       # what of surface_color.SurfaceColorizer.pixels a plan keeps beside the depth
+
+
 def raycast_rows(res, b):
-    """The device images of scene b of a VolumeRaycaster result."""
-    return {k: res[k][b] for k in ('depth', 'gradient') if k in res}
+    """The device images of scene b of a VolumeRaycaster result (with the colour images, when SurfaceColorizer.pixels completed it)."""
+    return {k: res[k][b] for k in ('depth', 'gradient', *COLOR_KEYS) if k in res}
 
 
 def images_from_rows(rows):
     """raycast_rows on the host (numpy) -> `volume_depth` [V,h,w] float32; with `gradient` also `volume_depth_normals` [V,h,w,3]
-    float64 = g / |g| computed on the host like the cloud's (a miss stays zero)."""
+    float64 = g / |g| computed on the host like the cloud's (a miss stays zero); with `color` / `color_weight` also `volume_color`
+    [V,h,w,3] and `volume_color_weight` [V,h,w] float32, as they are."""
     out = {'volume_depth': rows['depth']}
     if 'gradient' in rows:
         out['volume_depth_normals'] = unit_normals(rows['gradient']).reshape(rows['gradient'].shape)
+    out.update({'volume_' + k: rows[k] for k in COLOR_KEYS if k in rows})
     return out
 
 

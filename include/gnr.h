@@ -747,6 +747,58 @@ int gnr_volume_raycast_fwd(const GnrRaycastParams* params, const float* vol /*[B
                            const float* poses /*[B,V,3,4]*/, const float* Ks /*[B,V,3,3]*/, float* depth /*[B,V,h,w]*/,
                            float* gradient /*[B,V,h,w,3], NULL iff grad is*/, void* stream);
 
+/* gnr_surface_color_points_fwd / gnr_surface_color_pixels_fwd: view colours of surface points of B volumes [B,R,R,R] -- each point takes
+ * the colour of the V source images [B,V,3,H,W] it is seen in, weighted by how squarely it faces each camera, with visibility decided
+ * by the volume itself (a march from the point towards the eye).  One kernel body; the two entry points differ only in where a point
+ * comes from: rows of a point array (the surface cloud, the mesh's vertices), or the pixels of depth images of gnr_volume_raycast_fwd
+ * (the result is then an image-based rendering of the scene from those cameras).  No reference counterpart;
+ * tests/surface_color_reference.py is the same statement in numpy and the calls produce its bits.  vol, images, poses, Ks, depth, iso and
+ * fill convert to float64 before the first operation; everything below is float64, single correctly rounded operations in the order
+ * written.  Lattice point i of the volume sits at world origin + i * scale (the ray cast's convention).
+ *   cameras    eye_a and the pixel ray dw_a of a camera exactly as in gnr_volume_raycast_fwd;  e_a = (eye_a - origin_a) / scale.
+ *   point      points:  x_a = point_offset_a + points[b,r,a] for r < min(count[b * count_stride], max_n); other rows are left untouched.
+ *              pixels:  s = depth[b,c,y,x];  s <= 0 (the ray cast's miss) gives fill, weight 0, views 0;  otherwise
+ *                       x_a = eye'_a + s * dw'_a with eye', dw' of the target camera c (cam_poses, cam_Ks) through pixel (x, y).
+ *              p_a = (x_a - origin_a) / scale.
+ *   normal     from the volume:  g_a = T(p + 0.5 u_a) - T(p - 0.5 u_a), u_a the unit vector of axis a and T the trilinear value of
+ *              gnr_volume_raycast_fwd (base clamp(floor(.), 0, R-2); z, then y, then x);  n2 = (g_x g_x + g_y g_y) + g_z g_z;
+ *              n2 == 0: no view contributes.
+ *   views      v = 0 .. V-1 in this order, each with its pose (R | t) and K:
+ *     project    pc_a = ((R[a][0] x_0 + R[a][1] x_1) + R[a][2] x_2) + t_a;  skip unless pc_z > 0.
+ *                u = pc_x * fx / pc_z + cx, v = pc_y * fy / pc_z + cy (pixel centres are integers);  skip unless 0 <= u <= W-1 and
+ *                0 <= v <= H-1.
+ *     facing     q_a = e_a - p_a;  L = sqrt((q_x q_x + q_y q_y) + q_z q_z);  skip if L == 0;  d_a = q_a / L;
+ *                c = ((g_x d_x + g_y d_y) + g_z d_z) / sqrt(n2);  skip unless c > cos_min.
+ *     occlusion  samples s_k = bias + (double)k * step, k = 0, 1, .., while s_k < L and k < nmax = ceil(sqrt(3) (R-1) / step) + 1 (the
+ *                ray cast's bound), at p + s_k d per component.  The first sample with a component outside [0, R-1] ends the march:
+ *                visible.  A sample with T - (double)iso < 0 ends it: occluded, the view is skipped.  Out of samples: visible.
+ *     colour     bilinear tap of images[b,v,ch] at (u, v): base clamp(floor(.), 0, size-2) per axis, t = coordinate - base; lerp along
+ *                x in both rows, then along y, each a + t * (b - a).  acc_ch += c * colour_ch;  Wsum += c;  views |= 1 << v.
+ *   result     colors_ch = (float)(acc_ch / Wsum) when Wsum > 0, else fill_ch;  weight = (float)Wsum;  views: the bit mask.
+ * 1 <= B <= 65535, 1 <= V <= 32 (the mask), H, W >= 2, 2 <= R <= 256, max_n >= 1, count_stride >= 1 (2 for the mesh's [B,2] counts);
+ * Vc, hc, wc >= 1 (at most 2^28 tiles of 8 x 8 pixels); scale, step finite and > 0, step large enough that nmax is at most
+ * GNR_RAYCAST_MAX_SAMPLES; bias finite and >= 0; iso, origin, point_offset, cos_min, fill finite.  Results on a volume or images that
+ * hold a NaN or an infinity are undefined, but no access leaves the volume or an image whatever the inputs hold.
+ * Asynchronous on `stream`, no atomics, no workspace, no allocation, no synchronisation (they can be captured in a graph); a refused
+ * call has launched nothing.                                                                                                  */
+typedef struct GnrSurfaceColorParams {
+    int B, V, H, W, R;
+    float iso;
+    double scale;
+    double origin[3];
+    double point_offset[3];                    /* points mode: the cloud and the mesh live in a frame with origin 0 */
+    double step, bias, cos_min;                /* 0.5 and 1.5 voxels, 0                                              */
+    float fill[3];                             /* the colour of a point no view contributes to                       */
+} GnrSurfaceColorParams;
+int gnr_surface_color_points_fwd(const GnrSurfaceColorParams* params, const float* vol /*[B,R,R,R]*/, const double* points /*[B,max_n,3]*/,
+                                 const int* count /*[B * count_stride]*/, int count_stride, int max_n, const float* images /*[B,V,3,H,W]*/,
+                                 const float* poses /*[B,V,3,4]*/, const float* Ks /*[B,V,3,3]*/, float* colors /*[B,max_n,3]*/,
+                                 float* weight /*[B,max_n]*/, int* views /*[B,max_n]*/, void* stream);
+int gnr_surface_color_pixels_fwd(const GnrSurfaceColorParams* params, const float* vol /*[B,R,R,R]*/, const float* depth /*[B,Vc,hc,wc]*/,
+                                 const float* cam_poses /*[B,Vc,3,4]*/, const float* cam_Ks /*[B,Vc,3,3]*/, int Vc, int hc, int wc,
+                                 const float* images /*[B,V,3,H,W]*/, const float* poses /*[B,V,3,4]*/, const float* Ks /*[B,V,3,3]*/,
+                                 float* colors /*[B,Vc,hc,wc,3]*/, float* weight /*[B,Vc,hc,wc]*/, int* views /*[B,Vc,hc,wc]*/, void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
