@@ -93,6 +93,14 @@ class GnrSurfaceColorParams(C.Structure):
                 ('cos_min', C.c_double), ('fill', C.c_float * 3)]
 
 
+GNR_HAND_MAX_SAMPLES = 4194304
+
+
+class GnrHandParams(C.Structure):
+    _fields_ = [('height', C.c_double), ('finger_width', C.c_double), ('tail_length', C.c_double), ('depth', C.c_double),
+                ('opening', C.c_double), ('spacing', C.c_double), ('approach', C.c_double), ('scale', C.c_double)]
+
+
 class GnrError(RuntimeError):
     pass
 
@@ -282,6 +290,8 @@ def lib():
     L.gnr_surface_color_points_fwd.restype = C.c_int
     L.gnr_surface_color_pixels_fwd.argtypes = [C.POINTER(GnrSurfaceColorParams)] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 7
     L.gnr_surface_color_pixels_fwd.restype = C.c_int
+    L.gnr_hand_clearance_fwd.argtypes = [C.POINTER(GnrHandParams)] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 4
+    L.gnr_hand_clearance_fwd.restype = C.c_int
     L.gnr_tsdf_reset.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnr_tsdf_reset.restype = C.c_int
     L.gnr_tsdf_integrate.argtypes = [C.POINTER(GnrTsdfParams)] + [C.c_void_p] * 7
@@ -346,7 +356,7 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd',
             'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd',
             'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid', 'gnr_surface_mesh_workspace_bytes', 'gnr_surface_mesh_fwd',
-            'gnr_volume_raycast_fwd', 'gnr_surface_color_points_fwd', 'gnr_surface_color_pixels_fwd',
+            'gnr_volume_raycast_fwd', 'gnr_surface_color_points_fwd', 'gnr_surface_color_pixels_fwd', 'gnr_hand_clearance_fwd',
             'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 

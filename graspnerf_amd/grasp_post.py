@@ -337,6 +337,70 @@ def write_ply(path, points, colors, normals=None, faces=None):
                 f.write(f'3 {i} {j} {k}\n')
 
 
+# the hand of draw_utils.draw_gripper_o3d (draw_utils.py:429-432), metres: four boxes in the grasp frame of gd/vis.py's draw_grasp -- z the
+# approach (the fingers point along +z), y the closing direction, x the hand's thickness
+HAND_GEOMETRY = dict(height=0.004, finger_width=0.004, tail_length=0.04, depth=0.05)
+
+
+def hand_boxes(width, height=0.004, finger_width=0.004, tail_length=0.04, depth=0.05):
+    """(lo [3], hi [3]) of the left finger, the right finger, the palm and the tail of a hand opened to `width` metres, in the grasp
+    frame: the boxes hand.HandClearance samples (include/gnr.h, gnr_hand_clearance_fwd) and hand_mesh draws."""
+    h, f, t, d, w = float(height), float(finger_width), float(tail_length), float(depth), float(width)
+    return (((-h / 2, -w / 2 - f, -f), (h / 2, -w / 2, d)), ((-h / 2, w / 2, -f), (h / 2, w / 2 + f, d)),
+            ((-h / 2, -w / 2, -f), (h / 2, w / 2, 0.0)), ((-h / 2, -f / 2, -t - f), (h / 2, f / 2, -f)))
+
+
+def _box_faces():
+    """The 12 triangles of a box whose corner 4 i + 2 j + k sits at (x_i, y_j, z_k), 0 the low and 1 the high end: two per side, wound
+    counter-clockwise seen from outside."""
+    out = []
+    for a in range(3):
+        u, v = (a + 1) % 3, (a + 2) % 3                      # u x v = +a
+        for side in (0, 1):
+            quad = []
+            for cu, cv in ((0, 0), (1, 0), (1, 1), (0, 1)):  # counter-clockwise about +a
+                bits = [0, 0, 0]
+                bits[a], bits[u], bits[v] = side, cu, cv
+                quad.append(4 * bits[0] + 2 * bits[1] + bits[2])
+            quad = quad if side else quad[::-1]
+            out += [(quad[0], quad[1], quad[2]), (quad[0], quad[2], quad[3])]
+    return np.array(out, np.int64)
+
+
+BOX_FACES = _box_faces()
+
+
+def hand_mesh(grasps, scores=None, opening=None, **hand):
+    """The gripper mesh of visualize_grasping_3d / draw_gripper_o3d (database.py:260-276, draw_utils.py:408-480) for a list of grasps, on
+    the host: grasps = a plan's dict (`pos` [n,3] metres in the cloud's frame, `quat` [n,4] (x, y, z, w), `width` [n] metres);  scores
+    [n]: the colour, (score, 0, 1 - score) per vertex as in draw_gripper_o3d (None: the grasps' own `score`);  opening: one opening in
+    metres for every hand (None: each grasp's width);  hand: HAND_GEOMETRY's keys.
+    -> {'vertices': [32 n,3] float64, 'faces': [48 n,3] int64, 'colors': [32 n,3] float64}: per grasp the 8 corners of the left finger,
+    the right finger, the palm and the tail (hand_boxes; corner 4 i + 2 j + k of a box at (x_i, y_j, z_k)), 12 outward triangles each.
+    write_ply(path, m['vertices'], m['colors'], faces=m['faces']) writes it."""
+    from .tsdf import rotation_matrix
+    geometry = checked_params('hand', hand, HAND_GEOMETRY)
+    pos = np.asarray(grasps['pos'], np.float64).reshape(-1, 3)
+    quat = np.asarray(grasps['quat'], np.float64).reshape(-1, 4)
+    width = np.asarray(grasps['width'], np.float64).reshape(-1)
+    n = len(pos)
+    if len(quat) != n or len(width) != n:
+        raise ValueError(f'{n} positions but {len(quat)} quaternions and {len(width)} widths')
+    scores = np.asarray(grasps['score'] if scores is None else scores, np.float64).reshape(-1)
+    if len(scores) != n:
+        raise ValueError(f'{n} grasps but {len(scores)} scores')
+    corner = np.array([[i, j, k] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
+    vertices, faces = np.zeros((n, 32, 3)), np.zeros((n, 48, 3), np.int64)
+    for g in range(n):
+        M = rotation_matrix(quat[g] / max(np.linalg.norm(quat[g]), 1e-12))
+        for b, (lo, hi) in enumerate(hand_boxes(width[g] if opening is None else opening, **geometry)):
+            local = np.where(corner == 1, np.array(hi), np.array(lo))
+            vertices[g, 8 * b:8 * b + 8] = pos[g] + local @ M.T
+            faces[g, 12 * b:12 * b + 12] = BOX_FACES + (32 * g + 8 * b)
+    colors = np.repeat(np.stack([scores, np.zeros(n), 1.0 - scores], 1), 32, axis=0)
+    return {'vertices': vertices.reshape(-1, 3), 'faces': faces.reshape(-1, 3), 'colors': colors}
+
+
 def grasps_from_selection(sel, b=0, voxel_size=0.3 / 40, seed=None):
     """Scene b of a GraspSelector result -> numpy dict in the reference's conventions (main.py:79-84,201-209):
     `pos` = voxel index * voxel_size (metres, bbox-local), `quat` normalised (x,y,z,w; scipy Rotation.from_quat),

@@ -14,6 +14,8 @@ import torch
 from .renderer import GraspNeRF
 from .grasp_post import GRASP_UTILS_PROCESS, MESH_DEFAULTS, GraspSelector, MeshExtractor, SurfaceExtractor, checked_params, \
     grasps_from_selection, mesh_from_extraction, surface_from_extraction
+from .hand import HandClearance, device_params as _hand_device_params, hand_from_rows, hand_params as _hand_params, hand_rows, \
+    same_hand_params as _same_hand_params
 from .ingest import axis_tables
 from .planner_session import PLAN_BBOX3D, PlannerSession, deterministic_convolutions
 from .raycast import VolumeRaycaster, depth_params as _depth_params, images_from_raycast, same_depth_params as _same_depth_params, volume_origin
@@ -124,12 +126,15 @@ def real_volume_origin():
 
 
 def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, mesh=False,
-                 volume_depth=False, view_colors=False, **kw):
+                 volume_depth=False, view_colors=False, clearance=False, **kw):
     """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud
     (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True);  mesh: plan_real's, with the
     triangle mesh of the volume's iso-surface in the graph;  volume_depth: plan_real's, with the ray cast of the volume in the graph;
-    view_colors: plan_real's, with the colouring of each of these from the plan's frames in the graph)."""
-    vd, mp, cp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors)
+    view_colors: plan_real's, with the colouring of each of these from the plan's frames in the graph;  clearance: plan_real's, with
+    the gripper clearance of the stored grasps in the graph)."""
+    vd, mp, cp, hp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors), _hand_params(clearance, filter=False)
+    if hp is not None:
+        kw = dict(kw, hand_clearance={k: v for k, v in hp.items() if k != 'filter'})
     if cp is not None:
         kw = dict(kw, view_colors=dict(cp, origin=tuple(real_volume_origin())))
     if vd is not None:
@@ -144,7 +149,7 @@ def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, sur
 
 
 def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None,
-              normals=False, mesh=False, volume_depth=False, view_colors=False):
+              normals=False, mesh=False, volume_depth=False, view_colors=False, clearance=False):
     """`run_real` (grasp_utils.py:119-151) without its file output: one plan from camera frames.
     images: V >= 4 uint8 frames [h,w,3] (list or array); extrinsics: V world->camera [3|4,4]; intrinsic [3,3], the same for every view.
     run_real's workspace box, depth range (0.2, 0.8) and query view 3; grasp_utils.process's thresholds (GRASP_UTILS_PROCESS),
@@ -176,10 +181,21 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     float32 beside `volume_depth`: from other cameras an image-based rendering of the scene.  view_colors=dict(step=..., bias=...,
     cos_min=..., fill=...): the occlusion march's step and its start off the point in voxels (0.5, 1.5), the least cosine (0) and the
     colour without a view (black); a session must have been built with the same real_session(view_colors=...).  `colors` and every
-    other key do not depend on it; grasp_post.write_ply takes colors=cloud['view_colors']."""
+    other key do not depend on it; grasp_post.write_ply takes colors=cloud['view_colors'].
+    clearance=True: whether the hand fits where each grasp puts it, answered from the volume (hand.HandClearance; execute_grasp,
+    gd/simulation.py:369-402, answers it with physics).  The grasps dict gains `clearance` and `approach_clearance` [n] float32 -- the
+    smallest tsdf value under the four boxes of draw_gripper_o3d's hand at the grasp, and over everything they pass through on the
+    5 cm approach along the grasp's z; 1.0: nothing of the hand is inside the volume -- `hand_inside` and `hand_worst` [n,2] int32 (the
+    samples the volume could vouch for and the ordinal of the worst, at the grasp and on the approach) and `collision_free` [n] bool =
+    approach_clearance > level.  clearance=dict(height=..., finger_width=..., tail_length=..., depth=..., opening=..., spacing=...,
+    approach=..., level=..., filter=...): a real hand's dimensions in metres (the defaults are the viewer's), one opening for every grasp
+    (None: each grasp's own width; hand.EXECUTE_GRASP_OPENING is execute_grasp's 0.08), the samples' spacing in voxels, the approach in
+    metres, the level (0) -- and filter=True keeps only the collision_free rows of every column, in their order.  A session must have
+    been built with the same real_session(clearance=...) (`filter` aside).  No other key depends on it; grasp_post.hand_mesh draws the
+    same boxes."""
     if order not in ('permuted', 'score'):
         raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
-    vd, mp, cp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors)
+    vd, mp, cp, hp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors), _hand_params(clearance, filter=False)
     ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
     V = ext.shape[0]
     if V <= REAL_QUE_ID:
@@ -198,6 +214,9 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
                 or not _same_color_params(cp, session.view_color_params):
             raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range, normals, mesh, '
                              'volume_depth or view_colors (build it with planner.real_session)')
+        if not _same_hand_params(hp, getattr(session, 'hand_params', None)):
+            raise ValueError('plan_real(session=...): the session was built for another clearance (build it with '
+                             'planner.real_session(clearance=...))')
         g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
         tsdf_vol, cloud = g.pop('volumes')[0], session.cloud
         if session.mesh_params is not None:
@@ -211,12 +230,20 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
             raise ValueError(f'images must be uint8 [V,h,w,3] frames, got {frames.dtype} {frames.shape}')
         imgs = (frames.astype(np.float32) / 255).transpose([0, 3, 1, 2])                                  # color_map_forward, grasp_utils.py:134
         selector = GraspSelector(dev)
-        call = lambda vol, q, r, w, **kw: selector(vol, q, r, w, **{**kw, **GRASP_UTILS_PROCESS})
+        kept = {}                                                 # the device volume and selection of the plan, for the hand
+
+        def call(vol, q, r, w, **kw):
+            kept['vol'], kept['sel'] = vol, selector(vol, q, r, w, **{**kw, **GRASP_UTILS_PROCESS})
+            return kept['sel']
         with deterministic_convolutions():                        # the solvers a PlannerSession records: the same frames, the same bits
             g, dt = plan(net, imgs, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, selector=call, voxel_size=REAL_VOXEL_SIZE,
                          tsdf_thres_high=GRASP_UTILS_PROCESS['tsdf_thres_high'], tsdf_thres_low=GRASP_UTILS_PROCESS['tsdf_thres_low'],
                          order=sel_order, top_k=top_k, return_volumes=True, que_id=REAL_QUE_ID)
         tsdf_vol = g.pop('volumes')[0]
+        if hp is not None:                                        # positions are voxel indices: the lattice is the volume's own
+            res = HandClearance(dev).of_selection(kept['vol'], kept['sel'], scale=REAL_VOXEL_SIZE, **_hand_device_params(hp))
+            rows = hand_rows(res, 0, len(g['score']))
+            g.update(hand_from_rows({k: v.cpu().numpy() for k, v in rows.items()}, hp['level']))
         grad = None
         if normals:                                               # the volume's cameras again: the forward keeps no feature maps
             grad = _volume_gradient(net, imgs, ext, Ks, dev)
@@ -251,6 +278,8 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
             np.random.seed(seed)
         p = np.random.permutation(n)
         g = {k: v[p] for k, v in g.items()}
+    if hp is not None and hp['filter']:
+        g = {k: v[g['collision_free']] for k, v in g.items()}
     return g, g['score'], tsdf_vol, cloud, dt
 
 

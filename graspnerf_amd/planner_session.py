@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from .grasp_post import MESH_DEFAULTS, SELECTOR_DEFAULTS, SURFACE_DEFAULTS, VIEW_KEYS, GraspSelector, MeshExtractor, SurfaceExtractor, \
     checked_params, grasps_from_selection, mesh_bounds, mesh_from_rows, mesh_rows, surface_from_rows, surface_rows
+from .hand import HandClearance, device_params, hand_from_rows, hand_params, hand_rows
 from .ingest import DeviceIngest
 from .raycast import COLOR_KEYS, VolumeRaycaster, depth_params, images_from_rows, raycast_rows, volume_origin
 from .surface_color import SurfaceColorizer, cloud_level, color_params, march_params
@@ -37,10 +38,12 @@ def deterministic_convolutions(on=True):
 
 # ---- the optional products of the volume ---------------------------------------------------------------------------------------------
 # A product is one further output of the session's graph.  It owns (1) its normalised parameters, (2) its extractor, its pinned read-back
-# buffers and the number of count words it appends to the packed selection, (3) record(): its step of the captured forward, and (4)
-# fetch() / result(): the sized copies of one plan's rows and, after the session's one wait, the numpy dict -- through the same
+# buffers and the number of count words it appends to the packed selection, (3) record(): its step of the captured forward (it gets the
+# volume, its gradient, the cameras, the ingested frames and the selection), and (4) fetch() / result(): the sized copies of one plan's
+# rows (by its own count words, or by the number of stored grasps) and, after the session's one wait, the numpy dict -- through the same
 # *_rows / *_from_rows pair as the eager route (grasp_post.py, raycast.py).  PlannerSession builds the list `products` from its keywords
-# and names no product anywhere else; a new one is a class here, a keyword and one line in that list.
+# and names no product anywhere else (but for plan(), which merges the hand's columns into the grasps it returns); a new one is a class
+# here, a keyword and one line in that list.
 # The view colours (`colors`: a _Colors, or None) are no product of their own: each product colours its own rows in its record(), right
 # after the step that makes them, and reads the colours back with them.
 class _Pinned:
@@ -94,13 +97,13 @@ class _Cloud:
         n = R ** 3 if params['max_points'] is None else int(params['max_points'])
         self.pinned = _Pinned(index=((n, 3), torch.int32), colors=((n, 3), torch.float32), **_gradient_rows(normals, n, 3), **_view_rows(colors, n))
 
-    def record(self, vol, grad, cams, images):
+    def record(self, vol, grad, cams, images, sel):
         res = self.extract(vol, **self.params, gradient=grad)
         if self.colors is not None:                          # occluded below the middle of the cloud's range (0 for the real route's)
             self.colors.points(vol, res, 'points', images, cams, cloud_level(self.params['rg']))
         return res
 
-    def fetch(self, res, counts):
+    def fetch(self, res, counts, n_sel):
         rows = surface_rows(res, 0, *counts)
         del rows['points']
         if self.params['color'] is not None:
@@ -127,13 +130,13 @@ class _Mesh:
         self.pinned = _Pinned(vertices=((nv, 3), torch.float64), faces=((nf, 3), torch.int32), **_gradient_rows(normals, nv, 3),
                               **_view_rows(colors, nv))
 
-    def record(self, vol, grad, cams, images):
+    def record(self, vol, grad, cams, images, sel):
         res = self.extract(vol, **self.params, scale=self.scale, gradient=grad)
         if self.colors is not None:                          # (the count's stride is 2: vertices, triangles)
             self.colors.points(vol, res, 'vertices', images, cams, self.params['iso'])
         return res
 
-    def fetch(self, res, counts):
+    def fetch(self, res, counts, n_sel):
         self.pinned.fetch(mesh_rows(res, 0, *counts))
 
     def result(self):
@@ -155,7 +158,7 @@ class _DepthImages:
         color_rows = {} if colors is None else dict(zip(COLOR_KEYS, (((nv, *self.hw, 3), torch.float32), ((nv, *self.hw), torch.float32))))
         self.pinned = _Pinned(depth=((nv, *self.hw), torch.float32), **_gradient_rows(normals, nv, *self.hw, 3), **color_rows)
 
-    def record(self, vol, grad, cams, images):
+    def record(self, vol, grad, cams, images, sel):
         p = self.params
         poses = cams['poses'] if self.poses is None else self.poses
         Ks = cams['Ks'] if self.Ks is None else self.Ks
@@ -168,11 +171,31 @@ class _DepthImages:
                                              **dict(self.colors.kw, origin=p['origin']), iso=p['iso']))
         return res
 
-    def fetch(self, res, counts):
+    def fetch(self, res, counts, n_sel):
         self.pinned.fetch(raycast_rows(res, 0))
 
     def result(self):
         return images_from_rows(self.pinned.host('depth', *COLOR_KEYS))
+
+
+class _Hand:
+    """The gripper clearance of the selected grasps (hand.HandClearance): no count word -- its rows are the selection's, read back sized
+    by the selection's count.  It reads the selection, so it is recorded right after it."""
+    out, attr, words = 'hand', 'hand', 0
+
+    def __init__(self, params, max_grasps, voxel_size, dev):
+        self.params, self.scale, self.op = params, voxel_size, HandClearance(dev)
+        self.pinned = _Pinned(clearance=((max_grasps, 2), torch.float32), worst=((max_grasps, 2), torch.int32),
+                              inside=((max_grasps, 2), torch.int32))
+
+    def record(self, vol, grad, cams, images, sel):
+        return self.op.of_selection(vol, sel, scale=self.scale, **device_params(self.params))
+
+    def fetch(self, res, counts, n_sel):
+        self.pinned.fetch(hand_rows(res, 0, n_sel))
+
+    def result(self):
+        return hand_from_rows(self.pinned.host(), self.params['level'])
 
 
 class PlannerSession:
@@ -213,10 +236,17 @@ class PlannerSession:
     step as the rows they colour.  origin: the world position of voxel (0,0,0)'s centre and of the cloud's and the mesh's origin (the
     default is that of plan()'s default box).  Occluders are the voxels below the product's own level: the middle of the cloud's range,
     the mesh's iso, the ray cast's iso.
+    hand_clearance = dict(height=..., finger_width=..., tail_length=..., depth=..., opening=..., spacing=..., approach=..., level=...) ({}
+    for the defaults): the gripper clearance of the stored grasps against the volume (hand.HandClearance: positions are the voxel indices,
+    the lattice is the volume's own) is recorded right after the selection.  Its rows are read back sized by the selection's count, and
+    plan()'s grasps gain `clearance` and `approach_clearance` [n] float32 (the smallest value of the volume under the hand at the grasp
+    and on its approach), `hand_inside` and `hand_worst` [n,2] int32 and `collision_free` [n] bool = approach_clearance > level, through
+    the same permutation as the other columns; self.hand holds them in the selection's order.
     A session built without any of these records the graph it always recorded."""
 
     def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
-                 surface=None, surface_normals=False, surface_mesh=None, volume_depth=None, view_colors=None, **selector_params):
+                 surface=None, surface_normals=False, surface_mesh=None, volume_depth=None, view_colors=None, hand_clearance=None,
+                 **selector_params):
         cfg = net.nr_net.cfg
         if surface_normals and surface is None:
             raise ValueError('surface_normals=True needs the surface cloud: pass surface=dict(...) ({} for its defaults)')
@@ -229,6 +259,7 @@ class PlannerSession:
         self.mesh_params = checked_params('mesh', surface_mesh, MESH_DEFAULTS)
         self.volume_depth_params = depth_params(volume_depth, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
         self.view_color_params = color_params(view_colors, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
+        self.hand_params = hand_params(hand_clearance)
         if self.view_color_params is not None and self.surface_params is None and self.mesh_params is None and self.volume_depth_params is None:
             raise ValueError('view_colors needs a product to colour: pass surface=, surface_mesh= or volume_depth=')
         dev = next(net.parameters()).device
@@ -264,6 +295,8 @@ class PlannerSession:
         R, normals = int(cfg['volume_resolution']), self.surface_normals
         self.products = []                                   # in the order of their count words and of their copies
         colors = (lambda: None) if self.view_color_params is None else (lambda: _Colors(self.view_color_params, self.voxel_size, dev))
+        if self.hand_params is not None:                     # first: it reads the selection, nothing of the other products
+            self.products.append(_Hand(self.hand_params, M, self.voxel_size, dev))
         if self.surface_params is not None:
             self.products.append(_Cloud(self.surface_params, R, normals, dev, colors()))
         if self.mesh_params is not None:
@@ -275,7 +308,7 @@ class PlannerSession:
             p.at, words = words, words + p.words
         self._d_out = torch.zeros(words, dtype=torch.int32, device=dev)
         self._h_out = torch.zeros(words, dtype=torch.int32, pin_memory=True)
-        self.selection = self.cloud = self.mesh = self.volume_images = None
+        self.selection = self.cloud = self.mesh = self.volume_images = self.hand = None
         self.captures = 0
         self._set_example_cameras()
         self._capture()
@@ -309,7 +342,7 @@ class PlannerSession:
         out = {'volume': vol, 'qual': q, 'rot': r, 'width': w, 'sel_qual': sel['qual']}
         grad = nr.sample_volume_gradient(ref, _prep=prep) if self.surface_normals else None
         for p in self.products:
-            out[p.out] = p.record(vol, grad, self._d, imgs)
+            out[p.out] = p.record(vol, grad, self._d, imgs, sel)
             if p.words:
                 o[p.at:p.at + p.words].copy_(out[p.out]['count'].reshape(-1))
         return out
@@ -368,8 +401,9 @@ class PlannerSession:
         """The stored rows of the cloud and of the mesh, sized by the counts that came with the selection: one copy of the cloud's index
         (and of its colours in value-map mode, of its gradient rows with normals), one each of the mesh's vertex, face (and gradient)
         rows, the volume's depth images when the session casts them, then one wait."""
+        n_sel = min(int(h[0]), self.selector_params['top_k'] or self.max_grasps, self.max_grasps)
         for p in self.products:
-            p.fetch(self._out[p.out], h[p.at:p.at + p.words].tolist())
+            p.fetch(self._out[p.out], h[p.at:p.at + p.words].tolist(), max(n_sel, 0))
         st.synchronize()
         for p in self.products:
             setattr(self, p.attr, p.result())
@@ -405,6 +439,13 @@ class PlannerSession:
             self._read_rows(h, st)
             dt = time.time() - t0
         grasps = grasps_from_selection(self.selection, 0, self.voxel_size, seed)
+        if self.hand_params is not None:                     # the hand's columns, through the permutation of the other columns
+            hand, n = self.hand, len(grasps['score'])
+            if seed is not None and n > 0:
+                np.random.seed(seed)
+                p = np.random.permutation(n)
+                hand = {k: v[p] for k, v in hand.items()}
+            grasps.update(hand)
         if return_volumes:
             grasps['volumes'] = tuple(self._out[k].cpu().numpy() for k in ('volume', 'qual', 'rot', 'width', 'sel_qual'))
         return grasps, dt

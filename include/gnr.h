@@ -799,6 +799,56 @@ int gnr_surface_color_pixels_fwd(const GnrSurfaceColorParams* params, const floa
                                  const float* images /*[B,V,3,H,W]*/, const float* poses /*[B,V,3,4]*/, const float* Ks /*[B,V,3,3]*/,
                                  float* colors /*[B,Vc,hc,wc,3]*/, float* weight /*[B,Vc,hc,wc]*/, int* views /*[B,Vc,hc,wc]*/, void* stream);
 
+/* gnr_hand_clearance_fwd: the clearance of a parallel-jaw hand at the ranked grasps of B volumes [B,R,R,R] -- per grasp the smallest
+ * value of the volume over a lattice of samples of the hand's four boxes, once with the hand at the grasp and once over everything the
+ * boxes pass through while the hand comes in from `approach` metres back along its own z (execute_grasp's pre-grasp pose,
+ * gd/simulation.py:369-402, answered from the volume instead of physics).  No reference counterpart; tests/hand_reference.py is the same
+ * statement in numpy and the call produces its bits.  vol, quat and width convert to float64 before the first operation; everything
+ * below is float64, single correctly rounded operations in the order written.
+ *   frame      the grasp frame of gd/vis.py's draw_grasp: z the approach (the fingers point along +z), y the closing direction, x the
+ *              hand's thickness.  pos [B,max_n,3] float64 is in lattice units: voxel (i,j,k)'s value sits at position (i,j,k) (a
+ *              selection's `index`, the cloud's points / scale).  Hand-local metres go to lattice units by division by `scale`.
+ *   width      wv = opening / scale when opening >= 0 (one opening for every grasp), else (double)width[b,r] (voxels, a selection's);
+ *              wv = fmin(fmax(wv, 0), (double)R) (fmax drops a NaN);  w = wv * scale;  hw = 0.5 * w.
+ *   boxes      with h = height, f = finger_width, t = tail_length, d = depth, as (lo, extent) per axis, in this order:
+ *                left finger   x (-0.5 h, h)   y (-hw - f, f)    z (-f, d + f)
+ *                right finger  x (-0.5 h, h)   y (hw, f)         z (-f, d + f)
+ *                palm          x (-0.5 h, h)   y (-hw, w)        z (-f, f)
+ *                tail          x (-0.5 h, h)   y (-0.5 f, f)     z (-t - f, t)
+ *              (draw_utils.draw_gripper_o3d's boxes under visualize_grasping_3d's y_ccw_90: its X is this z, its Z this -x).
+ *   samples    cell = spacing * scale.  Per box and axis a with extent e:  n_a = fmax(2, ceil(e / cell) + 1), step_a = e / (n_a - 1),
+ *              coordinates lo_a + (double)i * step_a, i = 0 .. n_a-1.  Along z the lattice continues backwards: i = -m .. -1 with
+ *              m = ceil(approach / step_z) (approach == 0: m = 0).  Samples with i_z >= 0 are the hand AT THE GRASP, all samples the hand
+ *              ON ITS APPROACH.  The ordinal of a sample counts all samples: box, then i_x, then i_y, then i_z ascending from -m.
+ *   pose       q = (double)quat[b,r] (x, y, z, w);  n = fmax(sqrt(((x x + y y) + z z) + w w), 1e-12);  each component / n;  the matrix
+ *              M = [[1 - 2 (y y + z z), 2 (x y - z w), 2 (x z + y w)], [2 (x y + z w), 1 - 2 (x x + z z), 2 (y z - x w)],
+ *                   [2 (x z - y w), 2 (y z + x w), 1 - 2 (x x + y y)]]  (scipy's as_matrix; every product and sum as bracketed).
+ *   position   of the local sample l:  p_a = pos_a + ((M[a][0] l_x + M[a][1] l_y) + M[a][2] l_z) / scale.  A sample with a component
+ *              outside [0, R-1] (or not a number) is skipped: nothing is known there.  The others take the trilinear value T of
+ *              gnr_volume_raycast_fwd (base clamp(floor(.), 0, R-2); z, then y, then x).
+ *   result     per set (at the grasp: column 0; on the approach: column 1):  inside = the number of samples taken;  worst = the
+ *              ordinal of the first sample in ordinal order whose T is the smallest (np.argmin: -0.0 and 0.0 tie), -1 when inside
+ *              is 0;  clearance = (float)fmin(T at worst, free) with free = 1.0, the volume's upper clip; 1.0 when inside is 0.
+ *   rows       r < min(count[b * count_stride], top_k > 0 ? top_k : max_n, max_n); the other rows are left untouched.
+ * 1 <= B <= 65535, 2 <= R <= 256, max_n >= 1, count_stride >= 1, top_k >= 0; height, finger_width, tail_length, depth, spacing and
+ * scale finite and > 0; approach finite and >= 0; opening finite. The number of samples of a grasp whose width is R voxels
+ * (the most any row can have) must be at most GNR_HAND_MAX_SAMPLES.  Every loop is bounded by the parameters: no content of pos, quat,
+ * width or count ends one later or moves an access out of the volume.  Results on a volume that holds a NaN are undefined.
+ * Asynchronous on `stream`, no atomics, no workspace, no allocation, no synchronisation (it can be captured in a graph); a refused
+ * call has launched nothing.                                                                                                  */
+#define GNR_HAND_MAX_SAMPLES 4194304
+typedef struct GnrHandParams {
+    double height, finger_width, tail_length, depth;   /* metres: 0.004, 0.004, 0.04, 0.05 (the viewer's hand) */
+    double opening;                                    /* metres; < 0: each grasp's own width                  */
+    double spacing;                                    /* voxels between samples at most: 0.5                  */
+    double approach;                                   /* metres: 0.05; 0: no sweep                            */
+    double scale;                                      /* metres per voxel                                     */
+} GnrHandParams;
+int gnr_hand_clearance_fwd(const GnrHandParams* params, const float* vol /*[B,R,R,R]*/, const double* pos /*[B,max_n,3]*/,
+                           const float* quat /*[B,max_n,4]*/, const float* width /*[B,max_n], voxels*/, const int* count /*[B * count_stride]*/,
+                           int count_stride, int B, int R, int max_n, int top_k, float* clearance /*[B,max_n,2]*/, int* worst /*[B,max_n,2]*/,
+                           int* inside /*[B,max_n,2]*/, void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
