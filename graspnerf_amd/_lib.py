@@ -292,6 +292,8 @@ def lib():
     L.gnr_surface_color_pixels_fwd.restype = C.c_int
     L.gnr_hand_clearance_fwd.argtypes = [C.POINTER(GnrHandParams)] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 4
     L.gnr_hand_clearance_fwd.restype = C.c_int
+    L.gnr_finger_closure_fwd.argtypes = [C.POINTER(GnrHandParams), C.c_double, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 5
+    L.gnr_finger_closure_fwd.restype = C.c_int
     L.gnr_tsdf_reset.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnr_tsdf_reset.restype = C.c_int
     L.gnr_tsdf_integrate.argtypes = [C.POINTER(GnrTsdfParams)] + [C.c_void_p] * 7
@@ -356,7 +358,7 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_grasp_select_v2_workspace_bytes', 'gnr_grasp_select_v2_fwd', 'gnr_surface_points_workspace_bytes', 'gnr_surface_points_fwd',
             'gnr_sample_volume_grad_workspace_bytes', 'gnr_sample_volume_grad_fwd', 'gnr_surface_gradient_fwd',
             'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid', 'gnr_surface_mesh_workspace_bytes', 'gnr_surface_mesh_fwd',
-            'gnr_volume_raycast_fwd', 'gnr_surface_color_points_fwd', 'gnr_surface_color_pixels_fwd', 'gnr_hand_clearance_fwd',
+            'gnr_volume_raycast_fwd', 'gnr_surface_color_points_fwd', 'gnr_surface_color_pixels_fwd', 'gnr_hand_clearance_fwd', 'gnr_finger_closure_fwd',
             'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 

@@ -370,11 +370,12 @@ def _box_faces():
 BOX_FACES = _box_faces()
 
 
-def hand_mesh(grasps, scores=None, opening=None, **hand):
+def hand_mesh(grasps, scores=None, opening=None, travel=None, **hand):
     """The gripper mesh of visualize_grasping_3d / draw_gripper_o3d (database.py:260-276, draw_utils.py:408-480) for a list of grasps, on
     the host: grasps = a plan's dict (`pos` [n,3] metres in the cloud's frame, `quat` [n,4] (x, y, z, w), `width` [n] metres);  scores
     [n]: the colour, (score, 0, 1 - score) per vertex as in draw_gripper_o3d (None: the grasps' own `score`);  opening: one opening in
-    metres for every hand (None: each grasp's width);  hand: HAND_GEOMETRY's keys.
+    metres for every hand (None: each grasp's width);  travel [n,2]: metres each finger has moved towards the centre plane -- a plan's
+    `finger_travel` (plan_real(closure=True)) draws the fingers where they stopped (None: the open hand);  hand: HAND_GEOMETRY's keys.
     -> {'vertices': [32 n,3] float64, 'faces': [48 n,3] int64, 'colors': [32 n,3] float64}: per grasp the 8 corners of the left finger,
     the right finger, the palm and the tail (hand_boxes; corner 4 i + 2 j + k of a box at (x_i, y_j, z_k)), 12 outward triangles each.
     write_ply(path, m['vertices'], m['colors'], faces=m['faces']) writes it."""
@@ -389,12 +390,18 @@ def hand_mesh(grasps, scores=None, opening=None, **hand):
     scores = np.asarray(grasps['score'] if scores is None else scores, np.float64).reshape(-1)
     if len(scores) != n:
         raise ValueError(f'{n} grasps but {len(scores)} scores')
+    if travel is not None:
+        travel = np.asarray(travel, np.float64)
+        if travel.shape != (n, 2):
+            raise ValueError(f'travel must be [{n},2], got {travel.shape}')
     corner = np.array([[i, j, k] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
     vertices, faces = np.zeros((n, 32, 3)), np.zeros((n, 48, 3), np.int64)
     for g in range(n):
         M = rotation_matrix(quat[g] / max(np.linalg.norm(quat[g]), 1e-12))
         for b, (lo, hi) in enumerate(hand_boxes(width[g] if opening is None else opening, **geometry)):
             local = np.where(corner == 1, np.array(hi), np.array(lo))
+            if travel is not None and b < 2:                 # the left finger closes towards +y, the right one towards -y
+                local = local + [0.0, travel[g, 0] if b == 0 else -travel[g, 1], 0.0]
             vertices[g, 8 * b:8 * b + 8] = pos[g] + local @ M.T
             faces[g, 12 * b:12 * b + 12] = BOX_FACES + (32 * g + 8 * b)
     colors = np.repeat(np.stack([scores, np.zeros(n), 1.0 - scores], 1), 32, axis=0)

@@ -4,7 +4,11 @@ hand fits where the network wants to put it.  The reference answers this with ph
 in; on a real robot the only geometry the planner has is the volume it has just predicted.  Per grasp: the smallest value of the
 volume over samples of the hand's four boxes (grasp_post.HAND_GEOMETRY, draw_gripper_o3d's) at the grasp, and over everything they
 pass through on the approach.  include/gnr.h states the arithmetic; the results are the bits of the float64 statement
-tests/hand_reference.py.  No reference counterpart."""
+tests/hand_reference.py.  No reference counterpart.
+FingerClosure (gnr_finger_closure_fwd, the same file's second kernel) is the step after it: execute_grasp closes the fingers and
+check_success (gd/simulation.py:404,465-469) asks whether they hold something.  Per grasp: where pad rays on each finger's inner face
+first meet the surface on their way to the centre plane, the width of the closed hand, and the cosine between the surface and the
+closing direction at the two contacts; the bits of tests/closure_reference.py."""
 import ctypes as C
 import math
 
@@ -17,6 +21,10 @@ from .grasp_post import HAND_GEOMETRY, DeviceOp, checked_params, volume_batch
 HAND_DEFAULTS = dict(HAND_GEOMETRY, opening=None, spacing=0.5, approach=0.05)
 PLAN_DEFAULTS = dict(level=0.0)                              # what a plan adds: collision_free = approach_clearance > level
 EXECUTE_GRASP_OPENING = 0.08                                 # execute_grasp opens the hand to max_opening_width (simulation.py:372)
+CLOSURE_ROWS = ('travel', 'cosine', 'contact', 'closed')
+CLOSURE_DEFAULTS = dict(HAND_DEFAULTS, level=0.0, bisections=4)                # FingerClosure.__call__'s keywords
+CLOSURE_PLAN_DEFAULTS = dict(max_opening=0.08, friction=None)                  # what a plan adds: closure_from_rows's keywords
+CHECK_SUCCESS_FRACTION = 0.1                                                   # check_success: width > 0.1 * max_opening_width (simulation.py:468)
 
 
 def hand_params(clearance, **more):
@@ -65,6 +73,27 @@ def selection_pos(sel):
     return sel['index'].double()
 
 
+def checked_rows(pos, quat, width, count, top_k, B, d):
+    """The rows of grasps of B scenes on device d, as the kernels read them -> (pos [B,n,3] float64, quat [B,n,4] float32, width [B,n]
+    float32, n); count and top_k are checked."""
+    pos = torch.as_tensor(pos, dtype=torch.float64, device=d).contiguous()
+    quat = torch.as_tensor(quat, dtype=torch.float32, device=d).contiguous()
+    width = torch.as_tensor(width, dtype=torch.float32, device=d).contiguous()
+    if pos.dim() == 2:
+        pos, quat, width = pos[None], quat[None], width[None]
+    if pos.dim() != 3 or pos.shape[0] != B or pos.shape[2] != 3:
+        raise ValueError(f'pos must be [{B},max_n,3], got {tuple(pos.shape)}')
+    n = pos.shape[1]
+    if tuple(quat.shape) != (B, n, 4) or tuple(width.shape) != (B, n):
+        raise ValueError(f'quat must be [{B},{n},4] and width [{B},{n}], got {tuple(quat.shape)} and {tuple(width.shape)}')
+    if not torch.is_tensor(count) or count.dtype != torch.int32 or count.device != pos.device or count.shape[0] != B or \
+            not count.is_contiguous():
+        raise ValueError(f'count must be a contiguous int32 device tensor [{B}] or [{B},k]')
+    if top_k is not None and int(top_k) < 1:
+        raise ValueError(f'top_k must be None or positive, got {top_k!r}')
+    return pos, quat, width, n
+
+
 class HandClearance(DeviceOp):
     """The clearance of the hand at rows of grasps of B volumes.  The output buffers are kept per shape and written again by the next
     call of that shape, so their addresses are stable for a captured graph."""
@@ -89,21 +118,7 @@ class HandClearance(DeviceOp):
         d = self.device
         hand = checked_hand(height, finger_width, tail_length, depth, opening, spacing, approach)
         vol, B, R = volume_batch(vol, d)
-        pos = torch.as_tensor(pos, dtype=torch.float64, device=d).contiguous()
-        quat = torch.as_tensor(quat, dtype=torch.float32, device=d).contiguous()
-        width = torch.as_tensor(width, dtype=torch.float32, device=d).contiguous()
-        if pos.dim() == 2:
-            pos, quat, width = pos[None], quat[None], width[None]
-        if pos.dim() != 3 or pos.shape[0] != B or pos.shape[2] != 3:
-            raise ValueError(f'pos must be [{B},max_n,3], got {tuple(pos.shape)}')
-        n = pos.shape[1]
-        if tuple(quat.shape) != (B, n, 4) or tuple(width.shape) != (B, n):
-            raise ValueError(f'quat must be [{B},{n},4] and width [{B},{n}], got {tuple(quat.shape)} and {tuple(width.shape)}')
-        if not torch.is_tensor(count) or count.dtype != torch.int32 or count.device != pos.device or count.shape[0] != B or \
-                not count.is_contiguous():
-            raise ValueError(f'count must be a contiguous int32 device tensor [{B}] or [{B},k]')
-        if top_k is not None and int(top_k) < 1:
-            raise ValueError(f'top_k must be None or positive, got {top_k!r}')
+        pos, quat, width, n = checked_rows(pos, quat, width, count, top_k, B, d)
         out = self._out.get((B, n))
         if out is None:
             out = self._out[(B, n)] = (torch.zeros(B, n, 2, dtype=torch.float32, device=d), torch.zeros(B, n, 2, dtype=torch.int32, device=d),
@@ -118,6 +133,124 @@ class HandClearance(DeviceOp):
     def of_selection(self, vol, sel, *, scale, **hand):
         """... of the rows of a GraspSelector result (any route's: plan, plan_real, plan_depth), with its top_k."""
         return self(vol, selection_pos(sel), sel['quat'], sel['width'], sel['count'], scale=scale, top_k=sel.get('top_k'), **hand)
+
+
+class FingerClosure(DeviceOp):
+    """Where the two fingers stop when the hand closes on the volume, at rows of grasps of B volumes (csrc/gnr_hand.hip,
+    gnr_finger_closure_fwd): the third step of execute_grasp -- `gripper.move(0.0)` and check_success (gd/simulation.py:404,465-469) --
+    answered from the volume.  include/gnr.h states the arithmetic; the results are the bits of tests/closure_reference.py.  The output
+    buffers are kept per shape, as HandClearance's."""
+
+    def __init__(self, device='cuda:0'):
+        super().__init__(device, 'finger closure')
+        self._out = {}
+
+    def __call__(self, vol, pos, quat, width, count, *, scale, top_k=None, level=0.0, bisections=4, height=0.004, finger_width=0.004,
+                 tail_length=0.04, depth=0.05, opening=None, spacing=0.5, approach=0.05):
+        """vol, pos, quat, width, count, scale, top_k and the hand's keywords: HandClearance.__call__'s (tail_length and approach are checked
+        and not used);  level: the value of the volume at the surface (0 for the network's tsdf; 0.5 for the depth route's fused volume,
+        tsdf.py);  bisections: halvings of a ray's bracket before its secant step, 0..16.
+        Each finger's inner face carries pad rays at most `spacing` voxels apart; finger 0 closes from y = -opening / 2 towards +y,
+        finger 1 from +opening / 2 towards -y, both to the centre plane at the latest, and stops where its first ray meets a value below
+        the level.
+        -> {'travel': [B,max_n,2] float32 (metres each finger moved; opening / 2: it met nothing), 'cosine': [B,max_n,2] float32 (between
+        the surface's normal at the contact and the closing direction; 1: squarely, 0: no contact), 'contact': [B,max_n,2] int32 (the
+        ordinal of the ray that stopped the finger, -1: none), 'closed': [B,max_n] float32 (the width of the closed hand in metres)};
+        rows beyond min(count, top_k, max_n) keep what they held.  The tensors are this object's."""
+        d = self.device
+        hand = checked_hand(height, finger_width, tail_length, depth, opening, spacing, approach)
+        level, bisections = checked_closure(level, bisections)
+        vol, B, R = volume_batch(vol, d)
+        pos, quat, width, n = checked_rows(pos, quat, width, count, top_k, B, d)
+        out = self._out.get((B, n))
+        if out is None:
+            out = self._out[(B, n)] = (torch.zeros(B, n, 2, dtype=torch.float32, device=d), torch.zeros(B, n, 2, dtype=torch.float32, device=d),
+                                       torch.zeros(B, n, 2, dtype=torch.int32, device=d), torch.zeros(B, n, dtype=torch.float32, device=d))
+        p = _lib.GnrHandParams(scale=float(scale), **hand)
+        rc = self.L.gnr_finger_closure_fwd(C.byref(p), level, bisections, vol.data_ptr(), pos.data_ptr(), quat.data_ptr(), width.data_ptr(),
+                                           count.data_ptr(), count.numel() // B, B, R, n, int(top_k or 0), *(t.data_ptr() for t in out),
+                                           self._stream())
+        _lib.check(rc, 'gnr_finger_closure_fwd')
+        return dict(zip(CLOSURE_ROWS, out))
+
+    def of_selection(self, vol, sel, *, scale, **kw):
+        """... of the rows of a GraspSelector result (any route's: plan, plan_real, plan_depth), with its top_k.  The depth route has
+        no switch for it and calls this by hand with level=0.5 on (tsdf + 1) / 2 where weight > 0 and 1 elsewhere (get_grid() itself is 0
+        in unseen and far free space, which would read as solid)."""
+        return self(vol, selection_pos(sel), sel['quat'], sel['width'], sel['count'], scale=scale, top_k=sel.get('top_k'), **kw)
+
+
+def checked_closure(level=0.0, bisections=4):
+    """The closure's own parameters, checked before anything touches the device (the library refuses the same)."""
+    if not math.isfinite(level):
+        raise ValueError(f'closure level must be finite, got {level!r}')
+    if int(bisections) != bisections or not 0 <= bisections <= 16:
+        raise ValueError(f'closure bisections must be an integer in 0..16, got {bisections!r}')
+    return float(level), int(bisections)
+
+
+def closure_params(closure, **more):
+    """A plan's `closure` / a session's `finger_closure` argument -> None, or the closure's parameters (True / {}: the viewer's hand
+    opened to each grasp's own predicted width, pad rays half a voxel apart, the surface at 0, held = both fingers touch and the closed
+    hand is wider than 0.1 * 0.08 m, no friction coefficient).  more: further keys the caller takes, with their defaults (plan_real's
+    `filter`)."""
+    out = checked_params('closure', closure, {**CLOSURE_DEFAULTS, **CLOSURE_PLAN_DEFAULTS, **more})
+    if out is None:
+        return None
+    for k in ('height', 'finger_width', 'tail_length', 'depth', 'spacing', 'approach', 'max_opening'):
+        out[k] = float(out[k])
+    for k in ('opening', 'friction'):
+        out[k] = None if out[k] is None else float(out[k])
+    checked_hand(**{k: out[k] for k in HAND_DEFAULTS})
+    out['level'], out['bisections'] = checked_closure(out['level'], out['bisections'])
+    checked_held(out['max_opening'], out['friction'])
+    return out
+
+
+def checked_held(max_opening=0.08, friction=None):
+    if not (math.isfinite(max_opening) and max_opening > 0):
+        raise ValueError(f'closure max_opening must be finite and > 0 metres, got {max_opening!r}')
+    if friction is not None and not (math.isfinite(friction) and friction >= 0):
+        raise ValueError(f'closure friction must be None or finite and >= 0, got {friction!r}')
+
+
+def same_closure_params(a, b):
+    """Whether two closure_params results ask for the same product (either may hold further keys, plan_real's `filter`)."""
+    if a is None or b is None:
+        return a is None and b is None
+    return all(a[k] == b.get(k) for k in (*CLOSURE_DEFAULTS, *CLOSURE_PLAN_DEFAULTS))
+
+
+def closure_device_params(cp):
+    """closure_params -> the keyword arguments of FingerClosure.__call__ it sets."""
+    return {k: cp[k] for k in CLOSURE_DEFAULTS}
+
+
+def closure_host_params(cp):
+    """closure_params -> the keyword arguments of closure_from_rows it sets."""
+    return {k: cp[k] for k in CLOSURE_PLAN_DEFAULTS}
+
+
+def closure_rows(res, b, n):
+    """The device rows of scene b of a FingerClosure result, given the number of grasps n the selection stored."""
+    return {k: res[k][b, :n] for k in CLOSURE_ROWS}
+
+
+def closure_from_rows(rows, max_opening=0.08, friction=None):
+    """closure_rows on the host (numpy) -> the columns a plan adds to its grasps: `closed_width` [n] float32 (metres: what a robot
+    compares with its gripper's read-back), `finger_travel` [n,2] and `contact_cos` [n,2] float32, `finger_contact` [n,2] int32,
+    `grip_cos` [n] float32 (the smaller of the two cosines), `held` [n] bool = both fingers have a contact and closed_width >
+    0.1 * max_opening (check_success, gd/simulation.py:465-469,478);  with friction=mu also `force_closure` [n] bool = grip_cos >=
+    1 / sqrt(1 + mu^2): both contact normals lie within the friction cone about the closing direction (no default: the reference
+    sets none)."""
+    checked_held(max_opening, friction)
+    cos, contact, closed = np.asarray(rows['cosine']), np.asarray(rows['contact']), np.asarray(rows['closed'])
+    out = {'closed_width': closed.copy(), 'finger_travel': np.array(rows['travel']), 'contact_cos': cos.copy(), 'finger_contact': contact.copy(),
+           'grip_cos': cos.min(axis=1) if len(cos) else np.zeros(0, np.float32)}
+    out['held'] = (contact >= 0).all(axis=1) & (closed > np.float32(CHECK_SUCCESS_FRACTION * max_opening))
+    if friction is not None:
+        out['force_closure'] = out['grip_cos'] >= np.float32(1.0 / math.sqrt(1.0 + friction * friction))
+    return out
 
 
 def hand_rows(res, b, n):

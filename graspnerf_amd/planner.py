@@ -14,8 +14,9 @@ import torch
 from .renderer import GraspNeRF
 from .grasp_post import GRASP_UTILS_PROCESS, MESH_DEFAULTS, GraspSelector, MeshExtractor, SurfaceExtractor, checked_params, \
     grasps_from_selection, mesh_from_extraction, surface_from_extraction
-from .hand import HandClearance, device_params as _hand_device_params, hand_from_rows, hand_params as _hand_params, hand_rows, \
-    same_hand_params as _same_hand_params
+from .hand import FingerClosure, HandClearance, closure_device_params, closure_from_rows, closure_host_params, \
+    closure_params as _closure_params, closure_rows, device_params as _hand_device_params, hand_from_rows, hand_params as _hand_params, \
+    hand_rows, same_closure_params as _same_closure_params, same_hand_params as _same_hand_params
 from .ingest import axis_tables
 from .planner_session import PLAN_BBOX3D, PlannerSession, deterministic_convolutions
 from .raycast import VolumeRaycaster, depth_params as _depth_params, images_from_raycast, same_depth_params as _same_depth_params, volume_origin
@@ -126,13 +127,16 @@ def real_volume_origin():
 
 
 def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, mesh=False,
-                 volume_depth=False, view_colors=False, clearance=False, **kw):
+                 volume_depth=False, view_colors=False, clearance=False, closure=False, **kw):
     """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud
     (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True);  mesh: plan_real's, with the
     triangle mesh of the volume's iso-surface in the graph;  volume_depth: plan_real's, with the ray cast of the volume in the graph;
     view_colors: plan_real's, with the colouring of each of these from the plan's frames in the graph;  clearance: plan_real's, with
-    the gripper clearance of the stored grasps in the graph)."""
+    the gripper clearance of the stored grasps in the graph;  closure: plan_real's, with their finger closure in the graph)."""
     vd, mp, cp, hp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors), _hand_params(clearance, filter=False)
+    fp = _closure_params(closure, filter=False)
+    if fp is not None:
+        kw = dict(kw, finger_closure={k: v for k, v in fp.items() if k != 'filter'})
     if hp is not None:
         kw = dict(kw, hand_clearance={k: v for k, v in hp.items() if k != 'filter'})
     if cp is not None:
@@ -149,7 +153,7 @@ def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, sur
 
 
 def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None,
-              normals=False, mesh=False, volume_depth=False, view_colors=False, clearance=False):
+              normals=False, mesh=False, volume_depth=False, view_colors=False, clearance=False, closure=False):
     """`run_real` (grasp_utils.py:119-151) without its file output: one plan from camera frames.
     images: V >= 4 uint8 frames [h,w,3] (list or array); extrinsics: V world->camera [3|4,4]; intrinsic [3,3], the same for every view.
     run_real's workspace box, depth range (0.2, 0.8) and query view 3; grasp_utils.process's thresholds (GRASP_UTILS_PROCESS),
@@ -192,10 +196,26 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     (None: each grasp's own width; hand.EXECUTE_GRASP_OPENING is execute_grasp's 0.08), the samples' spacing in voxels, the approach in
     metres, the level (0) -- and filter=True keeps only the collision_free rows of every column, in their order.  A session must have
     been built with the same real_session(clearance=...) (`filter` aside).  No other key depends on it; grasp_post.hand_mesh draws the
-    same boxes."""
+    same boxes.
+    closure=True: what happens when the hand then closes, answered from the volume (hand.FingerClosure; execute_grasp closes the fingers
+    and check_success asks whether they touch something and the hand stays wider than a tenth of its opening, gd/simulation.py:404,
+    465-469).  The grasps dict gains `closed_width` [n] float32 -- the width in metres at which the fingers stop on the surface tsdf =
+    level, the number a robot compares with its gripper's read-back; 0: nothing between the fingers -- `finger_travel` [n,2] float32
+    (metres each finger moved), `finger_contact` [n,2] int32 (the pad ray that stopped it, -1: none), `contact_cos` [n,2] and `grip_cos`
+    [n] float32 (the cosine between the surface normal at each contact and the closing direction, and the smaller of the two; 1: the
+    surfaces face each other squarely) and `held` [n] bool = both fingers touch and closed_width > 0.1 * max_opening.
+    closure=dict(level=..., bisections=..., max_opening=..., friction=..., filter=..., and clearance's hand keys): the surface level
+    (0), the refinement of a contact (4 halvings), check_success's opening (0.08), a friction coefficient mu -- the dict then gains
+    `force_closure` [n] bool = grip_cos >= 1 / sqrt(1 + mu^2); no default, the reference sets none -- and filter=True keeps only the
+    `held` rows (with clearance=dict(filter=True) too, the rows that pass both).  A session must have been built with the same
+    real_session(closure=...) (`filter` aside).  No other key depends on it.  The depth route (plan_depth) has no such switch: on its selection
+    call hand.FingerClosure(dev).of_selection(vol, sel, scale=size / resolution, level=0.5) by hand, with a volume on the grid's scale
+    (tsdf + 1) / 2, whose surface is at 0.5 -- but not get_grid() itself, which is 0 in unseen and far free space and would read as
+    solid there: take (tsdf + 1) / 2 where weight > 0 and 1 elsewhere, as tsdf.render_depth does for its ray cast."""
     if order not in ('permuted', 'score'):
         raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
     vd, mp, cp, hp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors), _hand_params(clearance, filter=False)
+    fp = _closure_params(closure, filter=False)
     ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
     V = ext.shape[0]
     if V <= REAL_QUE_ID:
@@ -217,6 +237,9 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
         if not _same_hand_params(hp, getattr(session, 'hand_params', None)):
             raise ValueError('plan_real(session=...): the session was built for another clearance (build it with '
                              'planner.real_session(clearance=...))')
+        if not _same_closure_params(fp, getattr(session, 'closure_params', None)):
+            raise ValueError('plan_real(session=...): the session was built for another closure (build it with '
+                             'planner.real_session(closure=...))')
         g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
         tsdf_vol, cloud = g.pop('volumes')[0], session.cloud
         if session.mesh_params is not None:
@@ -244,6 +267,10 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
             res = HandClearance(dev).of_selection(kept['vol'], kept['sel'], scale=REAL_VOXEL_SIZE, **_hand_device_params(hp))
             rows = hand_rows(res, 0, len(g['score']))
             g.update(hand_from_rows({k: v.cpu().numpy() for k, v in rows.items()}, hp['level']))
+        if fp is not None:
+            res = FingerClosure(dev).of_selection(kept['vol'], kept['sel'], scale=REAL_VOXEL_SIZE, **closure_device_params(fp))
+            rows = closure_rows(res, 0, len(g['score']))
+            g.update(closure_from_rows({k: v.cpu().numpy() for k, v in rows.items()}, **closure_host_params(fp)))
         grad = None
         if normals:                                               # the volume's cameras again: the forward keeps no feature maps
             grad = _volume_gradient(net, imgs, ext, Ks, dev)
@@ -278,8 +305,9 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
             np.random.seed(seed)
         p = np.random.permutation(n)
         g = {k: v[p] for k, v in g.items()}
-    if hp is not None and hp['filter']:
-        g = {k: v[g['collision_free']] for k, v in g.items()}
+    keep = [g[k] for k, on in (('collision_free', hp), ('held', fp)) if on is not None and on['filter']]
+    if keep:
+        g = {k: v[np.logical_and.reduce(keep)] for k, v in g.items()}
     return g, g['score'], tsdf_vol, cloud, dt
 
 

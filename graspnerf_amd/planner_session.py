@@ -15,7 +15,8 @@ import torch
 from . import _lib
 from .grasp_post import MESH_DEFAULTS, SELECTOR_DEFAULTS, SURFACE_DEFAULTS, VIEW_KEYS, GraspSelector, MeshExtractor, SurfaceExtractor, \
     checked_params, grasps_from_selection, mesh_bounds, mesh_from_rows, mesh_rows, surface_from_rows, surface_rows
-from .hand import HandClearance, device_params, hand_from_rows, hand_params, hand_rows
+from .hand import FingerClosure, HandClearance, closure_device_params, closure_from_rows, closure_host_params, closure_params, closure_rows, \
+    device_params, hand_from_rows, hand_params, hand_rows
 from .ingest import DeviceIngest
 from .raycast import COLOR_KEYS, VolumeRaycaster, depth_params, images_from_rows, raycast_rows, volume_origin
 from .surface_color import SurfaceColorizer, cloud_level, color_params, march_params
@@ -42,8 +43,8 @@ def deterministic_convolutions(on=True):
 # volume, its gradient, the cameras, the ingested frames and the selection), and (4) fetch() / result(): the sized copies of one plan's
 # rows (by its own count words, or by the number of stored grasps) and, after the session's one wait, the numpy dict -- through the same
 # *_rows / *_from_rows pair as the eager route (grasp_post.py, raycast.py).  PlannerSession builds the list `products` from its keywords
-# and names no product anywhere else (but for plan(), which merges the hand's columns into the grasps it returns); a new one is a class
-# here, a keyword and one line in that list.
+# and names no product anywhere else (plan() merges the result of every product with `columns` into the grasps it returns); a new one
+# is a class here, a keyword and one line in that list.
 # The view colours (`colors`: a _Colors, or None) are no product of their own: each product colours its own rows in its record(), right
 # after the step that makes them, and reads the colours back with them.
 class _Pinned:
@@ -90,7 +91,7 @@ class _Colors:
 class _Cloud:
     """The surface cloud: one count word; the index rows (the colours in value-map mode, the gradient rows with normals) are read back,
     the float64 points stay on the device and are recomputed on the host as index * scale, a fixed colour is known on the host."""
-    out, attr, words = 'surface', 'cloud', 1
+    out, attr, words, columns = 'surface', 'cloud', 1, False
 
     def __init__(self, params, R, normals, dev, colors=None):
         self.params, self.extract, self.colors = params, SurfaceExtractor(dev), colors
@@ -122,7 +123,7 @@ class _Cloud:
 class _Mesh:
     """The triangle mesh of the iso-surface, in the cloud's frame (origin 0, the cloud's scale): two count words, vertices and
     triangles; the stored vertex, face (and gradient) rows are read back."""
-    out, attr, words = 'mesh', 'mesh', 2
+    out, attr, words, columns = 'mesh', 'mesh', 2, False
 
     def __init__(self, params, R, normals, dev, scale, colors=None):
         self.params, self.scale, self.extract, self.colors = params, scale, MeshExtractor(dev), colors
@@ -146,7 +147,7 @@ class _Mesh:
 class _DepthImages:
     """The ray cast of the volume: no count word, the whole images are read back.  Without cameras of its own it reads the plan's from
     the session's device block, which every plan uploads anyway; other cameras are the session's, uploaded once."""
-    out, attr, words = 'volume_depth', 'volume_images', 0
+    out, attr, words, columns = 'volume_depth', 'volume_images', 0, False
 
     def __init__(self, params, n_views, hw, voxel_size, normals, dev, colors=None):
         self.params, self.scale, self.cast, self.colors = params, voxel_size, VolumeRaycaster(dev), colors
@@ -181,7 +182,7 @@ class _DepthImages:
 class _Hand:
     """The gripper clearance of the selected grasps (hand.HandClearance): no count word -- its rows are the selection's, read back sized
     by the selection's count.  It reads the selection, so it is recorded right after it."""
-    out, attr, words = 'hand', 'hand', 0
+    out, attr, words, columns = 'hand', 'hand', 0, True      # columns: one row per stored grasp, merged into plan()'s grasps
 
     def __init__(self, params, max_grasps, voxel_size, dev):
         self.params, self.scale, self.op = params, voxel_size, HandClearance(dev)
@@ -196,6 +197,26 @@ class _Hand:
 
     def result(self):
         return hand_from_rows(self.pinned.host(), self.params['level'])
+
+
+class _Closure:
+    """The finger closure of the selected grasps (hand.FingerClosure): like _Hand, no count word, rows sized by the selection's count,
+    recorded right after the selection."""
+    out, attr, words, columns = 'closure', 'closure', 0, True
+
+    def __init__(self, params, max_grasps, voxel_size, dev):
+        self.params, self.scale, self.op = params, voxel_size, FingerClosure(dev)
+        self.pinned = _Pinned(travel=((max_grasps, 2), torch.float32), cosine=((max_grasps, 2), torch.float32),
+                              contact=((max_grasps, 2), torch.int32), closed=((max_grasps,), torch.float32))
+
+    def record(self, vol, grad, cams, images, sel):
+        return self.op.of_selection(vol, sel, scale=self.scale, **closure_device_params(self.params))
+
+    def fetch(self, res, counts, n_sel):
+        self.pinned.fetch(closure_rows(res, 0, n_sel))
+
+    def result(self):
+        return closure_from_rows(self.pinned.host(), **closure_host_params(self.params))
 
 
 class PlannerSession:
@@ -242,11 +263,16 @@ class PlannerSession:
     plan()'s grasps gain `clearance` and `approach_clearance` [n] float32 (the smallest value of the volume under the hand at the grasp
     and on its approach), `hand_inside` and `hand_worst` [n,2] int32 and `collision_free` [n] bool = approach_clearance > level, through
     the same permutation as the other columns; self.hand holds them in the selection's order.
+    finger_closure = dict(level=..., bisections=..., max_opening=..., friction=..., and hand_clearance's hand keys) ({} for the defaults):
+    where the fingers stop when the hand closes on the volume (hand.FingerClosure) is recorded right after the selection (and the
+    clearance).  plan()'s grasps gain `closed_width` [n], `finger_travel` and `contact_cos` [n,2] float32, `finger_contact` [n,2] int32,
+    `grip_cos` [n] float32 and `held` [n] bool (hand.closure_from_rows; with a friction coefficient also `force_closure`), through the
+    same permutation; self.closure holds them in the selection's order.
     A session built without any of these records the graph it always recorded."""
 
     def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
                  surface=None, surface_normals=False, surface_mesh=None, volume_depth=None, view_colors=None, hand_clearance=None,
-                 **selector_params):
+                 finger_closure=None, **selector_params):
         cfg = net.nr_net.cfg
         if surface_normals and surface is None:
             raise ValueError('surface_normals=True needs the surface cloud: pass surface=dict(...) ({} for its defaults)')
@@ -260,6 +286,7 @@ class PlannerSession:
         self.volume_depth_params = depth_params(volume_depth, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
         self.view_color_params = color_params(view_colors, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
         self.hand_params = hand_params(hand_clearance)
+        self.closure_params = closure_params(finger_closure)
         if self.view_color_params is not None and self.surface_params is None and self.mesh_params is None and self.volume_depth_params is None:
             raise ValueError('view_colors needs a product to colour: pass surface=, surface_mesh= or volume_depth=')
         dev = next(net.parameters()).device
@@ -297,6 +324,8 @@ class PlannerSession:
         colors = (lambda: None) if self.view_color_params is None else (lambda: _Colors(self.view_color_params, self.voxel_size, dev))
         if self.hand_params is not None:                     # first: it reads the selection, nothing of the other products
             self.products.append(_Hand(self.hand_params, M, self.voxel_size, dev))
+        if self.closure_params is not None:                  # likewise
+            self.products.append(_Closure(self.closure_params, M, self.voxel_size, dev))
         if self.surface_params is not None:
             self.products.append(_Cloud(self.surface_params, R, normals, dev, colors()))
         if self.mesh_params is not None:
@@ -308,7 +337,7 @@ class PlannerSession:
             p.at, words = words, words + p.words
         self._d_out = torch.zeros(words, dtype=torch.int32, device=dev)
         self._h_out = torch.zeros(words, dtype=torch.int32, pin_memory=True)
-        self.selection = self.cloud = self.mesh = self.volume_images = self.hand = None
+        self.selection = self.cloud = self.mesh = self.volume_images = self.hand = self.closure = None
         self.captures = 0
         self._set_example_cameras()
         self._capture()
@@ -439,13 +468,14 @@ class PlannerSession:
             self._read_rows(h, st)
             dt = time.time() - t0
         grasps = grasps_from_selection(self.selection, 0, self.voxel_size, seed)
-        if self.hand_params is not None:                     # the hand's columns, through the permutation of the other columns
-            hand, n = self.hand, len(grasps['score'])
+        columns = [getattr(self, p.attr) for p in self.products if p.columns]
+        if columns:                                          # the hand's columns, through the permutation of the other columns
+            n, p = len(grasps['score']), None
             if seed is not None and n > 0:
                 np.random.seed(seed)
                 p = np.random.permutation(n)
-                hand = {k: v[p] for k, v in hand.items()}
-            grasps.update(hand)
+            for cols in columns:
+                grasps.update(cols if p is None else {k: v[p] for k, v in cols.items()})
         if return_volumes:
             grasps['volumes'] = tuple(self._out[k].cpu().numpy() for k in ('volume', 'qual', 'rot', 'width', 'sel_qual'))
         return grasps, dt

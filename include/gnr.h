@@ -849,6 +849,39 @@ int gnr_hand_clearance_fwd(const GnrHandParams* params, const float* vol /*[B,R,
                            int count_stride, int B, int R, int max_n, int top_k, float* clearance /*[B,max_n,2]*/, int* worst /*[B,max_n,2]*/,
                            int* inside /*[B,max_n,2]*/, void* stream);
 
+/* gnr_finger_closure_fwd: where the two fingers of that hand stop when it closes on the volume, at the same rows -- the third step of
+ * execute_grasp (gd/simulation.py:404, `gripper.move(0.0)`, and check_success, :465-469) answered from the volume.  The frame, `width`,
+ * `pose`, `position`, `rows` and the trilinear value T are gnr_hand_clearance_fwd's, as are cell = spacing * scale and hw; tail_length
+ * and approach are checked and not used.  tests/closure_reference.py is the same statement in numpy and the call produces its bits.
+ *   pads       each finger's inner face carries pad rays over x in [-h/2, h/2] and z in [0, depth]:  n_x = fmax(2, ceil(height / cell) + 1),
+ *              n_z = fmax(2, ceil(depth / cell) + 1), step = extent / (n - 1), l_x = -0.5 h + (double)i_x * step_x, l_z = (double)i_z *
+ *              step_z.  The ordinal of a ray is i_x * n_z + i_z.
+ *   travel     finger 0 starts at l_y = -hw and moves towards +y, finger 1 at +hw towards -y, both to the centre plane at the latest:
+ *              n_y = fmax(1, ceil(hw / cell)), ds = hw / n_y, t_k = fmin((double)k * ds, hw) for k = 0 .. n_y;  after a travel of t:
+ *              u = hw - t, l_y = -u (finger 0) or u (finger 1).  f(t) = value - level, where value is T at the position of (l_x, l_y, l_z)
+ *              when every component of it lies in [0, R-1] and 1.0 (free) elsewhere: a finger outside the lattice touches nothing.
+ *   ray        f(t_0) < 0: the pad starts inside, t* = 0.  Else the first k >= 1 with f(t_{k-1}) >= 0 and f(t_k) < 0 gives the bracket
+ *              [A, B] = [t_{k-1}, t_k];  `bisections` times: m = 0.5 * (A + B), f(m) < 0 ? B = m : A = m (with their f's);  then
+ *              t* = A + (B - A) * (fA / (fA - fB)) (gnr_volume_raycast_fwd's refinement).  No such k: the ray has no contact.
+ *   finger     T_c = the smallest t* of its rays, contact_c = the lowest ordinal that attains it;  no ray with a contact: T_c = hw,
+ *              contact_c = -1.
+ *   cosine     at the position p of ray contact_c after a travel of T_c, with T's base corners c_xyz and t's, c00 .. c11 its z-lerped
+ *              edges and c0, c1 its y-lerped faces:  g_x = c1 - c0;  g_y = e0 + t_x * (e1 - e0) with e0 = c01 - c00, e1 = c11 - c10;
+ *              g_z = d0 + t_x * (d1 - d0) with d0 = d00 + t_y * (d01 - d00), d1 = d10 + t_y * (d11 - d10), d00 = c001 - c000 and
+ *              likewise.  a = column 1 of M;  dot = (g_x a_0 + g_y a_1) + g_z a_2;  norm = fmax(sqrt((g_x g_x + g_y g_y) + g_z g_z), 1e-12);
+ *              cos_0 = -dot / norm, cos_1 = dot / norm (1: the surface faces the finger squarely);  0 without a contact.
+ *   result     travel[b,r,c] = (float)T_c (metres), cosine[b,r,c] = (float)cos_c, contact[b,r,c], closed[b,r] = (float)((hw - T_0) +
+ *              (hw - T_1)): the width of the closed hand in metres.
+ * The limits of gnr_hand_clearance_fwd, refused with its texts; level finite; 0 <= bisections <= 16; the volume reads of a grasp whose
+ * width is R voxels, 2 n_x n_z (n_y + 1 + bisections + 2), must be at most GNR_HAND_MAX_SAMPLES.  Every loop is bounded by the
+ * parameters; results on a volume that holds a NaN are undefined.  Asynchronous on `stream`, no atomics, no workspace, no allocation,
+ * no synchronisation (it can be captured in a graph); a refused call has launched nothing.                                    */
+int gnr_finger_closure_fwd(const GnrHandParams* params, double level, int bisections, const float* vol /*[B,R,R,R]*/,
+                           const double* pos /*[B,max_n,3]*/, const float* quat /*[B,max_n,4]*/, const float* width /*[B,max_n], voxels*/,
+                           const int* count /*[B * count_stride]*/, int count_stride, int B, int R, int max_n, int top_k,
+                           float* travel /*[B,max_n,2]*/, float* cosine /*[B,max_n,2]*/, int* contact /*[B,max_n,2]*/,
+                           float* closed /*[B,max_n]*/, void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
