@@ -75,6 +75,22 @@ def checked_params(what, given, defaults):
     return {**defaults, **given}
 
 
+def same_params(asked, have):
+    """Whether a session that holds the parameters `have` serves a plan that asks for `asked` (checked_params results, or what became of
+    them): None equals only None; otherwise every key the asker set, `filter` aside (a plan's own business), has an equal value in
+    `have`, arrays and sequences compared by value.  `have` may hold further keys (a session's `origin`)."""
+    if asked is None or have is None:
+        return asked is None and have is None
+    plain = (type(None), bool, int, float, str)              # (every plan asks: numpy is for the few values that need it)
+    same = lambda x, y: x == y if isinstance(x, plain) and isinstance(y, plain) else np.array_equal(x, y)
+    return all(k in have and same(v, have[k]) for k, v in asked.items() if k != 'filter')
+
+
+def picked(params, defaults):
+    """The entries of `params` under the keys of one defaults dict: the keywords of the one call those are the defaults of."""
+    return {k: params[k] for k in defaults}
+
+
 def _call_defaults(cls, *skip):
     return {k: p.default for k, p in inspect.signature(cls.__call__).parameters.items() if p.default is not inspect.Parameter.empty and k not in skip}
 
@@ -272,6 +288,17 @@ class MeshExtractor(DeviceOp):
 
 
 MESH_DEFAULTS = dict(iso=0.0, max_vertices=None, max_faces=None)     # what a plan sets of MeshExtractor.__call__: the frame is the cloud's
+
+
+def surface_params(surface):
+    """A session's `surface` argument -> None, or the keyword arguments of SurfaceExtractor.__call__ ({}: its defaults)."""
+    return checked_params('surface', surface, SURFACE_DEFAULTS)
+
+
+def mesh_params(mesh):
+    """A plan's `mesh` / a session's `surface_mesh` argument -> None, or the mesh's parameters (True / {}: iso = 0, the exact upper
+    bounds)."""
+    return checked_params('mesh', mesh, MESH_DEFAULTS)
 
 
 def mesh_rows(res, b, nv, nf):

@@ -16,41 +16,38 @@ import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import HAND_GEOMETRY, DeviceOp, checked_params, volume_batch
+from .grasp_post import HAND_GEOMETRY, DeviceOp, checked_params, picked, volume_batch
 
 HAND_DEFAULTS = dict(HAND_GEOMETRY, opening=None, spacing=0.5, approach=0.05)
 PLAN_DEFAULTS = dict(level=0.0)                              # what a plan adds: collision_free = approach_clearance > level
 EXECUTE_GRASP_OPENING = 0.08                                 # execute_grasp opens the hand to max_opening_width (simulation.py:372)
-CLOSURE_ROWS = ('travel', 'cosine', 'contact', 'closed')
+HAND_ROW_TYPES = dict(clearance=((2,), torch.float32), worst=((2,), torch.int32), inside=((2,), torch.int32))      # per grasp: shape, dtype
+CLOSURE_ROW_TYPES = dict(travel=((2,), torch.float32), cosine=((2,), torch.float32), contact=((2,), torch.int32), closed=((), torch.float32))
+CLOSURE_ROWS = tuple(CLOSURE_ROW_TYPES)
 CLOSURE_DEFAULTS = dict(HAND_DEFAULTS, level=0.0, bisections=4)                # FingerClosure.__call__'s keywords
 CLOSURE_PLAN_DEFAULTS = dict(max_opening=0.08, friction=None)                  # what a plan adds: closure_from_rows's keywords
 CHECK_SUCCESS_FRACTION = 0.1                                                   # check_success: width > 0.1 * max_opening_width (simulation.py:468)
+
+
+def _hand_params(what, given, defaults):
+    """checked_params, with the hand's own keys as floats and checked (checked_hand)."""
+    out = checked_params(what, given, defaults)
+    if out is not None:
+        for k in ('height', 'finger_width', 'tail_length', 'depth', 'spacing', 'approach'):
+            out[k] = float(out[k])
+        out['opening'] = None if out['opening'] is None else float(out['opening'])
+        checked_hand(**picked(out, HAND_DEFAULTS))
+    return out
 
 
 def hand_params(clearance, **more):
     """A plan's `clearance` / a session's `hand_clearance` argument -> None, or the hand's parameters (True / {}: the viewer's hand of
     draw_gripper_o3d opened to each grasp's own predicted width, samples half a voxel apart, a 5 cm approach, collision_free =
     approach_clearance > 0).  more: further keys the caller takes, with their defaults (plan_real's `filter`)."""
-    out = checked_params('clearance', clearance, {**HAND_DEFAULTS, **PLAN_DEFAULTS, **more})
-    if out is None:
-        return None
-    for k in ('height', 'finger_width', 'tail_length', 'depth', 'spacing', 'approach', 'level'):
-        out[k] = float(out[k])
-    out['opening'] = None if out['opening'] is None else float(out['opening'])
-    checked_hand(**{k: out[k] for k in HAND_DEFAULTS})
+    out = _hand_params('clearance', clearance, {**HAND_DEFAULTS, **PLAN_DEFAULTS, **more})
+    if out is not None:
+        out['level'] = float(out['level'])
     return out
-
-
-def same_hand_params(a, b):
-    """Whether two hand_params results ask for the same check (either may hold further keys, plan_real's `filter`)."""
-    if a is None or b is None:
-        return a is None and b is None
-    return all(a[k] == b.get(k) for k in (*HAND_DEFAULTS, *PLAN_DEFAULTS))
-
-
-def device_params(hp):
-    """hand_params -> the keyword arguments of HandClearance.__call__ it sets."""
-    return {k: hp[k] for k in HAND_DEFAULTS}
 
 
 def checked_hand(height=0.004, finger_width=0.004, tail_length=0.04, depth=0.05, opening=None, spacing=0.5, approach=0.05):
@@ -94,13 +91,34 @@ def checked_rows(pos, quat, width, count, top_k, B, d):
     return pos, quat, width, n
 
 
-class HandClearance(DeviceOp):
-    """The clearance of the hand at rows of grasps of B volumes.  The output buffers are kept per shape and written again by the next
+class _GraspRows(DeviceOp):
+    """What the two checks of rows of grasps share.  The output buffers (ROW_TYPES) are kept per shape and written again by the next
     call of that shape, so their addresses are stable for a captured graph."""
 
     def __init__(self, device='cuda:0'):
-        super().__init__(device, 'hand clearance')
+        super().__init__(device, self.NOUN)
         self._out = {}
+
+    def _checked(self, vol, pos, quat, width, count, scale, top_k, *hand):
+        """The arguments both kernels take (hand: checked_hand's, in its order), checked -> (GnrHandParams, vol, pos, quat, width, B, R, n,
+        this shape's output tensors)."""
+        d = self.device
+        hand = checked_hand(*hand)
+        vol, B, R = volume_batch(vol, d)
+        pos, quat, width, n = checked_rows(pos, quat, width, count, top_k, B, d)
+        out = self._out.get((B, n))
+        if out is None:
+            out = self._out[(B, n)] = tuple(torch.zeros(B, n, *tail, dtype=dtype, device=d) for tail, dtype in self.ROW_TYPES.values())
+        return _lib.GnrHandParams(scale=float(scale), **hand), vol, pos, quat, width, B, R, n, out
+
+    def of_selection(self, vol, sel, *, scale, **kw):
+        """... of the rows of a GraspSelector result (any route's: plan, plan_real, plan_depth), with its top_k."""
+        return self(vol, selection_pos(sel), sel['quat'], sel['width'], sel['count'], scale=scale, top_k=sel.get('top_k'), **kw)
+
+
+class HandClearance(_GraspRows):
+    """The clearance of the hand at rows of grasps of B volumes."""
+    NOUN, ROW_TYPES = 'hand clearance', HAND_ROW_TYPES
 
     def __call__(self, vol, pos, quat, width, count, *, scale, top_k=None, height=0.004, finger_width=0.004, tail_length=0.04, depth=0.05,
                  opening=None, spacing=0.5, approach=0.05):
@@ -115,35 +133,21 @@ class HandClearance(DeviceOp):
         nothing of the hand is inside the volume), 'worst': [B,max_n,2] int32 (the ordinal of the sample that attains it, -1: none),
         'inside': [B,max_n,2] int32 (the samples inside the volume)}; rows beyond min(count, top_k, max_n) keep what they held.
         The tensors are this object's: the next call with the same shape writes them again."""
-        d = self.device
-        hand = checked_hand(height, finger_width, tail_length, depth, opening, spacing, approach)
-        vol, B, R = volume_batch(vol, d)
-        pos, quat, width, n = checked_rows(pos, quat, width, count, top_k, B, d)
-        out = self._out.get((B, n))
-        if out is None:
-            out = self._out[(B, n)] = (torch.zeros(B, n, 2, dtype=torch.float32, device=d), torch.zeros(B, n, 2, dtype=torch.int32, device=d),
-                                       torch.zeros(B, n, 2, dtype=torch.int32, device=d))
-        p = _lib.GnrHandParams(scale=float(scale), **hand)
+        p, vol, pos, quat, width, B, R, n, out = self._checked(vol, pos, quat, width, count, scale, top_k, height, finger_width, tail_length, depth,
+                                                               opening, spacing, approach)
         rc = self.L.gnr_hand_clearance_fwd(C.byref(p), vol.data_ptr(), pos.data_ptr(), quat.data_ptr(), width.data_ptr(), count.data_ptr(),
-                                           count.numel() // B, B, R, n, int(top_k or 0), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                           self._stream())
+                                           count.numel() // B, B, R, n, int(top_k or 0), *(t.data_ptr() for t in out), self._stream())
         _lib.check(rc, 'gnr_hand_clearance_fwd')
-        return dict(zip(('clearance', 'worst', 'inside'), out))
-
-    def of_selection(self, vol, sel, *, scale, **hand):
-        """... of the rows of a GraspSelector result (any route's: plan, plan_real, plan_depth), with its top_k."""
-        return self(vol, selection_pos(sel), sel['quat'], sel['width'], sel['count'], scale=scale, top_k=sel.get('top_k'), **hand)
+        return dict(zip(HAND_ROW_TYPES, out))
 
 
-class FingerClosure(DeviceOp):
+class FingerClosure(_GraspRows):
     """Where the two fingers stop when the hand closes on the volume, at rows of grasps of B volumes (csrc/gnr_hand.hip,
     gnr_finger_closure_fwd): the third step of execute_grasp -- `gripper.move(0.0)` and check_success (gd/simulation.py:404,465-469) --
-    answered from the volume.  include/gnr.h states the arithmetic; the results are the bits of tests/closure_reference.py.  The output
-    buffers are kept per shape, as HandClearance's."""
-
-    def __init__(self, device='cuda:0'):
-        super().__init__(device, 'finger closure')
-        self._out = {}
+    answered from the volume.  include/gnr.h states the arithmetic; the results are the bits of tests/closure_reference.py.  The depth
+    route has no switch for it and calls of_selection by hand with level=0.5 on (tsdf + 1) / 2 where weight > 0 and 1 elsewhere
+    (get_grid() itself is 0 in unseen and far free space, which would read as solid)."""
+    NOUN, ROW_TYPES = 'finger closure', CLOSURE_ROW_TYPES
 
     def __call__(self, vol, pos, quat, width, count, *, scale, top_k=None, level=0.0, bisections=4, height=0.004, finger_width=0.004,
                  tail_length=0.04, depth=0.05, opening=None, spacing=0.5, approach=0.05):
@@ -157,27 +161,14 @@ class FingerClosure(DeviceOp):
         the surface's normal at the contact and the closing direction; 1: squarely, 0: no contact), 'contact': [B,max_n,2] int32 (the
         ordinal of the ray that stopped the finger, -1: none), 'closed': [B,max_n] float32 (the width of the closed hand in metres)};
         rows beyond min(count, top_k, max_n) keep what they held.  The tensors are this object's."""
-        d = self.device
-        hand = checked_hand(height, finger_width, tail_length, depth, opening, spacing, approach)
         level, bisections = checked_closure(level, bisections)
-        vol, B, R = volume_batch(vol, d)
-        pos, quat, width, n = checked_rows(pos, quat, width, count, top_k, B, d)
-        out = self._out.get((B, n))
-        if out is None:
-            out = self._out[(B, n)] = (torch.zeros(B, n, 2, dtype=torch.float32, device=d), torch.zeros(B, n, 2, dtype=torch.float32, device=d),
-                                       torch.zeros(B, n, 2, dtype=torch.int32, device=d), torch.zeros(B, n, dtype=torch.float32, device=d))
-        p = _lib.GnrHandParams(scale=float(scale), **hand)
+        p, vol, pos, quat, width, B, R, n, out = self._checked(vol, pos, quat, width, count, scale, top_k, height, finger_width, tail_length, depth,
+                                                               opening, spacing, approach)
         rc = self.L.gnr_finger_closure_fwd(C.byref(p), level, bisections, vol.data_ptr(), pos.data_ptr(), quat.data_ptr(), width.data_ptr(),
                                            count.data_ptr(), count.numel() // B, B, R, n, int(top_k or 0), *(t.data_ptr() for t in out),
                                            self._stream())
         _lib.check(rc, 'gnr_finger_closure_fwd')
         return dict(zip(CLOSURE_ROWS, out))
-
-    def of_selection(self, vol, sel, *, scale, **kw):
-        """... of the rows of a GraspSelector result (any route's: plan, plan_real, plan_depth), with its top_k.  The depth route has
-        no switch for it and calls this by hand with level=0.5 on (tsdf + 1) / 2 where weight > 0 and 1 elsewhere (get_grid() itself is 0
-        in unseen and far free space, which would read as solid)."""
-        return self(vol, selection_pos(sel), sel['quat'], sel['width'], sel['count'], scale=scale, top_k=sel.get('top_k'), **kw)
 
 
 def checked_closure(level=0.0, bisections=4):
@@ -194,16 +185,12 @@ def closure_params(closure, **more):
     opened to each grasp's own predicted width, pad rays half a voxel apart, the surface at 0, held = both fingers touch and the closed
     hand is wider than 0.1 * 0.08 m, no friction coefficient).  more: further keys the caller takes, with their defaults (plan_real's
     `filter`)."""
-    out = checked_params('closure', closure, {**CLOSURE_DEFAULTS, **CLOSURE_PLAN_DEFAULTS, **more})
-    if out is None:
-        return None
-    for k in ('height', 'finger_width', 'tail_length', 'depth', 'spacing', 'approach', 'max_opening'):
-        out[k] = float(out[k])
-    for k in ('opening', 'friction'):
-        out[k] = None if out[k] is None else float(out[k])
-    checked_hand(**{k: out[k] for k in HAND_DEFAULTS})
-    out['level'], out['bisections'] = checked_closure(out['level'], out['bisections'])
-    checked_held(out['max_opening'], out['friction'])
+    out = _hand_params('closure', closure, {**CLOSURE_DEFAULTS, **CLOSURE_PLAN_DEFAULTS, **more})
+    if out is not None:
+        out['max_opening'] = float(out['max_opening'])
+        out['friction'] = None if out['friction'] is None else float(out['friction'])
+        out['level'], out['bisections'] = checked_closure(out['level'], out['bisections'])
+        checked_held(out['max_opening'], out['friction'])
     return out
 
 
@@ -212,23 +199,6 @@ def checked_held(max_opening=0.08, friction=None):
         raise ValueError(f'closure max_opening must be finite and > 0 metres, got {max_opening!r}')
     if friction is not None and not (math.isfinite(friction) and friction >= 0):
         raise ValueError(f'closure friction must be None or finite and >= 0, got {friction!r}')
-
-
-def same_closure_params(a, b):
-    """Whether two closure_params results ask for the same product (either may hold further keys, plan_real's `filter`)."""
-    if a is None or b is None:
-        return a is None and b is None
-    return all(a[k] == b.get(k) for k in (*CLOSURE_DEFAULTS, *CLOSURE_PLAN_DEFAULTS))
-
-
-def closure_device_params(cp):
-    """closure_params -> the keyword arguments of FingerClosure.__call__ it sets."""
-    return {k: cp[k] for k in CLOSURE_DEFAULTS}
-
-
-def closure_host_params(cp):
-    """closure_params -> the keyword arguments of closure_from_rows it sets."""
-    return {k: cp[k] for k in CLOSURE_PLAN_DEFAULTS}
 
 
 def closure_rows(res, b, n):
@@ -255,7 +225,7 @@ def closure_from_rows(rows, max_opening=0.08, friction=None):
 
 def hand_rows(res, b, n):
     """The device rows of scene b of a HandClearance result, given the number of grasps n the selection stored."""
-    return {k: res[k][b, :n] for k in ('clearance', 'worst', 'inside')}
+    return {k: res[k][b, :n] for k in HAND_ROW_TYPES}
 
 
 def hand_from_rows(rows, level=0.0):

@@ -12,15 +12,10 @@ import numpy as np
 import torch
 
 from .renderer import GraspNeRF
-from .grasp_post import GRASP_UTILS_PROCESS, MESH_DEFAULTS, GraspSelector, MeshExtractor, SurfaceExtractor, checked_params, \
-    grasps_from_selection, mesh_from_extraction, surface_from_extraction
-from .hand import FingerClosure, HandClearance, closure_device_params, closure_from_rows, closure_host_params, \
-    closure_params as _closure_params, closure_rows, device_params as _hand_device_params, hand_from_rows, hand_params as _hand_params, \
-    hand_rows, same_closure_params as _same_closure_params, same_hand_params as _same_hand_params
+from .grasp_post import GRASP_UTILS_PROCESS, GraspSelector, grasps_from_selection, same_params
 from .ingest import axis_tables
-from .planner_session import PLAN_BBOX3D, PlannerSession, deterministic_convolutions
-from .raycast import VolumeRaycaster, depth_params as _depth_params, images_from_raycast, same_depth_params as _same_depth_params, volume_origin
-from .surface_color import SurfaceColorizer, cloud_level, color_params as _color_params, march_params, same_color_params as _same_color_params
+from .planner_session import PLAN_BBOX3D, PRODUCTS, PlannerSession, build_products, deterministic_convolutions, product_params
+from .raycast import depth_params as _depth_params, volume_origin            # (_depth_params: the name the tests and tools know)
 from .tsdf import create_tsdf, rotation_matrix
 
 
@@ -115,41 +110,37 @@ REAL_BBOX3D = ((-0.15, -0.15, 0.0), (0.15, 0.15, 0.3))                          
 REAL_DEPTH_RANGE, REAL_QUE_ID, REAL_VOXEL_SIZE = (0.2, 0.8), 3, 0.3 / 40                                  # grasp_utils.py:122,137,146
 
 
-def _mesh_params(mesh):
-    """plan_real's `mesh` argument -> None, or the surface_mesh parameters of a PlannerSession (True: iso = 0, the exact upper bounds).
-    (Its `volume_depth` argument: raycast.depth_params, here as _depth_params.)"""
-    return checked_params('mesh', mesh, MESH_DEFAULTS)
-
-
 def real_volume_origin():
     """World position of voxel (0,0,0)'s centre of run_real's volume: the lattice origin of its ray cast."""
     return volume_origin(REAL_BBOX3D[0], REAL_VOXEL_SIZE)
 
 
+def _asked(given):
+    """plan_real's product arguments {Product.plan_kw: argument} -> {Product.attr: normalised parameters, or None} (with `filter`, where
+    the product adds columns to the grasps)."""
+    return {t.attr: t.params(given[t.plan_kw], **({'filter': False} if t.keep else {})) for t in PRODUCTS if t.plan_kw is not None}
+
+
+def _session_keywords(asked, surface_rg, normals):
+    """_asked -> PlannerSession's keywords for the real route's products: the cloud over surface_rg, `filter` stripped (a plan's own
+    business), the real route's lattice origin where a product takes one."""
+    kw = dict(surface=dict(rg=tuple(surface_rg)), surface_normals=bool(normals))
+    for t in PRODUCTS:
+        if asked.get(t.attr) is not None:
+            kw[t.session_kw] = {k: v for k, v in asked[t.attr].items() if k != 'filter'}
+            if t.origin:
+                kw[t.session_kw]['origin'] = tuple(real_volume_origin())
+    return kw
+
+
 def real_session(net, n_views, src_hw, img_wh, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), max_grasps=2048, normals=False, mesh=False,
                  volume_depth=False, view_colors=False, clearance=False, closure=False, **kw):
-    """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud
-    (normals=True: with the SDF gradient rows and unit normals of the cloud, for plan_real(normals=True);  mesh: plan_real's, with the
-    triangle mesh of the volume's iso-surface in the graph;  volume_depth: plan_real's, with the ray cast of the volume in the graph;
-    view_colors: plan_real's, with the colouring of each of these from the plan's frames in the graph;  clearance: plan_real's, with
-    the gripper clearance of the stored grasps in the graph;  closure: plan_real's, with their finger closure in the graph)."""
-    vd, mp, cp, hp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors), _hand_params(clearance, filter=False)
-    fp = _closure_params(closure, filter=False)
-    if fp is not None:
-        kw = dict(kw, finger_closure={k: v for k, v in fp.items() if k != 'filter'})
-    if hp is not None:
-        kw = dict(kw, hand_clearance={k: v for k, v in hp.items() if k != 'filter'})
-    if cp is not None:
-        kw = dict(kw, view_colors=dict(cp, origin=tuple(real_volume_origin())))
-    if vd is not None:
-        kw = dict(kw, volume_depth=dict(vd, origin=tuple(real_volume_origin())))
-    if normals:
-        kw = dict(kw, surface_normals=True)
-    if mp is not None:
-        kw = dict(kw, surface_mesh=mp)
+    """The PlannerSession plan_real(session=...) takes: grasp_utils.process's thresholds, the ranking and the surface cloud, and for
+    each of normals, mesh, volume_depth, view_colors, clearance and closure (plan_real's, to be given here as there) that product in
+    the graph."""
+    kw.update(_session_keywords(_asked(locals()), surface_rg, normals))
     return PlannerSession(net, n_views, src_hw, img_wh, max_grasps=max_grasps, voxel_size=REAL_VOXEL_SIZE,
-                          surface=dict(rg=tuple(surface_rg)), order='score' if order == 'score' else 'index', top_k=top_k,
-                          **GRASP_UTILS_PROCESS, **kw)
+                          order='score' if order == 'score' else 'index', top_k=top_k, **GRASP_UTILS_PROCESS, **kw)
 
 
 def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted', top_k=None, surface_rg=(-0.2, 0.2), session=None,
@@ -166,17 +157,17 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     (NeuralRayRenderer.sample_volume_gradient: the reference's summed VJP, world frame) -- and `normals` [N,3] float64 = g / |g|;
     a session must have been built with real_session(normals=True).  The grasps do not depend on the switch.
     mesh=True: the cloud dict gains `mesh` = {vertices [N,3] float64, faces [F,3] int64}: the triangle mesh of the surface tsdf = 0
-    (grasp_post.MeshExtractor, naive surface nets; no counterpart in run_real) in the cloud's own frame -- origin 0, REAL_VOXEL_SIZE per
+    (gnr_surface_mesh_fwd, naive surface nets; no counterpart in run_real) in the cloud's own frame -- origin 0, REAL_VOXEL_SIZE per
     voxel, so it overlays `points` -- with triangle normals towards increasing tsdf; with normals=True also `gradient` [N,3] float32 and
     `normals` [N,3] float64 at the vertices.  mesh=dict(iso=..., max_vertices=..., max_faces=...) sets another level or smaller
     buffers; a session must have been built with the same real_session(mesh=...).  Grasps and cloud do not depend on it.
     volume_depth=True: the cloud dict gains `volume_depth` [V,h,w] float32 -- the camera-z depth in metres (0: no surface) of the surface
-    tsdf = 0 of the volume seen from the plan's own V cameras at the network's image size (raycast.VolumeRaycaster; world frame, voxel
+    tsdf = 0 of the volume seen from the plan's own V cameras at the network's image size (raycast.py over gnr_volume_raycast_fwd; world frame, voxel
     centres at REAL_BBOX3D[0] + (i + 0.5) * REAL_VOXEL_SIZE; `intrinsic` is that of the frames the network sees); with normals=True also
     `volume_depth_normals` [V,h,w,3] float64, unit vectors, zero on a miss.  volume_depth=dict(extrinsics=..., intrinsic=..., hw=...,
     iso=..., step=..., bisections=...) chooses other cameras, another image size or level; a session must have been built with the same
     real_session(volume_depth=...).  Grasps, cloud and mesh do not depend on it.
-    view_colors=True: colours from the plan's own frames (surface_color.SurfaceColorizer; the float frames the network sees, the plan's
+    view_colors=True: colours from the plan's own frames (surface_color.py over gnr_surface_color_*_fwd; the float frames the network sees, the plan's
     cameras).  The cloud dict gains `view_colors` [N,3] float32 -- per point the mean of the bilinear taps of the views that see it,
     weighted by the cosine between the volume's normal there and the direction to each camera; a view sees a point that projects into
     its image, faces it, and whose way to the camera crosses no voxel below the surface level -- `view_weight` [N] float32 (the sum of
@@ -186,7 +177,7 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     cos_min=..., fill=...): the occlusion march's step and its start off the point in voxels (0.5, 1.5), the least cosine (0) and the
     colour without a view (black); a session must have been built with the same real_session(view_colors=...).  `colors` and every
     other key do not depend on it; grasp_post.write_ply takes colors=cloud['view_colors'].
-    clearance=True: whether the hand fits where each grasp puts it, answered from the volume (hand.HandClearance; execute_grasp,
+    clearance=True: whether the hand fits where each grasp puts it, answered from the volume (hand.py over gnr_hand_clearance_fwd; execute_grasp,
     gd/simulation.py:369-402, answers it with physics).  The grasps dict gains `clearance` and `approach_clearance` [n] float32 -- the
     smallest tsdf value under the four boxes of draw_gripper_o3d's hand at the grasp, and over everything they pass through on the
     5 cm approach along the grasp's z; 1.0: nothing of the hand is inside the volume -- `hand_inside` and `hand_worst` [n,2] int32 (the
@@ -197,7 +188,7 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     metres, the level (0) -- and filter=True keeps only the collision_free rows of every column, in their order.  A session must have
     been built with the same real_session(clearance=...) (`filter` aside).  No other key depends on it; grasp_post.hand_mesh draws the
     same boxes.
-    closure=True: what happens when the hand then closes, answered from the volume (hand.FingerClosure; execute_grasp closes the fingers
+    closure=True: what happens when the hand then closes, answered from the volume (gnr_finger_closure_fwd; execute_grasp closes the fingers
     and check_success asks whether they touch something and the hand stays wider than a tenth of its opening, gd/simulation.py:404,
     465-469).  The grasps dict gains `closed_width` [n] float32 -- the width in metres at which the fingers stop on the surface tsdf =
     level, the number a robot compares with its gripper's read-back; 0: nothing between the fingers -- `finger_travel` [n,2] float32
@@ -209,13 +200,12 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     `force_closure` [n] bool = grip_cos >= 1 / sqrt(1 + mu^2); no default, the reference sets none -- and filter=True keeps only the
     `held` rows (with clearance=dict(filter=True) too, the rows that pass both).  A session must have been built with the same
     real_session(closure=...) (`filter` aside).  No other key depends on it.  The depth route (plan_depth) has no such switch: on its selection
-    call hand.FingerClosure(dev).of_selection(vol, sel, scale=size / resolution, level=0.5) by hand, with a volume on the grid's scale
+    call of_selection(vol, sel, scale=size / resolution, level=0.5) of hand.py's closure wrapper by hand, with a volume on the grid's scale
     (tsdf + 1) / 2, whose surface is at 0.5 -- but not get_grid() itself, which is 0 in unseen and far free space and would read as
     solid there: take (tsdf + 1) / 2 where weight > 0 and 1 elsewhere, as tsdf.render_depth does for its ray cast."""
     if order not in ('permuted', 'score'):
         raise ValueError(f"order must be 'permuted' or 'score', got {order!r}")
-    vd, mp, cp, hp = _depth_params(volume_depth), _mesh_params(mesh), _color_params(view_colors), _hand_params(clearance, filter=False)
-    fp = _closure_params(closure, filter=False)
+    asked = _asked(locals())
     ext = np.stack([np.asarray(e, np.float32) for e in extrinsics], 0)                                    # grasp_utils.py:120-122
     V = ext.shape[0]
     if V <= REAL_QUE_ID:
@@ -226,26 +216,18 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
     Ks = np.repeat(np.asarray(intrinsic, np.float32)[None], V, 0)
     sel_order = 'score' if order == 'score' else 'index'
     if session is not None:
-        sp, su = session.selector_params, session.surface_params
         want = dict(GRASP_UTILS_PROCESS, order=sel_order, top_k=top_k)
-        if session.net is not net or su is None or tuple(su['rg']) != tuple(surface_rg) or any(sp[k] != v for k, v in want.items()) \
-                or session.voxel_size != REAL_VOXEL_SIZE or bool(normals) != session.surface_normals \
-                or mp != session.mesh_params or not _same_depth_params(vd, session.volume_depth_params) \
-                or not _same_color_params(cp, session.view_color_params):
-            raise ValueError('plan_real(session=...): the session was built for another net, order, top_k, surface range, normals, mesh, '
-                             'volume_depth or view_colors (build it with planner.real_session)')
-        if not _same_hand_params(hp, getattr(session, 'hand_params', None)):
-            raise ValueError('plan_real(session=...): the session was built for another clearance (build it with '
-                             'planner.real_session(clearance=...))')
-        if not _same_closure_params(fp, getattr(session, 'closure_params', None)):
-            raise ValueError('plan_real(session=...): the session was built for another closure (build it with '
-                             'planner.real_session(closure=...))')
+        general = 'net, order, top_k, surface range, normals, mesh, volume_depth or view_colors'
+        other = [t.noun or general for t in PRODUCTS              # (of the cloud, a plan sets the range alone)
+                 if not same_params(asked.get(t.attr, dict(rg=tuple(surface_rg))), getattr(session, t.attr))]
+        if session.net is not net or any(session.selector_params[k] != v for k, v in want.items()) or session.voxel_size != REAL_VOXEL_SIZE \
+                or bool(normals) != session.surface_normals:
+            other.insert(0, general)
+        if other:
+            raise ValueError(f'plan_real(session=...): the session was built for another {other[0]} (build it with planner.real_session)')
         g, dt = session.plan(images, ext, Ks, REAL_DEPTH_RANGE, REAL_BBOX3D, seed=None, return_volumes=True)
-        tsdf_vol, cloud = g.pop('volumes')[0], session.cloud
-        if session.mesh_params is not None:
-            cloud = dict(cloud, mesh=session.mesh)
-        if session.volume_depth_params is not None:
-            cloud = dict(cloud, **session.volume_images)
+        tsdf_vol = g.pop('volumes')[0]
+        results = [(p, getattr(session, p.attr)) for p in session.products]       # (their columns are in g already: the same again)
     else:
         dev = next(net.parameters()).device
         frames = np.stack([np.asarray(f) for f in images], 0)
@@ -253,7 +235,7 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
             raise ValueError(f'images must be uint8 [V,h,w,3] frames, got {frames.dtype} {frames.shape}')
         imgs = (frames.astype(np.float32) / 255).transpose([0, 3, 1, 2])                                  # color_map_forward, grasp_utils.py:134
         selector = GraspSelector(dev)
-        kept = {}                                                 # the device volume and selection of the plan, for the hand
+        kept = {}                                                 # the device volume and selection of the plan, for the products
 
         def call(vol, q, r, w, **kw):
             kept['vol'], kept['sel'] = vol, selector(vol, q, r, w, **{**kw, **GRASP_UTILS_PROCESS})
@@ -263,41 +245,21 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
                          tsdf_thres_high=GRASP_UTILS_PROCESS['tsdf_thres_high'], tsdf_thres_low=GRASP_UTILS_PROCESS['tsdf_thres_low'],
                          order=sel_order, top_k=top_k, return_volumes=True, que_id=REAL_QUE_ID)
         tsdf_vol = g.pop('volumes')[0]
-        if hp is not None:                                        # positions are voxel indices: the lattice is the volume's own
-            res = HandClearance(dev).of_selection(kept['vol'], kept['sel'], scale=REAL_VOXEL_SIZE, **_hand_device_params(hp))
-            rows = hand_rows(res, 0, len(g['score']))
-            g.update(hand_from_rows({k: v.cpu().numpy() for k, v in rows.items()}, hp['level']))
-        if fp is not None:
-            res = FingerClosure(dev).of_selection(kept['vol'], kept['sel'], scale=REAL_VOXEL_SIZE, **closure_device_params(fp))
-            rows = closure_rows(res, 0, len(g['score']))
-            g.update(closure_from_rows({k: v.cpu().numpy() for k, v in rows.items()}, **closure_host_params(fp)))
-        grad = None
-        if normals:                                               # the volume's cameras again: the forward keeps no feature maps
-            grad = _volume_gradient(net, imgs, ext, Ks, dev)
-        res = SurfaceExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), rg=surface_rg, gradient=grad)     # grasp_utils.py:149
-        if cp is not None:                                        # the frames the network saw, the plan's cameras, the volume's lattice
-            paint, origin = SurfaceColorizer(dev), real_volume_origin()
-            src = (torch.as_tensor(imgs, device=dev), ext[:, :3, :], Ks)
-            lattice = dict(march_params(cp), origin=origin, scale=REAL_VOXEL_SIZE)
-            res.update(paint.points(torch.as_tensor(tsdf_vol, device=dev), res['points'], res['count'], *src, point_offset=origin,
-                                    iso=cloud_level(surface_rg), **lattice))
-        cloud = surface_from_extraction(res, 0)
-        if mp is not None:
-            res = MeshExtractor(dev)(torch.as_tensor(tsdf_vol, device=dev), **mp, scale=REAL_VOXEL_SIZE, gradient=grad)
-            if cp is not None:
-                res.update(paint.points(torch.as_tensor(tsdf_vol, device=dev), res['vertices'], res['count'], *src, point_offset=origin,
-                                        iso=mp['iso'], **lattice))
-            cloud['mesh'] = mesh_from_extraction(res, 0)
-        if vd is not None:
-            K = Ks[0] if vd['intrinsic'] is None else vd['intrinsic']
-            poses = ext[:, :3, :] if vd['extrinsics'] is None else vd['extrinsics']
-            res = VolumeRaycaster(dev)(torch.as_tensor(tsdf_vol, device=dev), poses, np.repeat(K[None], len(poses), 0),
-                                       frames.shape[1:3] if vd['hw'] is None else vd['hw'], origin=real_volume_origin(), scale=REAL_VOXEL_SIZE,
-                                       iso=vd['iso'], step=vd['step'], bisections=vd['bisections'], gradient=grad)
-            if cp is not None:
-                res.update(paint.pixels(torch.as_tensor(tsdf_vol, device=dev), res['depth'], poses, np.repeat(K[None], len(poses), 0), *src,
-                                        iso=vd['iso'], **lattice))
-            cloud.update(images_from_raycast(res, 0))
+        # the products a real_session would record, on the plan's volume, the frames the network saw and the plan's cameras;  the
+        # gradient from the volume's cameras again: the forward keeps no feature maps
+        products = build_products(product_params(_session_keywords(asked, surface_rg, normals)), dev=dev, R=tsdf_vol.shape[-1],
+                                  max_grasps=selector.max_grasps, n_views=V, hw=frames.shape[1:3], voxel_size=REAL_VOXEL_SIZE,
+                                  normals=bool(normals), lean=False)
+        grad = _volume_gradient(net, imgs, ext, Ks, dev) if normals else None
+        cams = {'poses': torch.as_tensor(ext[:, :3, :], device=dev), 'Ks': torch.as_tensor(Ks, device=dev)}
+        seen, results = torch.as_tensor(imgs, device=dev), []
+        for p in products:                                        # each one's rows are on the host before the next one records
+            res = p.record(kept['vol'], grad, cams, seen, kept['sel'])
+            counts = res['count'].reshape(-1).tolist() if p.words else []
+            results.append((p, p.result({k: v.cpu().numpy() for k, v in p.rows(res, counts, len(g['score'])).items()})))
+    cloud = {}
+    for p, out in results:
+        (g if p.columns else cloud).update(out if p.key is None else {p.key: out})
     tsdf_vol = np.asarray(tsdf_vol).reshape(tsdf_vol.shape[-3:])
     n = len(g['score'])
     if order == 'permuted' and n > 0:                                                                     # grasp_utils.py:144-147
@@ -305,7 +267,7 @@ def plan_real(net, images, extrinsics, intrinsic, *, seed=None, order='permuted'
             np.random.seed(seed)
         p = np.random.permutation(n)
         g = {k: v[p] for k, v in g.items()}
-    keep = [g[k] for k, on in (('collision_free', hp), ('held', fp)) if on is not None and on['filter']]
+    keep = [g[t.keep] for t in PRODUCTS if t.keep and asked[t.attr] is not None and asked[t.attr]['filter']]
     if keep:
         g = {k: v[np.logical_and.reduce(keep)] for k, v in g.items()}
     return g, g['score'], tsdf_vol, cloud, dt

@@ -8,21 +8,24 @@ Limits: one scene per plan, a fixed view count, frame size and selector paramete
 route); the model's parameters may change between plans (the graph is captured again when they did)."""
 import contextlib
 import time
+import types
+import typing
 
 import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import MESH_DEFAULTS, SELECTOR_DEFAULTS, SURFACE_DEFAULTS, VIEW_KEYS, GraspSelector, MeshExtractor, SurfaceExtractor, \
-    checked_params, grasps_from_selection, mesh_bounds, mesh_from_rows, mesh_rows, surface_from_rows, surface_rows
-from .hand import FingerClosure, HandClearance, closure_device_params, closure_from_rows, closure_host_params, closure_params, closure_rows, \
-    device_params, hand_from_rows, hand_params, hand_rows
+from .grasp_post import SELECTOR_DEFAULTS, SURFACE_DEFAULTS, VIEW_KEYS, GraspSelector, MeshExtractor, SurfaceExtractor, checked_params, \
+    grasps_from_selection, mesh_bounds, mesh_from_rows, mesh_params, mesh_rows, picked, surface_from_rows, surface_params, surface_rows
+from .hand import CLOSURE_DEFAULTS, CLOSURE_PLAN_DEFAULTS, CLOSURE_ROW_TYPES, HAND_DEFAULTS, HAND_ROW_TYPES, PLAN_DEFAULTS, FingerClosure, \
+    HandClearance, closure_from_rows, closure_params, closure_rows, hand_from_rows, hand_params, hand_rows
 from .ingest import DeviceIngest
 from .raycast import COLOR_KEYS, VolumeRaycaster, depth_params, images_from_rows, raycast_rows, volume_origin
-from .surface_color import SurfaceColorizer, cloud_level, color_params, march_params
+from .surface_color import COLOR_DEFAULTS, SurfaceColorizer, cloud_level, color_params
 
 _SEG = 64                                                    # floats: every camera block starts on a 256-byte boundary
 PLAN_BBOX3D = ((-0.15, -0.15, -0.0503), (0.15, 0.15, 0.2497))       # the planner's workspace box (main.py:91): plan()'s default
+PLAN_ORIGIN = tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40))        # ... and the lattice origin of its volume: the products' default
 
 
 @contextlib.contextmanager
@@ -38,13 +41,15 @@ def deterministic_convolutions(on=True):
 
 
 # ---- the optional products of the volume ---------------------------------------------------------------------------------------------
-# A product is one further output of the session's graph.  It owns (1) its normalised parameters, (2) its extractor, its pinned read-back
-# buffers and the number of count words it appends to the packed selection, (3) record(): its step of the captured forward (it gets the
-# volume, its gradient, the cameras, the ingested frames and the selection), and (4) fetch() / result(): the sized copies of one plan's
-# rows (by its own count words, or by the number of stored grasps) and, after the session's one wait, the numpy dict -- through the same
-# *_rows / *_from_rows pair as the eager route (grasp_post.py, raycast.py).  PlannerSession builds the list `products` from its keywords
-# and names no product anywhere else (plan() merges the result of every product with `columns` into the grasps it returns); a new one
-# is a class here, a keyword and one line in that list.
+# A product is one further output of a plan, on both routes: a PlannerSession records it into its graph, the eager planner.plan_real runs
+# it after its forward.  It states (1) its normalised parameters, its device wrappers and the number of count words it appends to a
+# session's packed selection, (2) record(): its device step (it gets the volume, its gradient, the cameras, the float frames and the
+# selection), (3) rows(): which device rows of that result belong to one plan (by its own count words, or by the number of stored
+# grasps), and shapes(): the most such rows, (4) result(): the plan's numpy dict from those rows on the host -- through the *_rows /
+# *_from_rows pair beside its wrapper (grasp_post.py, raycast.py, hand.py).  How the rows reach the host is the route's: a session
+# copies them into pinned twins of shapes() and waits once, the eager route reads each product's rows before the next one records.
+# The table PRODUCTS below lists them with their keywords; nothing else names a product (a product with `columns` adds columns to the
+# grasps, the others join the cloud's dict, under `key` if they have one).
 # The view colours (`colors`: a _Colors, or None) are no product of their own: each product colours its own rows in its record(), right
 # after the step that makes them, and reads the colours back with them.
 class _Pinned:
@@ -78,9 +83,9 @@ class _Colors:
     """What a product needs to colour its rows from the plan's views (surface_color.SurfaceColorizer): the march's parameters, the
     volume's lattice (origin, voxel size) and a colouriser of its own, whose kept buffers are the product's."""
 
-    def __init__(self, params, voxel_size, dev):
-        self.origin, self.op = params['origin'], SurfaceColorizer(dev)
-        self.kw = dict(march_params(params), origin=params['origin'], scale=voxel_size)
+    def __init__(self, params, env):
+        self.origin, self.op = params['origin'], SurfaceColorizer(env.dev)
+        self.kw = dict(picked(params, COLOR_DEFAULTS), origin=params['origin'], scale=env.voxel_size)
 
     def points(self, vol, res, key, images, cams, iso):
         """An extractor's result, completed with the view colours of its rows `key` (in the frame with origin 0)."""
@@ -88,31 +93,46 @@ class _Colors:
         return res
 
 
-class _Cloud:
-    """The surface cloud: one count word; the index rows (the colours in value-map mode, the gradient rows with normals) are read back,
-    the float64 points stay on the device and are recomputed on the host as index * scale, a fixed colour is known on the host."""
-    out, attr, words, columns = 'surface', 'cloud', 1, False
+class _Product:
+    """params: the product's normalised parameters;  env: what the route knows (dev, R, max_grasps, n_views, hw = the frames' (H, W),
+    voxel_size, normals, cloud_scale, lean: a session's, which leaves on the device what the host knows);  paint(): a _Colors of the
+    product's own, or None.  words: its count words;  columns: it adds columns to the grasps;  key: where it goes in the cloud's dict
+    (None: its keys join the dict's);  kept: the host rows result() hands on as they are;  wrapper: of its device step, self.op;
+    painted: it colours its rows, with self.colors."""
+    words, columns, key, kept, painted = 0, False, None, (), True
 
-    def __init__(self, params, R, normals, dev, colors=None):
-        self.params, self.extract, self.colors = params, SurfaceExtractor(dev), colors
-        n = R ** 3 if params['max_points'] is None else int(params['max_points'])
-        self.pinned = _Pinned(index=((n, 3), torch.int32), colors=((n, 3), torch.float32), **_gradient_rows(normals, n, 3), **_view_rows(colors, n))
+    def __init__(self, params, env, paint):
+        self.params, self.env, self.op, self.colors = params, env, self.wrapper(env.dev), paint() if self.painted else None
+
+
+class _Cloud(_Product):
+    """The surface cloud: one count word.  A session reads back the index rows (the colours in value-map mode, the gradient rows with
+    normals); the float64 points stay on the device and are recomputed on the host as index * scale, a fixed colour is known on the
+    host, and its cloud says its row count."""
+    out, attr, words, kept, wrapper = 'surface', 'cloud', 1, ('gradient', *VIEW_KEYS), SurfaceExtractor
+
+    def shapes(self):
+        n = self.env.R ** 3 if self.params['max_points'] is None else int(self.params['max_points'])
+        return dict(index=((n, 3), torch.int32), colors=((n, 3), torch.float32), **_gradient_rows(self.env.normals, n, 3),
+                    **_view_rows(self.colors, n))
 
     def record(self, vol, grad, cams, images, sel):
-        res = self.extract(vol, **self.params, gradient=grad)
+        res = self.op(vol, **self.params, gradient=grad)
         if self.colors is not None:                          # occluded below the middle of the cloud's range (0 for the real route's)
             self.colors.points(vol, res, 'points', images, cams, cloud_level(self.params['rg']))
         return res
 
-    def fetch(self, res, counts, n_sel):
+    def rows(self, res, counts, n_sel):
         rows = surface_rows(res, 0, *counts)
-        del rows['points']
-        if self.params['color'] is not None:
-            del rows['colors']
-        self.pinned.fetch(rows)
+        if self.env.lean:
+            del rows['points']
+            if self.params['color'] is not None:
+                del rows['colors']
+        return rows
 
-    def result(self):
-        rows = self.pinned.host('gradient', *VIEW_KEYS)
+    def result(self, rows):
+        if 'points' in rows:
+            return surface_from_rows(rows)
         n = len(rows['index'])
         rows['points'] = rows['index'].astype(np.float64) * float(self.params['scale'])
         if 'colors' not in rows:
@@ -120,44 +140,45 @@ class _Cloud:
         return {'count': n, **surface_from_rows(rows)}
 
 
-class _Mesh:
+class _Mesh(_Product):
     """The triangle mesh of the iso-surface, in the cloud's frame (origin 0, the cloud's scale): two count words, vertices and
     triangles; the stored vertex, face (and gradient) rows are read back."""
-    out, attr, words, columns = 'mesh', 'mesh', 2, False
+    out, attr, words, key, kept, wrapper = 'mesh', 'mesh', 2, 'mesh', ('vertices', 'gradient', *VIEW_KEYS), MeshExtractor
+    result = staticmethod(mesh_from_rows)
 
-    def __init__(self, params, R, normals, dev, scale, colors=None):
-        self.params, self.scale, self.extract, self.colors = params, scale, MeshExtractor(dev), colors
-        nv, nf = (b if m is None else int(m) for b, m in zip(mesh_bounds(R), (params['max_vertices'], params['max_faces'])))
-        self.pinned = _Pinned(vertices=((nv, 3), torch.float64), faces=((nf, 3), torch.int32), **_gradient_rows(normals, nv, 3),
-                              **_view_rows(colors, nv))
+    def shapes(self):
+        nv, nf = (b if m is None else int(m) for b, m in zip(mesh_bounds(self.env.R), (self.params['max_vertices'], self.params['max_faces'])))
+        return dict(vertices=((nv, 3), torch.float64), faces=((nf, 3), torch.int32), **_gradient_rows(self.env.normals, nv, 3),
+                    **_view_rows(self.colors, nv))
 
     def record(self, vol, grad, cams, images, sel):
-        res = self.extract(vol, **self.params, scale=self.scale, gradient=grad)
+        res = self.op(vol, **self.params, scale=self.env.cloud_scale, gradient=grad)
         if self.colors is not None:                          # (the count's stride is 2: vertices, triangles)
             self.colors.points(vol, res, 'vertices', images, cams, self.params['iso'])
         return res
 
-    def fetch(self, res, counts, n_sel):
-        self.pinned.fetch(mesh_rows(res, 0, *counts))
-
-    def result(self):
-        return mesh_from_rows(self.pinned.host('vertices', 'gradient', *VIEW_KEYS))
+    def rows(self, res, counts, n_sel):
+        return mesh_rows(res, 0, *counts)
 
 
-class _DepthImages:
-    """The ray cast of the volume: no count word, the whole images are read back.  Without cameras of its own it reads the plan's from
-    the session's device block, which every plan uploads anyway; other cameras are the session's, uploaded once."""
-    out, attr, words, columns = 'volume_depth', 'volume_images', 0, False
+class _DepthImages(_Product):
+    """The ray cast of the volume: no count word, the whole images are read back.  Without cameras of its own it takes the plan's (a
+    session's device block, which every plan uploads anyway); other cameras are the product's, uploaded once."""
+    out, attr, kept, wrapper = 'volume_depth', 'volume_images', ('depth', *COLOR_KEYS), VolumeRaycaster
+    result = staticmethod(images_from_rows)
 
-    def __init__(self, params, n_views, hw, voxel_size, normals, dev, colors=None):
-        self.params, self.scale, self.cast, self.colors = params, voxel_size, VolumeRaycaster(dev), colors
-        self.hw = hw if params['hw'] is None else params['hw']
-        nv = n_views if params['extrinsics'] is None else len(params['extrinsics'])
-        up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+    def __init__(self, params, env, paint):
+        super().__init__(params, env, paint)
+        self.hw = env.hw if params['hw'] is None else params['hw']
+        self.nv = env.n_views if params['extrinsics'] is None else len(params['extrinsics'])
+        up = lambda a: None if a is None else torch.from_numpy(a).to(env.dev)
         self.poses = up(params['extrinsics'])
-        self.Ks = up(None if params['intrinsic'] is None else np.repeat(params['intrinsic'][None], nv, 0))
-        color_rows = {} if colors is None else dict(zip(COLOR_KEYS, (((nv, *self.hw, 3), torch.float32), ((nv, *self.hw), torch.float32))))
-        self.pinned = _Pinned(depth=((nv, *self.hw), torch.float32), **_gradient_rows(normals, nv, *self.hw, 3), **color_rows)
+        self.Ks = up(None if params['intrinsic'] is None else np.repeat(params['intrinsic'][None], self.nv, 0))
+
+    def shapes(self):
+        shape = (self.nv, *self.hw)
+        color_rows = {} if self.colors is None else dict(zip(COLOR_KEYS, (((*shape, 3), torch.float32), (shape, torch.float32))))
+        return dict(depth=(shape, torch.float32), **_gradient_rows(self.env.normals, *shape, 3), **color_rows)
 
     def record(self, vol, grad, cams, images, sel):
         p = self.params
@@ -165,58 +186,81 @@ class _DepthImages:
         Ks = cams['Ks'] if self.Ks is None else self.Ks
         if Ks.shape[0] != poses.shape[0]:                    # the plan's own intrinsics (one per view, all equal on this route) for other cameras
             Ks = Ks[:1].expand(poses.shape[0], 3, 3)
-        res = self.cast(vol, poses, Ks, self.hw, origin=p['origin'], scale=self.scale, iso=p['iso'], step=p['step'],
+        res = self.op(vol, poses, Ks, self.hw, origin=p['origin'], scale=self.env.voxel_size, iso=p['iso'], step=p['step'],
                         bisections=p['bisections'], gradient=grad)
         if self.colors is not None:                          # the ray cast's own lattice and level; the sources are the plan's views
             res.update(self.colors.op.pixels(vol, res['depth'], poses, Ks, images, cams['poses'], cams['Ks'],
                                              **dict(self.colors.kw, origin=p['origin']), iso=p['iso']))
         return res
 
-    def fetch(self, res, counts, n_sel):
-        self.pinned.fetch(raycast_rows(res, 0))
-
-    def result(self):
-        return images_from_rows(self.pinned.host('depth', *COLOR_KEYS))
+    def rows(self, res, counts, n_sel):
+        return raycast_rows(res, 0)
 
 
-class _Hand:
-    """The gripper clearance of the selected grasps (hand.HandClearance): no count word -- its rows are the selection's, read back sized
-    by the selection's count.  It reads the selection, so it is recorded right after it."""
-    out, attr, words, columns = 'hand', 'hand', 0, True      # columns: one row per stored grasp, merged into plan()'s grasps
+class _Hand(_Product):
+    """The gripper clearance of the selected grasps (hand.HandClearance): no count word -- its rows are the selection's, sized by the
+    selection's count.  It reads the selection, so it comes right after it; positions are voxel indices, the lattice is the volume's."""
+    out, attr, columns, painted = 'hand', 'hand', True, False      # columns: one row per stored grasp, merged into the plan's grasps
+    wrapper, row_types, rows_of, from_rows = HandClearance, HAND_ROW_TYPES, staticmethod(hand_rows), staticmethod(hand_from_rows)
+    device_keys, host_keys = HAND_DEFAULTS, PLAN_DEFAULTS    # the keywords of the wrapper's call and of from_rows among the parameters
 
-    def __init__(self, params, max_grasps, voxel_size, dev):
-        self.params, self.scale, self.op = params, voxel_size, HandClearance(dev)
-        self.pinned = _Pinned(clearance=((max_grasps, 2), torch.float32), worst=((max_grasps, 2), torch.int32),
-                              inside=((max_grasps, 2), torch.int32))
+    def shapes(self):
+        return {k: ((self.env.max_grasps, *tail), dtype) for k, (tail, dtype) in self.row_types.items()}
 
     def record(self, vol, grad, cams, images, sel):
-        return self.op.of_selection(vol, sel, scale=self.scale, **device_params(self.params))
+        return self.op.of_selection(vol, sel, scale=self.env.voxel_size, **picked(self.params, self.device_keys))
 
-    def fetch(self, res, counts, n_sel):
-        self.pinned.fetch(hand_rows(res, 0, n_sel))
+    def rows(self, res, counts, n_sel):
+        return self.rows_of(res, 0, n_sel)
 
-    def result(self):
-        return hand_from_rows(self.pinned.host(), self.params['level'])
+    def result(self, rows):
+        return self.from_rows(rows, **picked(self.params, self.host_keys))
 
 
-class _Closure:
-    """The finger closure of the selected grasps (hand.FingerClosure): like _Hand, no count word, rows sized by the selection's count,
-    recorded right after the selection."""
-    out, attr, words, columns = 'closure', 'closure', 0, True
+class _Closure(_Hand):
+    """The finger closure of the selected grasps (hand.FingerClosure): the same shape of product as _Hand."""
+    out, attr = 'closure', 'closure'
+    wrapper, row_types, rows_of, from_rows = FingerClosure, CLOSURE_ROW_TYPES, staticmethod(closure_rows), staticmethod(closure_from_rows)
+    device_keys, host_keys = CLOSURE_DEFAULTS, CLOSURE_PLAN_DEFAULTS
 
-    def __init__(self, params, max_grasps, voxel_size, dev):
-        self.params, self.scale, self.op = params, voxel_size, FingerClosure(dev)
-        self.pinned = _Pinned(travel=((max_grasps, 2), torch.float32), cosine=((max_grasps, 2), torch.float32),
-                              contact=((max_grasps, 2), torch.int32), closed=((max_grasps,), torch.float32))
 
-    def record(self, vol, grad, cams, images, sel):
-        return self.op.of_selection(vol, sel, scale=self.scale, **closure_device_params(self.params))
+class Product(typing.NamedTuple):
+    """One row of PRODUCTS.  plan_kw: the keyword of planner.plan_real / real_session (None: every plan has it);  session_kw:
+    PlannerSession's;  attr: the session attribute with its normalised parameters;  params: argument -> those (None: not asked for);
+    noun: what planner.plan_real(session=...) says the session was built for another of (None: its general list names it);  cls: its
+    class above (None: it is part of the others);  keep: the bool column of the grasps its plan_real parameter filter=True keeps the
+    rows of;  origin: its parameters take the lattice origin of the volume (PLAN_ORIGIN unless given)."""
+    plan_kw: typing.Optional[str]
+    session_kw: str
+    attr: str
+    params: typing.Callable
+    noun: typing.Optional[str]
+    cls: typing.Optional[type]
+    keep: typing.Optional[str] = None
+    origin: bool = False
 
-    def fetch(self, res, counts, n_sel):
-        self.pinned.fetch(closure_rows(res, 0, n_sel))
 
-    def result(self):
-        return closure_from_rows(self.pinned.host(), **closure_host_params(self.params))
+PRODUCTS = (                                                 # in the order of a session's count words and copies
+    Product('clearance', 'hand_clearance', 'hand_params', hand_params, 'clearance', _Hand, keep='collision_free'),
+    Product('closure', 'finger_closure', 'closure_params', closure_params, 'closure', _Closure, keep='held'),
+    Product(None, 'surface', 'surface_params', surface_params, None, _Cloud),
+    Product('mesh', 'surface_mesh', 'mesh_params', mesh_params, None, _Mesh),
+    Product('volume_depth', 'volume_depth', 'volume_depth_params', depth_params, None, _DepthImages, origin=True),
+    Product('view_colors', 'view_colors', 'view_color_params', color_params, None, None, origin=True),
+)
+
+
+def product_params(given):
+    """PlannerSession's product keywords (absent: not asked for) -> {Product.attr: normalised parameters, or None}."""
+    return {t.attr: t.params(given.get(t.session_kw), **({'origin': PLAN_ORIGIN} if t.origin else {})) for t in PRODUCTS}
+
+
+def build_products(params, **env):
+    """product_params -> the list of the products asked for, in the table's order.  env: _Product's, but for cloud_scale."""
+    env = types.SimpleNamespace(**env, cloud_scale=(params['surface_params'] or SURFACE_DEFAULTS)['scale'])
+    cp = params['view_color_params']
+    paint = (lambda: None) if cp is None else (lambda: _Colors(cp, env))
+    return [t.cls(params[t.attr], env, paint) for t in PRODUCTS if t.cls is not None and params[t.attr] is not None]
 
 
 class PlannerSession:
@@ -273,6 +317,7 @@ class PlannerSession:
     def __init__(self, net, n_views, src_hw, img_wh, max_grasps=2048, voxel_size=0.3 / 40, channels=3, warmup=3, deterministic=True,
                  surface=None, surface_normals=False, surface_mesh=None, volume_depth=None, view_colors=None, hand_clearance=None,
                  finger_closure=None, **selector_params):
+        given = dict(locals())                               # (the products' keywords, by name: PRODUCTS' session_kw)
         cfg = net.nr_net.cfg
         if surface_normals and surface is None:
             raise ValueError('surface_normals=True needs the surface cloud: pass surface=dict(...) ({} for its defaults)')
@@ -281,12 +326,9 @@ class PlannerSession:
         if not cfg.get('sample_volume', False):
             raise ValueError("the planner needs cfg['sample_volume'] = True")
         self.selector_params = checked_params('selector', selector_params, SELECTOR_DEFAULTS)
-        self.surface_params, self.surface_normals = checked_params('surface', surface, SURFACE_DEFAULTS), bool(surface_normals)
-        self.mesh_params = checked_params('mesh', surface_mesh, MESH_DEFAULTS)
-        self.volume_depth_params = depth_params(volume_depth, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
-        self.view_color_params = color_params(view_colors, origin=tuple(volume_origin(PLAN_BBOX3D[0], 0.3 / 40)))
-        self.hand_params = hand_params(hand_clearance)
-        self.closure_params = closure_params(finger_closure)
+        self.surface_normals = bool(surface_normals)
+        params = product_params(given)
+        vars(self).update(params)                            # self.surface_params, .mesh_params, ...: Product.attr
         if self.view_color_params is not None and self.surface_params is None and self.mesh_params is None and self.volume_depth_params is None:
             raise ValueError('view_colors needs a product to colour: pass surface=, surface_mesh= or volume_depth=')
         dev = next(net.parameters()).device
@@ -319,25 +361,15 @@ class PlannerSession:
         self.images = torch.zeros(V, 3, H, W, dtype=torch.float32, device=dev)       # the ingested frames of the last plan
         # the selection, packed for one read-back: count | index [M,3] | score [M] | quat [M,4] | width [M], 4-byte words
         # (+ the cloud's row count, when the session extracts one; + the mesh's vertex and triangle counts, likewise)
-        R, normals = int(cfg['volume_resolution']), self.surface_normals
-        self.products = []                                   # in the order of their count words and of their copies
-        colors = (lambda: None) if self.view_color_params is None else (lambda: _Colors(self.view_color_params, self.voxel_size, dev))
-        if self.hand_params is not None:                     # first: it reads the selection, nothing of the other products
-            self.products.append(_Hand(self.hand_params, M, self.voxel_size, dev))
-        if self.closure_params is not None:                  # likewise
-            self.products.append(_Closure(self.closure_params, M, self.voxel_size, dev))
-        if self.surface_params is not None:
-            self.products.append(_Cloud(self.surface_params, R, normals, dev, colors()))
-        if self.mesh_params is not None:
-            self.products.append(_Mesh(self.mesh_params, R, normals, dev, (self.surface_params or SURFACE_DEFAULTS)['scale'], colors()))
-        if self.volume_depth_params is not None:
-            self.products.append(_DepthImages(self.volume_depth_params, V, (H, W), self.voxel_size, normals, dev, colors()))
+        self.products = build_products(params, dev=dev, R=int(cfg['volume_resolution']), max_grasps=M, n_views=V, hw=(H, W),
+                                       voxel_size=self.voxel_size, normals=self.surface_normals, lean=True)
         words = 1 + 9 * M
-        for p in self.products:
-            p.at, words = words, words + p.words
+        for p in self.products:                              # in the order of their count words and of their copies
+            p.at, words, p.pinned = words, words + p.words, _Pinned(**p.shapes())
         self._d_out = torch.zeros(words, dtype=torch.int32, device=dev)
         self._h_out = torch.zeros(words, dtype=torch.int32, pin_memory=True)
-        self.selection = self.cloud = self.mesh = self.volume_images = self.hand = self.closure = None
+        self.selection = None
+        vars(self).update({t.cls.attr: None for t in PRODUCTS if t.cls is not None})      # self.cloud, .mesh, ...: the last plan's
         self.captures = 0
         self._set_example_cameras()
         self._capture()
@@ -432,10 +464,10 @@ class PlannerSession:
         rows, the volume's depth images when the session casts them, then one wait."""
         n_sel = min(int(h[0]), self.selector_params['top_k'] or self.max_grasps, self.max_grasps)
         for p in self.products:
-            p.fetch(self._out[p.out], h[p.at:p.at + p.words].tolist(), max(n_sel, 0))
+            p.pinned.fetch(p.rows(self._out[p.out], h[p.at:p.at + p.words].tolist(), max(n_sel, 0)))
         st.synchronize()
         for p in self.products:
-            setattr(self, p.attr, p.result())
+            setattr(self, p.attr, p.result(p.pinned.host(*p.kept)))
 
     def plan(self, frames_u8, extrinsics, intrinsics, depth_range=(0.2, 0.8), bbox3d=PLAN_BBOX3D, seed=None, return_volumes=False):
         """planner.plan() from raw frames: frames_u8 [V,h,w,c] uint8 (array, list of arrays, or a device tensor);

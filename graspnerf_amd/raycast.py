@@ -38,14 +38,6 @@ def depth_params(volume_depth, **more):
     return out
 
 
-def same_depth_params(a, b):
-    """Whether two depth_params results ask for the same images (b may hold further keys)."""
-    if a is None or b is None:
-        return a is None and b is None
-    same = lambda x, y: (x is None and y is None) if (x is None or y is None) else np.array_equal(x, y)
-    return all(same(a[k], b.get(k)) for k in a)
-
-
 class VolumeRaycaster(DeviceOp):
     """The depth images [B,V,h,w] of the iso-surface vol = iso of B volumes from V cameras each; with a gradient volume also the
     gradient images [B,V,h,w,3].  The output buffers are kept per shape and written again by the next call of that shape, so their

@@ -28,22 +28,10 @@ def color_params(view_colors, **more):
     return out
 
 
-def same_color_params(a, b):
-    """Whether two color_params results ask for the same colouring (b may hold further keys)."""
-    if a is None or b is None:
-        return a is None and b is None
-    return all(a[k] == b.get(k) for k in a)
-
-
 def cloud_level(rg):
     """The level below which a voxel occludes a point of the surface cloud with tsdf in rg: the middle of the range as float32 (0 for
     the real route's (-0.2, 0.2))."""
     return float(np.float32(0.5 * (float(rg[0]) + float(rg[1]))))
-
-
-def march_params(cp):
-    """color_params -> the keyword arguments of SurfaceColorizer.points / .pixels it sets."""
-    return {k: cp[k] for k in COLOR_DEFAULTS}
 
 
 class SurfaceColorizer(DeviceOp):

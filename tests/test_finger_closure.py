@@ -203,9 +203,9 @@ def test_keyword_checks():
     assert {k: p.default for k, p in inspect.signature(hand.closure_from_rows).parameters.items() if k != 'rows'} == hand.CLOSURE_PLAN_DEFAULTS
     p = hand.closure_params(dict(opening=hand.EXECUTE_GRASP_OPENING, spacing=1, bisections=2, friction=1, filter=True), filter=False)
     assert p == dict(want, opening=0.08, spacing=1.0, bisections=2, friction=1.0, filter=True) and isinstance(p['spacing'], float)
-    assert hand.same_closure_params(p, {k: v for k, v in p.items() if k != 'filter'}) and not hand.same_closure_params(p, hand.closure_params(True))
-    assert not hand.same_closure_params(p, None) and hand.same_closure_params(None, None)
-    assert set(hand.closure_device_params(p)) == set(hand.CLOSURE_DEFAULTS) and set(hand.closure_host_params(p)) == {'max_opening', 'friction'}
+    assert grasp_post.same_params(p, {k: v for k, v in p.items() if k != 'filter'}) and not grasp_post.same_params(p, hand.closure_params(True))
+    assert not grasp_post.same_params(p, None) and grasp_post.same_params(None, None)
+    assert set(grasp_post.picked(p, hand.CLOSURE_DEFAULTS)) == set(hand.CLOSURE_DEFAULTS) and set(grasp_post.picked(p, hand.CLOSURE_PLAN_DEFAULTS)) == {'max_opening', 'friction'}
     for fn, name, default in ((planner.plan_real, 'closure', False), (planner.real_session, 'closure', False),
                               (PlannerSession.__init__, 'finger_closure', None)):
         assert inspect.signature(fn).parameters[name].default is default, fn

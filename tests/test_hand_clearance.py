@@ -297,8 +297,8 @@ def test_keyword_checks():
     assert inspect.signature(hand.HandClearance.__call__).parameters['top_k'].default is None
     p = hand.hand_params(dict(opening=hand.EXECUTE_GRASP_OPENING, spacing=1, filter=True), filter=False)
     assert p == dict(want, opening=0.08, spacing=1.0, filter=True) and isinstance(p['spacing'], float)
-    assert hand.same_hand_params(p, {k: v for k, v in p.items() if k != 'filter'}) and not hand.same_hand_params(p, hand.hand_params(True))
-    assert not hand.same_hand_params(p, None) and hand.same_hand_params(None, None)
+    assert grasp_post.same_params(p, {k: v for k, v in p.items() if k != 'filter'}) and not grasp_post.same_params(p, hand.hand_params(True))
+    assert not grasp_post.same_params(p, None) and grasp_post.same_params(None, None)
     assert hand.checked_hand()['opening'] == -1.0 and hand.checked_hand(opening=0.0)['opening'] == 0.0
     for fn, name, default in ((planner.plan_real, 'clearance', False), (planner.real_session, 'clearance', False),
                               (PlannerSession.__init__, 'hand_clearance', None)):
@@ -307,7 +307,7 @@ def test_keyword_checks():
     net = object()
     built = lambda hc: types.SimpleNamespace(net=net, selector_params=dict(GRASP_UTILS_PROCESS, order='index', top_k=None), surface_params=dict(rg=(-0.2, 0.2)),
                                              voxel_size=planner.REAL_VOXEL_SIZE, surface_normals=False, mesh_params=None, volume_depth_params=None,
-                                             view_color_params=None, hand_params=hand.hand_params(hc))
+                                             view_color_params=None, hand_params=hand.hand_params(hc), closure_params=None)
     for have, ask in ((False, True), (True, False), (True, dict(approach=0.0)), (dict(level=0.5), True)):
         with pytest.raises(ValueError, match=r'the session was built for another clearance \(build it with planner.real_session'):
             planner.plan_real(net, frames, cams, np.eye(3), session=built(have), clearance=ask)

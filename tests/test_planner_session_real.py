@@ -136,6 +136,47 @@ def test_every_product_in_one_graph(ctx):
     assert not same(eA[2], eB[2]) and not same(eA[3]['volume_depth'], eB[3]['volume_depth'])
 
 
+def test_all_six_switches_in_one_graph(ctx):
+    """Every product of the table at once -- clearance, closure, cloud with normals, mesh, depth images, each of the last three coloured
+    from the views -- in ONE session against the eager plan_real with the same keywords: the first and third plan are bitwise the eager
+    plan of A, the one between them that of B.  No count word but the cloud's and the mesh's two; the products in the table's order."""
+    net, cam, A, B, rg, iso = (ctx[k] for k in ('net', 'cam', 'A', 'B', 'rg', 'iso'))
+    kw = dict(order='score', top_k=TOP_K, surface_rg=rg, normals=True, mesh=dict(iso=iso), volume_depth=dict(iso=iso), view_colors=True,
+              clearance=dict(level=iso), closure=dict(level=iso, friction=0.5))
+    sess = planner.real_session(net, V, HW, HW[::-1], max_grasps=MAX_GRASPS, **kw)
+    assert sess.captures == 1 and sess._d_out.numel() == 1 + 9 * MAX_GRASPS + 1 + 2
+    assert [p.out for p in sess.products] == ['hand', 'closure', 'surface', 'mesh', 'volume_depth']
+    eA, eB = planner.plan_real(net, A, **cam, **kw), planner.plan_real(net, B, **cam, **kw)
+    g, cloud = eA[0], eA[3]
+    assert len(cloud['index']) > 100 and len(cloud['mesh']['faces']) > 100 and (cloud['volume_depth'] > 0).sum() > 100, \
+        'the level set is too small to show anything'
+    assert (g['finger_contact'] >= 0).any(), 'no finger touches anything: the closure columns show nothing'
+    print(f'{len(cloud["index"])} cloud rows, {len(cloud["mesh"]["faces"])} faces, {(cloud["volume_depth"] > 0).sum()} pixels hit, '
+          f'{(g["finger_contact"] >= 0).sum()} finger contacts; coloured: {(cloud["view_weight"] > 0).sum()} rows, '
+          f'{(cloud["mesh"]["view_weight"] > 0).sum()} vertices, {(cloud["volume_color_weight"] > 0).sum()} pixels')
+    hand_keys = {'clearance', 'approach_clearance', 'hand_inside', 'hand_worst', 'collision_free'}
+    closure_keys = {'closed_width', 'finger_travel', 'finger_contact', 'contact_cos', 'grip_cos', 'held', 'force_closure'}
+    assert set(g) == {'index', 'pos', 'quat', 'width', 'score'} | hand_keys | closure_keys
+    view_keys = ['view_colors', 'view_mask', 'view_weight']
+    images = ['volume_color', 'volume_color_weight', 'volume_depth', 'volume_depth_normals']
+    assert sorted(cloud) == sorted(['index', 'points', 'colors', 'gradient', 'normals', 'mesh', *view_keys, *images])
+    assert sorted(cloud['mesh']) == sorted(['vertices', 'faces', 'gradient', 'normals', *view_keys])
+    plans = [planner.plan_real(net, f, **cam, **kw, session=sess) for f in (A, B, A)]
+    assert sess.captures == 1
+    for what, got, want in (('A', plans[0], eA), ('B', plans[1], eB), ('A, second replay', plans[2], eA)):
+        _equal_plans(got, want, what)
+        assert sorted(got[0]) == sorted(want[0]), what
+        for k in want[0]:
+            assert same(got[0][k], want[0][k]), (what, 'grasps', k)
+        assert sorted(got[3]) == sorted([*want[3], 'count']), what                        # (a session's cloud also says its row count)
+        for k in set(want[3]) - {'mesh'}:
+            assert same(got[3][k], want[3][k]), (what, 'cloud', k)
+        assert sorted(got[3]['mesh']) == sorted(want[3]['mesh']), what
+        for k in want[3]['mesh']:
+            assert same(got[3]['mesh'][k], want[3]['mesh'][k]), (what, 'mesh', k)
+    assert not same(eA[2], eB[2]) and not same(eA[3]['volume_color'], eB[3]['volume_color'])
+
+
 def test_session_without_the_new_arguments_is_todays_session(ctx):
     """No surface, no ranking: the packed read-back has today's size, the graph's outputs today's names, and the plan the bits of the
     original select call on the session's own volumes."""

@@ -277,8 +277,8 @@ def test_keyword_checks():
     assert p == dict(step=1.0, bias=1.5, cos_min=0.0, fill=(0.25, 0.5, 0.75)) and isinstance(p['step'], float)
     with pytest.raises(ValueError, match='three numbers'):
         surface_color.color_params(dict(fill=(0, 0)))
-    assert surface_color.same_color_params(p, dict(p, origin=(0, 0, 0))) and not surface_color.same_color_params(p, surface_color.color_params(True))
-    assert not surface_color.same_color_params(p, None) and surface_color.same_color_params(None, None)
+    assert planner.same_params(p, dict(p, origin=(0, 0, 0))) and not planner.same_params(p, surface_color.color_params(True))
+    assert not planner.same_params(p, None) and planner.same_params(None, None)
     assert surface_color.cloud_level((-0.2, 0.2)) == 0.0 and surface_color.cloud_level((0.25, 0.5)) == 0.375
     for fn, default in ((planner.plan_real, False), (planner.real_session, False), (PlannerSession.__init__, None)):
         assert inspect.signature(fn).parameters['view_colors'].default is default, fn
@@ -286,7 +286,8 @@ def test_keyword_checks():
     net = object()
     built = lambda vc: types.SimpleNamespace(net=net, selector_params=dict(GRASP_UTILS_PROCESS, order='index', top_k=None), surface_params=dict(rg=(-0.2, 0.2)),
                                              voxel_size=planner.REAL_VOXEL_SIZE, surface_normals=False, mesh_params=None, volume_depth_params=None,
-                                             view_color_params=surface_color.color_params(vc, origin=(0.0, 0.0, 0.0)))
+                                             view_color_params=surface_color.color_params(vc, origin=(0.0, 0.0, 0.0)), hand_params=None,
+                                             closure_params=None)
     for have, ask in ((False, True), (True, False), (True, dict(bias=2.0))):
         with pytest.raises(ValueError, match=r'the session was built for another .*volume_depth or view_colors \(build it with planner.real_session\)'):
             planner.plan_real(net, frames, cams, np.eye(3), session=built(have), view_colors=ask)

@@ -397,11 +397,11 @@ def test_graph_capture_and_replay(batch16):
 
 # ---- the real-robot route --------------------------------------------------------------------------------------------------------
 def test_session_arguments_are_checked_before_anything_is_built():
-    from graspnerf_amd import planner
+    from graspnerf_amd import grasp_post
     with pytest.raises(TypeError, match='unknown mesh parameters'):
-        planner._mesh_params(dict(level=0.0))
-    assert planner._mesh_params(False) is None and planner._mesh_params(True) == dict(iso=0.0, max_vertices=None, max_faces=None)
-    assert planner._mesh_params(dict(iso=0.25, max_faces=7)) == dict(iso=0.25, max_vertices=None, max_faces=7)
+        grasp_post.mesh_params(dict(level=0.0))
+    assert grasp_post.mesh_params(False) is None and grasp_post.mesh_params(True) == dict(iso=0.0, max_vertices=None, max_faces=None)
+    assert grasp_post.mesh_params(dict(iso=0.25, max_faces=7)) == dict(iso=0.25, max_vertices=None, max_faces=7)
 
 
 @pytest.mark.gpu

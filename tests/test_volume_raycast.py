@@ -257,8 +257,8 @@ def test_keyword_checks(monkeypatch):
     assert planner._depth_params(True) == dict(extrinsics=None, intrinsic=None, hw=None, iso=0.0, step=0.5, bisections=4)
     p = planner._depth_params(dict(extrinsics=[np.eye(4)] * 2, intrinsic=np.eye(3), hw=[5, 7], iso=0.25))
     assert p['extrinsics'].shape == (2, 3, 4) and p['extrinsics'].dtype == f32 and p['hw'] == (5, 7) and p['iso'] == 0.25
-    assert planner._same_depth_params(p, dict(p, origin=(0, 0, 0))) and not planner._same_depth_params(p, planner._depth_params(True))
-    assert not planner._same_depth_params(p, None) and planner._same_depth_params(None, None)
+    assert planner.same_params(p, dict(p, origin=(0, 0, 0))) and not planner.same_params(p, planner._depth_params(True))
+    assert not planner.same_params(p, None) and planner.same_params(None, None)
     assert inspect.signature(PlannerSession.__init__).parameters['volume_depth'].default is None
     # Validator(volume_depth=False): the keys of today
     monkeypatch.setattr(trainer_mod, 'train_losses', stub_losses)
