@@ -19,7 +19,8 @@
 // output is a pure function of the input bits.  Everything is float64, every operation one correctly rounded IEEE operation in the
 // order written here (contraction is off for the whole file).
 // The second kernel of the file, k_finger_closure (further down, with its own notes), closes the fingers of the same hand on the
-// volume; the two share the opening, the pose, the placement of a local point and the launch shape.
+// volume; the two share the opening, the pose, the placement of a local point and the launch shape.  The third, k_grasp_objects
+// (gnr_grasp_objects_fwd), shares them too: it reads gnr_objects.hip's label volume at the samples between the pads.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -308,6 +309,72 @@ __global__ __launch_bounds__(256) void k_finger_closure(const float* __restrict_
     }
 }
 
+// ---- which object a grasp closes on ----------------------------------------------------------------------------------------------------
+// Per grasp: the samples of one box, the closing region between the pads, vote for the label (gnr_volume_objects_fwd's) at their
+// nearest voxel.  Mapping and rows: k_hand_clearance's.  No histogram is kept: pass after pass, the lanes stride over the samples and
+// find the smallest label above the last pass's and its votes (a min and two sums over the lanes), so the labels are met in ascending
+// order and a strict `>` keeps the smaller of two labels with equal votes.  One pass per different label and one that finds none: two
+// or three for a hand between objects; the bound is the number of samples.  Integers throughout, any order of the lanes.
+__global__ __launch_bounds__(256) void k_grasp_objects(const int* __restrict__ labels, const double* __restrict__ pos,
+                                                       const float* __restrict__ quat, const float* __restrict__ width,
+                                                       const int* __restrict__ count, int* __restrict__ object, int* __restrict__ votes,
+                                                       int* __restrict__ distinct, int* __restrict__ inside, Shape sh) {
+    const int R = sh.R, b = blockIdx.y;
+    const int* lab = labels + (size_t)b * R * R * R;
+    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const double top = (double)(R - 1);
+    const int n = count[(size_t)b * sh.count_stride];
+    const int rows = n < sh.rows ? n : sh.rows;                   // (a negative count: no row)
+    for (unsigned blk = blockIdx.x; blk < sh.blocks; blk += gridDim.x) {
+        const unsigned r = blk * 4u + wave;
+        if (rows <= 0 || r >= (unsigned)rows) continue;           // wave-uniform: rows beyond the count are left untouched
+        const size_t o = (size_t)b * sh.max_n + r;
+        const double w = width_of(sh, width[o]);
+        const double lo[3] = {-0.5 * sh.height, -(0.5 * w), 0.0}, ext[3] = {sh.height, w, sh.depth};
+        double step[3];
+        int nn[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double na = count_of(ext[a], sh.cell);
+            step[a] = ext[a] / (na - 1.0);
+            nn[a] = (int)na;
+        }
+        const int nyz = nn[1] * nn[2], total = nn[0] * nyz;
+        double M[3][3], g[3];
+        pose_of(quat + o * 4, pos + o * 3, M, g);
+        int cur = 0, best = 0, most = 0, kinds = 0, in = 0;
+        for (int pass = 0; pass <= total; ++pass) {
+            int mn = INT32_MAX, cnt = 0, taken = 0;               // the smallest label above `cur` this lane met, its votes, the samples taken
+            for (int s = (int)lane; s < total; s += 64) {
+                const int ix = s / nyz, rem = s - ix * nyz;
+                const int iy = rem / nn[2], iz = rem - iy * nn[2];
+                double p[3];
+                place(M, g, sh.scale, lo[0] + (double)ix * step[0], lo[1] + (double)iy * step[1], lo[2] + (double)iz * step[2], p);
+                if (!within(p, top)) continue;
+                taken += 1;
+                const int vi = (int)floor(p[0] + 0.5), vj = (int)floor(p[1] + 0.5), vk = (int)floor(p[2] + 0.5);   // in 0 .. R-1
+                const int L = lab[((size_t)vi * R + vj) * R + vk];
+                if (L > cur) {
+                    if (L < mn) { mn = L; cnt = 1; }
+                    else if (L == mn) cnt += 1;
+                }
+            }
+            int low = mn;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) { const int ol = __shfl_xor(low, d); low = ol < low ? ol : low; }
+            int c = mn == low ? cnt : 0;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) { c += __shfl_xor(c, d); taken += __shfl_xor(taken, d); }
+            if (pass == 0) in = taken;
+            if (low == INT32_MAX) break;                          // (the same in every lane)
+            kinds += 1;
+            if (c > most) { best = low; most = c; }
+            cur = low;
+        }
+        if (lane == 0) { object[o] = best; votes[o] = most; distinct[o] = kinds; inside[o] = in; }
+    }
+}
+
 }  // namespace gnr_hand
 
 using namespace gnr_hand;
@@ -380,4 +447,19 @@ extern "C" int gnr_finger_closure_fwd(const GnrHandParams* p, double level, int 
     const Closure cl{level, bisections};
     return launch<k_finger_closure>("k_finger_closure@gnr_finger_closure_fwd", (hipStream_t)stream, grid_of(sh, B), dim3(256), 0, vol, pos, quat,
                                     width, count, travel, cosine, contact, closed, sh, cl);
+}
+
+extern "C" int gnr_grasp_objects_fwd(const GnrHandParams* p, const int* labels, const double* pos, const float* quat, const float* width,
+                                     const int* count, int count_stride, int B, int R, int max_n, int top_k, int* object, int* votes,
+                                     int* distinct, int* inside, void* stream) {
+    const char* fn = "gnr_grasp_objects_fwd";
+    Shape sh;
+    if (int rc = shape_of(fn, p, labels && pos && quat && width && count && object && votes && distinct && inside, count_stride, B, R, max_n, top_k, sh))
+        return rc;
+    // the samples of the widest hand, R voxels: the device's counts, as doubles before any cast
+    const double most = count_of(p->height, sh.cell) * count_of((double)R * p->scale, sh.cell) * count_of(p->depth, sh.cell);
+    if (!(most <= (double)GNR_HAND_MAX_SAMPLES))
+        return refuse(fn, GNR_ERR_ARG, "spacing too small, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) samples");
+    return launch<k_grasp_objects>("k_grasp_objects@gnr_grasp_objects_fwd", (hipStream_t)stream, grid_of(sh, B), dim3(256), 0, labels, pos, quat,
+                                   width, count, object, votes, distinct, inside, sh);
 }

@@ -99,12 +99,14 @@ class _GraspRows(DeviceOp):
         super().__init__(device, self.NOUN)
         self._out = {}
 
+    _batch = staticmethod(volume_batch)                      # what the rows are checked against (objects.GraspObjects: a label volume)
+
     def _checked(self, vol, pos, quat, width, count, scale, top_k, *hand):
         """The arguments both kernels take (hand: checked_hand's, in its order), checked -> (GnrHandParams, vol, pos, quat, width, B, R, n,
         this shape's output tensors)."""
         d = self.device
         hand = checked_hand(*hand)
-        vol, B, R = volume_batch(vol, d)
+        vol, B, R = self._batch(vol, d)
         pos, quat, width, n = checked_rows(pos, quat, width, count, top_k, B, d)
         out = self._out.get((B, n))
         if out is None:

@@ -882,6 +882,67 @@ int gnr_finger_closure_fwd(const GnrHandParams* params, double level, int bisect
                            float* travel /*[B,max_n,2]*/, float* cosine /*[B,max_n,2]*/, int* contact /*[B,max_n,2]*/,
                            float* closed /*[B,max_n]*/, void* stream);
 
+/* gnr_volume_objects_fwd: the objects of B volumes [B,R,R,R] -- connected-component labelling of their solid voxels, per component
+ * its size, box and coordinate sums, and a copy of the volume with the small components set to free.  What the reference asks its
+ * simulator (`while sim.num_objects > 0`, src/gd/experiments/clutter_removal.py:92), answered from the volume.  No reference
+ * counterpart; tests/objects_reference.py is the same statement over scipy.ndimage.label and the call produces its bits.  Nothing is
+ * floating-point beyond the threshold compare.
+ *   lattice    voxel (i,j,k) of scene b sits at ((b*R + i)*R + j)*R + k; k is the world z of the plan's frame, as in gnr_tsdf_*.
+ *   solid      lower < (double)v && (double)v < level && k >= z_min, v the voxel's value: a NaN is not solid.
+ *   labels     a voxel that is not solid gets 0.  Two solid voxels of one scene are neighbours when their index difference
+ *              (di, dj, dk), each in -1..1 and not all 0, has at most 1 (connectivity 6), 2 (18) or 3 (26) non-zero components:
+ *              scipy's generate_binary_structure(3, 1 | 2 | 3).  Scenes never join, and neither do the ends of two rows (the
+ *              neighbours of a voxel at a face of the lattice are those inside).  A component's label is 1 + the number of components
+ *              of its scene whose smallest linear index is smaller: ndimage.label's numbering.  count[b] is the number of components,
+ *              the true number even when it exceeds max_objects; the labels are always complete and do not depend on max_objects.
+ *   statistics every call first writes rows 0 .. max_objects-1: voxels 0, bbox (R,R,R,-1,-1,-1), sums 0; then, for the labels
+ *              1 .. min(count, max_objects), at row label-1: voxels = the component's voxels, bbox = the smallest and the largest i, j, k
+ *              (inclusive), sums = the sums of its voxels' i, j and k.  Integer atomics only: any order gives the same bits.
+ *   cleaned    (when not NULL) free_value at every voxel of a component with fewer than min_voxels voxels -- of every component,
+ *              also those beyond max_objects --, vol's value elsewhere.
+ *   workspace  at least gnr_volume_objects_workspace_bytes(B, R) (0 for a B or R outside the limits).  Its first int is the status
+ *              word of the call, valid once the stream has run it: 0, or GNR_OBJECTS_STATUS_BOUND when a loop of the labelling ran into
+ *              its bound (R^3 links of a chain, R^3 retries of a union; it never spins on) -- the results are then not to be used.
+ *              Everything a call reads from its workspace it has written in that call; nothing is kept between calls.
+ * 1 <= B <= 65535, 2 <= R <= 256; connectivity 6, 18 or 26; max_objects >= 1; 0 <= z_min <= R; level finite; lower not a NaN;
+ * free_value finite.  Asynchronous on `stream`, no allocation, no synchronisation, no float atomics (it can be captured in a graph and
+ * replayed); a refused call has launched nothing.                                                                              */
+#define GNR_OBJECTS_STATUS_BOUND 1
+typedef struct GnrObjectsParams {
+    double level;        /* solid: lower < (double)v && (double)v < level; a NaN is not solid.  0.0 for the network's tsdf      */
+    double lower;        /* -inf: none.  (-1 keeps out a label volume's "unknown")                                             */
+    int    z_min;        /* voxels with k < z_min are not solid (cuts the table slab, on which every object stands); 0: none   */
+    int    connectivity; /* 6, 18 or 26: scipy's generate_binary_structure(3, 1 | 2 | 3)                                       */
+    int    max_objects;  /* rows of the statistics                                                                             */
+    int    min_voxels;   /* for `cleaned`: components with fewer voxels become free_value; <= 1: nothing is removed            */
+    float  free_value;   /* 1.0f, the volume's upper clip                                                                      */
+} GnrObjectsParams;
+size_t gnr_volume_objects_workspace_bytes(int B, int R);
+int gnr_volume_objects_fwd(const GnrObjectsParams* params, const float* vol /*[B,R,R,R]*/, int B, int R, int* labels /*[B,R,R,R]*/,
+                           int* count /*[B]*/, int* voxels /*[B,max_objects]*/,
+                           int* bbox /*[B,max_objects,6]: lo i,j,k, hi i,j,k (inclusive)*/,
+                           unsigned long long* sums /*[B,max_objects,3]: sum of i, j, k*/, float* cleaned /*[B,R,R,R] or NULL*/,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* gnr_grasp_objects_fwd: which object each ranked grasp would close on -- the samples of the closing region between the pads of
+ * gnr_hand_clearance_fwd's hand vote for the label (gnr_volume_objects_fwd's) at their nearest voxel.  The frame, `width`, `pose`,
+ * `position` and `rows` are gnr_hand_clearance_fwd's, word for word, as is cell = spacing * scale; finger_width, tail_length and approach
+ * are checked and not used.  tests/objects_reference.py is the same statement in numpy and the call produces its bits.
+ *   samples    gnr_hand_clearance_fwd's `samples` rule applied to one box, as (lo, extent): x (-0.5 h, h), y (-hw, w), z (0, d); no
+ *              approach continuation (m = 0).
+ *   votes      a sample with a component outside [0, R-1] (or not a number) is skipped.  The others vote for the label at voxel
+ *              ((int)floor(p_x + 0.5), (int)floor(p_y + 0.5), (int)floor(p_z + 0.5)); label 0 (and anything below) casts no vote.
+ *   result     inside = the samples taken;  distinct = the number of different labels voted for;  object = the label with the most
+ *              votes, of several the smallest, 0 when there is none;  votes = that label's votes.  Integers throughout, any order.
+ * The limits of gnr_hand_clearance_fwd, refused with its texts; n_x n_y n_z of a grasp whose width is R voxels must be at most
+ * GNR_HAND_MAX_SAMPLES.  Every loop is bounded by the parameters (one pass over the samples per different label, at most as many
+ * passes as samples).  Asynchronous on `stream`, no atomics, no workspace, no allocation, no synchronisation (it can be captured in
+ * a graph); a refused call has launched nothing.                                                                               */
+int gnr_grasp_objects_fwd(const GnrHandParams* hand, const int* labels /*[B,R,R,R]*/, const double* pos /*[B,max_n,3]*/,
+                          const float* quat /*[B,max_n,4]*/, const float* width /*[B,max_n], voxels*/, const int* count /*[B * count_stride]*/,
+                          int count_stride, int B, int R, int max_n, int top_k, int* object /*[B,max_n]*/, int* votes /*[B,max_n]*/,
+                          int* distinct /*[B,max_n]*/, int* inside /*[B,max_n]*/, void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
