@@ -109,6 +109,10 @@ class GnrObjectsParams(C.Structure):
                 ('min_voxels', C.c_int), ('free_value', C.c_float)]
 
 
+class GnrDistanceParams(C.Structure):
+    _fields_ = [('level', C.c_double), ('lower', C.c_double), ('scale', C.c_double), ('surface_offset', C.c_double), ('z_min', C.c_int)]
+
+
 class GnrError(RuntimeError):
     pass
 
@@ -309,6 +313,11 @@ def lib():
     L.gnr_volume_objects_fwd.restype = C.c_int
     L.gnr_grasp_objects_fwd.argtypes = [C.POINTER(GnrHandParams)] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 5
     L.gnr_grasp_objects_fwd.restype = C.c_int
+    L.gnr_volume_distance_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    L.gnr_volume_distance_workspace_bytes.restype = C.c_size_t
+    L.gnr_volume_distance_fwd.argtypes = [C.POINTER(GnrDistanceParams), C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + \
+                                         [C.c_void_p, C.c_size_t, C.c_void_p]
+    L.gnr_volume_distance_fwd.restype = C.c_int
     L.gnr_tsdf_reset.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnr_tsdf_reset.restype = C.c_int
     L.gnr_tsdf_integrate.argtypes = [C.POINTER(GnrTsdfParams)] + [C.c_void_p] * 7
@@ -375,6 +384,7 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid', 'gnr_surface_mesh_workspace_bytes', 'gnr_surface_mesh_fwd',
             'gnr_volume_raycast_fwd', 'gnr_surface_color_points_fwd', 'gnr_surface_color_pixels_fwd', 'gnr_hand_clearance_fwd', 'gnr_finger_closure_fwd',
             'gnr_volume_objects_workspace_bytes', 'gnr_volume_objects_fwd', 'gnr_grasp_objects_fwd',
+            'gnr_volume_distance_workspace_bytes', 'gnr_volume_distance_fwd',
             'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 

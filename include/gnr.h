@@ -943,6 +943,47 @@ int gnr_grasp_objects_fwd(const GnrHandParams* hand, const int* labels /*[B,R,R,
                           int count_stride, int B, int R, int max_n, int top_k, int* object /*[B,max_n]*/, int* votes /*[B,max_n]*/,
                           int* distinct /*[B,max_n]*/, int* inside /*[B,max_n]*/, void* stream);
 
+/* gnr_volume_distance_fwd: the distance field of B volumes [B,R,R,R] -- the exact Euclidean distance transform of their solid mask:
+ * per voxel the squared distance to the nearest solid voxel and that voxel, the same to the nearest free voxel, the signed metric
+ * field made of the two, and the object (gnr_volume_objects_fwd's label) the nearest solid voxel belongs to.  The volume itself is a
+ * truncated field, metric only within a few voxels of a surface; this one is metric everywhere, and every operator that takes a
+ * volume (gnr_hand_clearance_fwd above all: by how much the hand misses) takes `esdf` as it is.  No reference counterpart;
+ * tests/distance_reference.py is the same statement over scipy.ndimage.distance_transform_edt and the call produces its bits.
+ *   lattice    gnr_volume_objects_fwd's: voxel (i,j,k) of scene b sits at ((b*R + i)*R + j)*R + k.
+ *   solid      gnr_volume_objects_fwd's rule: lower < (double)v && (double)v < level && k >= z_min; a NaN is not solid.  Every
+ *              other voxel is free.
+ *   d2_solid   min over the solid voxels (i',j',k') of the SAME scene of (i-i')^2 + (j-j')^2 + (k-k')^2, an integer: 0 at a solid
+ *              voxel.  A scene without a solid voxel: 3 R R everywhere (above every real value, 3 (R-1)^2).
+ *   nearest_solid  the voxel that attains it, as i' R R + j' R + k' inside its scene; of several the one with the smallest such
+ *              index.  A scene without a solid voxel: -1.
+ *   d2_free, nearest_free  (both or neither) the same over the free voxels.
+ *   esdf       (when not NULL; the free pair is then computed whether it is returned or not) in float64, single correctly rounded
+ *              operations in this order:  t = sqrt((double)d2);  t = t - surface_offset;  t = t * scale;  with d2 = d2_solid at a
+ *              free voxel, and d2 = d2_free and t = -t at a solid one;  esdf = (float)t.  With surface_offset = 0.5 the surface lies
+ *              halfway between a solid voxel and its free neighbour, which read -0.5 and +0.5 voxels.
+ *   nearest_label  (when not NULL; needs labels [B,R,R,R], gnr_volume_objects_fwd's) labels[b, nearest_solid], 0 where
+ *              nearest_solid is -1.  0 also when the nearest solid voxel carries no label (a table slab the labelling cut by z_min).
+ *   workspace  at least gnr_volume_distance_workspace_bytes(B, R) (0 for a B or R outside the limits).  Everything a call reads
+ *              from it it has written in that call; nothing is kept between calls.
+ * Three line passes (along k, j, i), each min over x' of g[x'] + (x - x')^2 with the smaller x' winning a tie, which leaves the
+ * smallest linear index among the nearest voxels.  Every output is fully written.  1 <= B <= 65535, 2 <= R <= 256; 0 <= z_min <= R;
+ * level finite; lower not a NaN; scale finite and > 0; surface_offset finite and >= 0; these, a null required pointer, nearest_label
+ * without labels and one of the free pair without the other are refused with GNR_ERR_ARG, a workspace too small with
+ * GNR_ERR_WORKSPACE.  Asynchronous on `stream`, no atomics, no allocation, no synchronisation, every loop bounded by R (it can be
+ * captured in a graph and replayed); a refused call has launched nothing.                                                       */
+typedef struct GnrDistanceParams {
+    double level;           /* solid: lower < (double)v && (double)v < level; a NaN is not solid.  0.0 for the network's tsdf   */
+    double lower;           /* -inf: none                                                                                       */
+    double scale;           /* metres per voxel                                                                                 */
+    double surface_offset;  /* voxels taken off every distance: 0.5 puts the surface between a solid voxel and its free neighbour */
+    int    z_min;           /* voxels with k < z_min are not solid; 0: none                                                     */
+} GnrDistanceParams;
+size_t gnr_volume_distance_workspace_bytes(int B, int R);
+int gnr_volume_distance_fwd(const GnrDistanceParams* params, const float* vol /*[B,R,R,R]*/, const int* labels /*[B,R,R,R] or NULL*/,
+                            int B, int R, int* d2_solid /*[B,R,R,R]*/, int* nearest_solid /*[B,R,R,R]*/, int* d2_free /*[B,R,R,R] or NULL*/,
+                            int* nearest_free /*[B,R,R,R] or NULL*/, float* esdf /*[B,R,R,R] or NULL*/,
+                            int* nearest_label /*[B,R,R,R] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
