@@ -26,9 +26,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "gnr_host.h"
+#include "gnr_solid.h"
 
 #pragma clang fp contract(off)
 
@@ -47,12 +47,6 @@ struct Shape {
 };
 struct Out { int* p[2]; };                     // per transform: 0 to the solid voxels, 1 to the free ones
 struct In { const int* p[2]; };
-
-// gnr_volume_objects_fwd's rule (gnr_objects.hip, solid_at)
-__device__ inline bool solid_at(const Shape& sh, float v, int k) {
-    const double x = (double)v;
-    return sh.lower < x && x < sh.level && k >= sh.z_min;
-}
 
 // launch grid: (ceil(R^2 / 32), B, transforms), 256 threads
 __global__ __launch_bounds__(256) void k_line_k(const float* __restrict__ vol, Out site_out, Shape sh) {
@@ -148,23 +142,17 @@ __global__ __launch_bounds__(256) void k_field(const float* __restrict__ vol, co
     }
 }
 
-static int refuse(const char* fn, int code, const char* what) {
-    char text[200];
-    snprintf(text, sizeof text, "%s: %s", fn, what);
-    return fail(code, text);
-}
-
 // the workspace: per transform the sites of the pass along k, then the values and the sites of the pass along j.  The pass along i
 // writes a free pair the caller did not ask for over the two site arrays of the pass along k, which nothing reads any more.
-struct Layout { size_t site_k[2], val_j[2], site_j[2], total; };
+struct Work { Out site_k, val_j, site_j; size_t total; };
 
-static Layout layout_of(int B, int R) {
-    const size_t bytes = al256((size_t)B * R * R * R * sizeof(int));
-    Layout l;
-    size_t at = 0;
-    for (int t = 0; t < 2; ++t) { l.site_k[t] = at; at += bytes; l.val_j[t] = at; at += bytes; l.site_j[t] = at; at += bytes; }
-    l.total = at;
-    return l;
+static Work carve(int B, int R, void* base) {
+    const size_t n = (size_t)B * R * R * R;
+    Carve c(base);
+    Work k;
+    for (int t = 0; t < 2; ++t) { k.site_k.p[t] = c.take<int>(n); k.val_j.p[t] = c.take<int>(n); k.site_j.p[t] = c.take<int>(n); }
+    k.total = c.total();
+    return k;
 }
 
 }  // namespace gnr_distance
@@ -172,42 +160,35 @@ static Layout layout_of(int B, int R) {
 using namespace gnr_distance;
 
 extern "C" size_t gnr_volume_distance_workspace_bytes(int B, int R) {
-    if (B < 1 || B > 65535 || R < 2 || R > 256) return 0;
-    return layout_of(B, R).total;
+    return scenes_ok(B) && lattice_ok(R) ? carve(B, R, nullptr).total : 0;
 }
 
 extern "C" int gnr_volume_distance_fwd(const GnrDistanceParams* p, const float* vol, const int* labels, int B, int R, int* d2_solid,
                                        int* nearest_solid, int* d2_free, int* nearest_free, float* esdf, int* nearest_label, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    const char* fn = "gnr_volume_distance_fwd";
-    auto no = [&](int code, const char* what) { return refuse(fn, code, what); };
+    const Refuse no{"gnr_volume_distance_fwd"};
     if (!p || !vol || !d2_solid || !nearest_solid || !workspace) return no(GNR_ERR_ARG, "null pointer");
-    if (B < 1 || B > 65535) return no(GNR_ERR_ARG, "B must be in 1..65535");
-    if (R < 2 || R > 256) return no(GNR_ERR_ARG, "R must be in 2..256");
-    if (p->z_min < 0 || p->z_min > R) return no(GNR_ERR_ARG, "z_min must be in 0..R");
-    if (!isfinite(p->level)) return no(GNR_ERR_ARG, "level must be finite");
-    if (isnan(p->lower)) return no(GNR_ERR_ARG, "lower must not be a NaN (-inf: none)");
+    if (int rc = check_scenes(no, GNR_ERR_ARG, B)) return rc;         // GNR_ERR_ARG where the siblings say GNR_ERR_SHAPE: the tests pin it
+    if (int rc = check_lattice(no, GNR_ERR_ARG, R)) return rc;
+    if (int rc = check_solid(no, p->level, p->lower, p->z_min, R)) return rc;
     if (!(isfinite(p->scale) && p->scale > 0)) return no(GNR_ERR_ARG, "scale must be finite and > 0");
     if (!(isfinite(p->surface_offset) && p->surface_offset >= 0)) return no(GNR_ERR_ARG, "surface_offset must be finite and >= 0");
     if (nearest_label && !labels) return no(GNR_ERR_ARG, "nearest_label needs labels");
     if (!d2_free != !nearest_free) return no(GNR_ERR_ARG, "d2_free and nearest_free go together");
-    const Layout l = layout_of(B, R);
-    if (workspace_bytes < l.total) return no(GNR_ERR_WORKSPACE, "workspace too small");
+    const Work k = carve(B, R, workspace);
+    if (workspace_bytes < k.total) return no(GNR_ERR_WORKSPACE, "workspace too small");
     Shape sh{};
     sh.R = R; sh.n = R * R * R; sh.cols = R * R;
     sh.z_min = p->z_min; sh.level = p->level; sh.lower = p->lower; sh.scale = p->scale; sh.offset = p->surface_offset;
-    char* ws = (char*)workspace;
-    auto at = [&](size_t o) { return (int*)(ws + o); };
     const unsigned transforms = d2_free || esdf ? 2u : 1u;
-    if (!d2_free) { d2_free = at(l.site_k[0]); nearest_free = at(l.site_k[1]); }   // (read by k_field alone, and only with esdf)
-    const Out site_k{{at(l.site_k[0]), at(l.site_k[1])}}, val_j{{at(l.val_j[0]), at(l.val_j[1])}}, site_j{{at(l.site_j[0]), at(l.site_j[1])}};
+    if (!d2_free) { d2_free = k.site_k.p[0]; nearest_free = k.site_k.p[1]; }       // (read by k_field alone, and only with esdf)
     const Out d2{{d2_solid, d2_free}}, nearest{{nearest_solid, nearest_free}};
     auto in = [](const Out& o) { return In{{o.p[0], o.p[1]}}; };
     hipStream_t st = (hipStream_t)stream;
     const dim3 lines((unsigned)((sh.cols + KT - 1) / KT), (unsigned)B, transforms);
-    if (int rc = launch<k_line_k>("k_line_k@gnr_volume_distance_fwd", st, lines, dim3(256), 0, vol, site_k, sh)) return rc;
-    if (int rc = launch<k_line<1>>("k_line_j@gnr_volume_distance_fwd", st, lines, dim3(256), 0, In{{nullptr, nullptr}}, in(site_k), val_j, site_j, sh)) return rc;
-    if (int rc = launch<k_line<2>>("k_line_i@gnr_volume_distance_fwd", st, lines, dim3(256), 0, in(val_j), in(site_j), d2, nearest, sh)) return rc;
+    if (int rc = launch<k_line_k>("k_line_k@gnr_volume_distance_fwd", st, lines, dim3(256), 0, vol, k.site_k, sh)) return rc;
+    if (int rc = launch<k_line<1>>("k_line_j@gnr_volume_distance_fwd", st, lines, dim3(256), 0, In{{nullptr, nullptr}}, in(k.site_k), k.val_j, k.site_j, sh)) return rc;
+    if (int rc = launch<k_line<2>>("k_line_i@gnr_volume_distance_fwd", st, lines, dim3(256), 0, in(k.val_j), in(k.site_j), d2, nearest, sh)) return rc;
     if (!esdf && !nearest_label) return GNR_OK;
     return launch<k_field>("k_field@gnr_volume_distance_fwd", st, dim3((unsigned)((sh.n + 255) / 256), (unsigned)B), dim3(256), 0, vol,
                            (const int*)d2_solid, (const int*)d2_free, (const int*)nearest_solid, labels, esdf, nearest_label, sh);

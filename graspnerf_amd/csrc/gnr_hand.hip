@@ -380,17 +380,10 @@ __global__ __launch_bounds__(256) void k_grasp_objects(const int* __restrict__ l
 using namespace gnr_hand;
 
 // The refusals the two entry points share, in one order and one text each, and the shape of the launch.  `pointers`: none is null.
-static int refuse(const char* fn, int code, const char* what) {
-    char text[200];
-    snprintf(text, sizeof text, "%s: %s", fn, what);
-    return fail(code, text);
-}
-
-static int shape_of(const char* fn, const GnrHandParams* p, bool pointers, int count_stride, int B, int R, int max_n, int top_k, Shape& sh) {
-    auto no = [&](int code, const char* what) { return refuse(fn, code, what); };
+static int shape_of(const Refuse& no, const GnrHandParams* p, bool pointers, int count_stride, int B, int R, int max_n, int top_k, Shape& sh) {
     if (!p || !pointers) return no(GNR_ERR_ARG, "null pointer");
-    if (B < 1 || B > 65535) return no(GNR_ERR_SHAPE, "B must be in 1..65535");
-    if (R < 2 || R > 256) return no(GNR_ERR_SHAPE, "R must be in 2..256");
+    if (int rc = check_scenes(no, GNR_ERR_SHAPE, B)) return rc;
+    if (int rc = check_lattice(no, GNR_ERR_SHAPE, R)) return rc;
     if (max_n < 1) return no(GNR_ERR_SHAPE, "max_n must be >= 1");
     if (count_stride < 1) return no(GNR_ERR_ARG, "count_stride must be >= 1");
     if (top_k < 0) return no(GNR_ERR_ARG, "top_k must be >= 0 (0: every row)");
@@ -413,9 +406,9 @@ static dim3 grid_of(const Shape& sh, int B) { return dim3(sh.blocks < 65536u ? s
 extern "C" int gnr_hand_clearance_fwd(const GnrHandParams* p, const float* vol, const double* pos, const float* quat, const float* width,
                                       const int* count, int count_stride, int B, int R, int max_n, int top_k, float* clearance, int* worst,
                                       int* inside, void* stream) {
-    const char* fn = "gnr_hand_clearance_fwd";
+    const Refuse no{"gnr_hand_clearance_fwd"};
     Shape sh;
-    if (int rc = shape_of(fn, p, vol && pos && quat && width && count && clearance && worst && inside, count_stride, B, R, max_n, top_k, sh)) return rc;
+    if (int rc = shape_of(no, p, vol && pos && quat && width && count && clearance && worst && inside, count_stride, B, R, max_n, top_k, sh)) return rc;
     // the samples of the widest hand, R voxels: the same operations as the device's layout(), summed as doubles before any cast
     const double cell = p->spacing * p->scale, f = p->finger_width, wmax = (double)R * p->scale;
     const double ext[4][3] = {{p->height, f, p->depth + f}, {p->height, f, p->depth + f}, {p->height, wmax, f}, {p->height, f, p->tail_length}};
@@ -425,7 +418,7 @@ extern "C" int gnr_hand_clearance_fwd(const GnrHandParams* p, const float* vol, 
         most += count_of(ext[k][0], cell) * count_of(ext[k][1], cell) * (nz + m);
     }
     if (!(most <= (double)GNR_HAND_MAX_SAMPLES))
-        return refuse(fn, GNR_ERR_ARG, "spacing too small or approach too long, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) samples");
+        return no(GNR_ERR_ARG, "spacing too small or approach too long, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) samples");
     return launch<k_hand_clearance>("k_hand_clearance@gnr_hand_clearance_fwd", (hipStream_t)stream, grid_of(sh, B), dim3(256), 0, vol, pos, quat,
                                     width, count, clearance, worst, inside, sh);
 }
@@ -433,17 +426,17 @@ extern "C" int gnr_hand_clearance_fwd(const GnrHandParams* p, const float* vol, 
 extern "C" int gnr_finger_closure_fwd(const GnrHandParams* p, double level, int bisections, const float* vol, const double* pos,
                                       const float* quat, const float* width, const int* count, int count_stride, int B, int R, int max_n,
                                       int top_k, float* travel, float* cosine, int* contact, float* closed, void* stream) {
-    const char* fn = "gnr_finger_closure_fwd";
+    const Refuse no{"gnr_finger_closure_fwd"};
     Shape sh;
-    if (int rc = shape_of(fn, p, vol && pos && quat && width && count && travel && cosine && contact && closed, count_stride, B, R, max_n, top_k, sh))
+    if (int rc = shape_of(no, p, vol && pos && quat && width && count && travel && cosine && contact && closed, count_stride, B, R, max_n, top_k, sh))
         return rc;
-    if (!isfinite(level)) return refuse(fn, GNR_ERR_ARG, "level must be finite");
-    if (bisections < 0 || bisections > 16) return refuse(fn, GNR_ERR_ARG, "bisections must be in 0..16");
+    if (!isfinite(level)) return no(GNR_ERR_ARG, "level must be finite");
+    if (bisections < 0 || bisections > 16) return no(GNR_ERR_ARG, "bisections must be in 0..16");
     // the volume reads of the widest hand, R voxels: the device's counts, as doubles before any cast
     const double rays = 2.0 * count_of(p->height, sh.cell) * count_of(p->depth, sh.cell);
     const double most = rays * (march_of(0.5 * ((double)R * p->scale), sh.cell) + 1.0 + (double)bisections + 2.0);
     if (!(most <= (double)GNR_HAND_MAX_SAMPLES))
-        return refuse(fn, GNR_ERR_ARG, "spacing too small, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) volume reads");
+        return no(GNR_ERR_ARG, "spacing too small, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) volume reads");
     const Closure cl{level, bisections};
     return launch<k_finger_closure>("k_finger_closure@gnr_finger_closure_fwd", (hipStream_t)stream, grid_of(sh, B), dim3(256), 0, vol, pos, quat,
                                     width, count, travel, cosine, contact, closed, sh, cl);
@@ -452,14 +445,14 @@ extern "C" int gnr_finger_closure_fwd(const GnrHandParams* p, double level, int 
 extern "C" int gnr_grasp_objects_fwd(const GnrHandParams* p, const int* labels, const double* pos, const float* quat, const float* width,
                                      const int* count, int count_stride, int B, int R, int max_n, int top_k, int* object, int* votes,
                                      int* distinct, int* inside, void* stream) {
-    const char* fn = "gnr_grasp_objects_fwd";
+    const Refuse no{"gnr_grasp_objects_fwd"};
     Shape sh;
-    if (int rc = shape_of(fn, p, labels && pos && quat && width && count && object && votes && distinct && inside, count_stride, B, R, max_n, top_k, sh))
+    if (int rc = shape_of(no, p, labels && pos && quat && width && count && object && votes && distinct && inside, count_stride, B, R, max_n, top_k, sh))
         return rc;
     // the samples of the widest hand, R voxels: the device's counts, as doubles before any cast
     const double most = count_of(p->height, sh.cell) * count_of((double)R * p->scale, sh.cell) * count_of(p->depth, sh.cell);
     if (!(most <= (double)GNR_HAND_MAX_SAMPLES))
-        return refuse(fn, GNR_ERR_ARG, "spacing too small, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) samples");
+        return no(GNR_ERR_ARG, "spacing too small, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) samples");
     return launch<k_grasp_objects>("k_grasp_objects@gnr_grasp_objects_fwd", (hipStream_t)stream, grid_of(sh, B), dim3(256), 0, labels, pos, quat,
                                    width, count, object, votes, distinct, inside, sh);
 }

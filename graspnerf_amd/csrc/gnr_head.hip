@@ -415,7 +415,7 @@ static void pack_folded(float* dst, const float* W, const float* bias, int cout,
 }
 
 extern "C" int gnr_pack_grasp_head(const float* c, float* p) {
-    if (!c || !p) return fail(GNR_ERR_ARG, "gnr_pack_grasp_head: null pointer");
+    if (!c || !p) return Refuse{"gnr_pack_grasp_head"}(GNR_ERR_ARG, "null pointer");
     for (int i = 0; i < P_TOTAL; ++i) p[i] = 0.f;
     for (int i = 0; i < w_sz(16, 1, 5); ++i) p[P_E1 + i] = c[C_E1W + i];
     for (int i = 0; i < 16; ++i) p[P_E1 + w_sz(16, 1, 5) + i] = c[C_E1B + i];
@@ -460,8 +460,9 @@ static int launch_staged(const ConvArgs& a, hipStream_t st) {
 // (the reference interpolates to the fixed sizes 10/20/40 whatever R is, networks.py:88-96).
 extern "C" int gnr_grasp_head_fwd(int B, int R, const float* volume, const float* packed, float* qual, float* rot, float* width,
                                   void* ws, size_t ws_bytes, void* stream) {
-    if (!volume || !packed || !qual || !rot || !width || !ws) return fail(GNR_ERR_ARG, "gnr_grasp_head_fwd: null pointer");
-    if (B < 1 || R < 8 || R > 64) return fail(GNR_ERR_SHAPE, "gnr_grasp_head_fwd: bad B/R");
+    const Refuse no{"gnr_grasp_head_fwd"};
+    if (!volume || !packed || !qual || !rot || !width || !ws) return no(GNR_ERR_ARG, "null pointer");
+    if (B < 1 || R < 8 || R > 64) return no(GNR_ERR_SHAPE, "bad B/R");
     if (ws_bytes < gnr_grasp_head_workspace_bytes(B, R)) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     TimingScope ts("grasp_head_fwd(all kernels)@gnr_grasp_head_fwd", stream);
@@ -560,7 +561,7 @@ __global__ __launch_bounds__(256) void k_conv3d_bwd_weight(const float* __restri
 extern "C" int gnr_conv3d_bwd_weight(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int K,
                                      void* stream) {
     if (!x || !dy || !dw || B < 1 || Cin < 1 || Cout < 1 || D < 1 || H < 1 || W < 1 || K < 1 || !(K & 1))
-        return fail(GNR_ERR_ARG, "gnr_conv3d_bwd_weight: null pointer, a size below 1 or an even K");
+        return Refuse{"gnr_conv3d_bwd_weight"}(GNR_ERR_ARG, "null pointer, a size below 1 or an even K");
     const long total = (long)B * D * H * W;
     const int nchunk = (int)((total + gnr_head::BW_CHUNK - 1) / gnr_head::BW_CHUNK);
     const long njobs = (long)nchunk * K * K * K * ((Cin + 15) / 16) * ((Cout + 15) / 16);
@@ -865,7 +866,7 @@ extern "C" size_t gnr_conv3d_tap_mask_words(int Cin, int Cout) {
 // mask [Cin blocks][Cout blocks][4 words] <- which taps of each 16 x 16 weight block exist in `pattern` [Cout][Cin][K^3] (device, any
 // non-zero = the weight exists).  Made once per layer shape; the masked entry points below skip the absent taps in all three directions.
 extern "C" int gnr_conv3d_tap_mask(const float* pattern, unsigned* mask, int Cin, int Cout, int K, void* stream) {
-    if (!pattern || !mask || Cin < 1 || Cout < 1 || (K != 3 && K != 5)) return fail(GNR_ERR_ARG, "gnr_conv3d_tap_mask: null pointer, a size below 1 or K not 3 or 5");
+    if (!pattern || !mask || Cin < 1 || Cout < 1 || (K != 3 && K != 5)) return Refuse{"gnr_conv3d_tap_mask"}(GNR_ERR_ARG, "null pointer, a size below 1 or K not 3 or 5");
     const int nbi = (Cin + 15) / 16, nbo = (Cout + 15) / 16;
     return launch<gnr_head::k_conv3d_tap_mask>(nullptr, (hipStream_t)stream, dim3(nbi * nbo), dim3(64), 0, pattern, mask, Cin, Cout, K * K * K, nbo);
 }

@@ -1,8 +1,10 @@
-// Host layer shared by every source file of libgnr.so: the one error text, the per-launch timing bracket and the one way to
-// launch a kernel.  Internal (not installed next to include/gnr.h), host code only.
+// Host layer shared by every source file of libgnr.so: the one error text, an entry point's refusals, the batch and lattice limits,
+// the workspace carve, the per-launch timing bracket and the one way to launch a kernel.  Internal (not installed next to
+// include/gnr.h), host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdio.h>
 #include <atomic>
 
 #include "../../include/gnr.h"
@@ -24,7 +26,34 @@ static inline int fail(int code, const char* what, hipError_t e = hipSuccess) { 
         if (e_ != hipSuccess) return gnr::fail(GNR_ERR_HIP, #call, e_);       \
     } while (0)
 
+// An entry point's refusals: `gnr::Refuse no{"gnr_x_fwd"};` then `return no(code, what)` fails with the text "gnr_x_fwd: what".
+struct Refuse {
+    const char* fn;
+    int operator()(int code, const char* what) const {
+        char text[256];                                // (fail() copies the text)
+        snprintf(text, sizeof text, "%s: %s", fn, what);
+        return fail(code, text);
+    }
+};
+
+// The limits every volume operator shares: the scene is a grid dimension (y or z: 65535 at most), a lattice has 2..256 voxels a side.
+// check_*: GNR_OK, or the refusal under the entry point's own status code.
+constexpr int MAX_SCENES = 65535, MIN_LATTICE = 2, MAX_LATTICE = 256;
+static inline bool scenes_ok(int B) { return B >= 1 && B <= MAX_SCENES; }
+static inline bool lattice_ok(int R) { return R >= MIN_LATTICE && R <= MAX_LATTICE; }
+static inline int check_scenes(const Refuse& no, int code, int B) { return scenes_ok(B) ? GNR_OK : no(code, "B must be in 1..65535"); }
+static inline int check_lattice(const Refuse& no, int code, int R) { return lattice_ok(R) ? GNR_OK : no(code, "R must be in 2..256"); }
+
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// A workspace, carved in order into regions aligned to 256 bytes.  An operator states its regions once, in one function over a
+// Carve: its *_workspace_bytes carves nullptr (every take() is null) and returns total(), its entry point carves the caller's pointer.
+struct Carve {
+    char* base; size_t off;
+    explicit Carve(void* ws) : base((char*)ws), off(0) {}
+    template <typename T> T* take(size_t count) { T* q = base ? (T*)(base + off) : nullptr; off += al256(count * sizeof(T)); return q; }
+    size_t total() const { return off; }
+};
 
 // hipFuncSetAttribute (dynamic LDS above 64 KiB) is per device: one bit per device id and kernel (launch())
 static inline bool attr_needed(std::atomic<unsigned long long>& done) {

@@ -329,9 +329,10 @@ const char* gnr_img_last_error(void) { return gnr_last_error(); }             //
 
 int gnr_instnorm_act(const float* x, const float* res, const float* weight, const float* bias, float* y, float* mean, float* rstd,
                      long long planes, int C, int HW, float eps, int act, void* stream) {
-    if (!x || !weight || !bias || !y || !mean || !rstd) return fail(GNR_ERR_ARG, "gnr_instnorm_act: null pointer");
+    const Refuse no{"gnr_instnorm_act"};
+    if (!x || !weight || !bias || !y || !mean || !rstd) return no(GNR_ERR_ARG, "null pointer");
     if (planes < 0 || C <= 0 || HW <= 0 || planes % C != 0 || act < GNR_ACT_NONE || act > GNR_ACT_ELU || planes > 0x7fffffffLL)
-        return fail(GNR_ERR_SHAPE, "gnr_instnorm_act: planes must be a multiple of C > 0, HW > 0, act in {0,1,2}");
+        return no(GNR_ERR_SHAPE, "planes must be a multiple of C > 0, HW > 0, act in {0,1,2}");
     if (planes == 0) return GNR_OK;
     hipStream_t st = (hipStream_t)stream;
     InArgs a{x, res, weight, bias, y, mean, rstd, C, HW, eps, act};
@@ -348,10 +349,11 @@ int gnr_instnorm_act(const float* x, const float* res, const float* weight, cons
 int gnr_instnorm_act_bwd(const float* dy, const float* out, const float* x, const float* mean, const float* rstd, const float* weight,
                          float* dx, float* dres, float* s1, float* s2, float* dweight, float* dbias, long long planes, int C, int HW, int act,
                          void* stream) {
+    const Refuse no{"gnr_instnorm_act_bwd"};
     if (!dy || !x || !mean || !rstd || !weight || !dx || !s1 || !s2 || !dweight || !dbias || (act != GNR_ACT_NONE && !out))
-        return fail(GNR_ERR_ARG, "gnr_instnorm_act_bwd: null pointer");
+        return no(GNR_ERR_ARG, "null pointer");
     if (planes < 0 || C <= 0 || HW <= 0 || planes % C != 0 || act < GNR_ACT_NONE || act > GNR_ACT_ELU || planes > 0x7fffffffLL)
-        return fail(GNR_ERR_SHAPE, "gnr_instnorm_act_bwd: planes must be a multiple of C > 0, HW > 0, act in {0,1,2}");
+        return no(GNR_ERR_SHAPE, "planes must be a multiple of C > 0, HW > 0, act in {0,1,2}");
     hipStream_t st = (hipStream_t)stream;
     if (planes == 0) {
         GNR_HIP(hipMemsetAsync(dweight, 0, sizeof(float) * C, st));
@@ -372,44 +374,48 @@ int gnr_instnorm_act_bwd(const float* dy, const float* out, const float* x, cons
     return launch<k_in_wb>(nullptr, st, dim3((unsigned)(C + 63) / 64), dim3(64), 0, s1, s2, dweight, dbias, (int)(planes / C), C);
 }
 
-static int pad_args(const void* a, const void* b, long long planes, int H, int W, int pad, const char* who) {
-    if (!a || !b) return fail(GNR_ERR_ARG, who);
-    if (planes < 0 || H <= 0 || W <= 0 || pad < 0 || pad >= H || pad >= W) return fail(GNR_ERR_SHAPE, who);    // F.pad: pad < size
+static int pad_args(const Refuse& no, const void* a, const void* b, long long planes, int H, int W, int pad) {
+    if (!a || !b) return no(GNR_ERR_ARG, "null pointer or pad outside [0, min(H, W))");
+    // F.pad: pad < size
+    if (planes < 0 || H <= 0 || W <= 0 || pad < 0 || pad >= H || pad >= W) return no(GNR_ERR_SHAPE, "null pointer or pad outside [0, min(H, W))");
     return GNR_OK;
 }
 
 int gnr_reflect_pad2d(const float* x, float* y, long long planes, int H, int W, int pad, void* stream) {
-    if (const int rc = pad_args(x, y, planes, H, W, pad, "gnr_reflect_pad2d: null pointer or pad outside [0, min(H, W))")) return rc;
+    const Refuse no{"gnr_reflect_pad2d"};
+    if (const int rc = pad_args(no, x, y, planes, H, W, pad)) return rc;
     const unsigned groups = (unsigned)(W + 2 * pad + 3) / 4;
     const unsigned long long total = (unsigned long long)planes * (H + 2 * pad) * groups;
-    if (total > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_reflect_pad2d: too many pixels for one launch");
+    if (total > 0x7fffffffULL) return no(GNR_ERR_SHAPE, "too many pixels for one launch");
     if (total == 0) return GNR_OK;
     return launch<k_reflect_pad>(nullptr, (hipStream_t)stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, x, y, H, W, pad, groups, (unsigned)total);
 }
 
 int gnr_reflect_pad2d_bwd(const float* dy, float* dx, long long planes, int H, int W, int pad, void* stream) {
-    if (const int rc = pad_args(dy, dx, planes, H, W, pad, "gnr_reflect_pad2d_bwd: null pointer or pad outside [0, min(H, W))")) return rc;
+    const Refuse no{"gnr_reflect_pad2d_bwd"};
+    if (const int rc = pad_args(no, dy, dx, planes, H, W, pad)) return rc;
     const unsigned groups = (unsigned)(W + 3) / 4;
     const unsigned long long total = (unsigned long long)planes * H * groups;
-    if (total > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_reflect_pad2d_bwd: too many pixels for one launch");
+    if (total > 0x7fffffffULL) return no(GNR_ERR_SHAPE, "too many pixels for one launch");
     if (total == 0) return GNR_OK;
     return launch<k_reflect_pad_bwd>(nullptr, (hipStream_t)stream, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, dy, dx, H, W, pad, groups, (unsigned)total);
 }
 
 int gnr_upsample2x_bilinear(const float* x, float* y, long long planes, int H, int W, void* stream) {
-    if (!x || !y) return fail(GNR_ERR_ARG, "gnr_upsample2x_bilinear: null pointer");
-    if (planes < 0 || H <= 0 || W <= 0) return fail(GNR_ERR_SHAPE, "gnr_upsample2x_bilinear: H, W > 0");
+    const Refuse no{"gnr_upsample2x_bilinear"};
+    if (!x || !y) return no(GNR_ERR_ARG, "null pointer");
+    if (planes < 0 || H <= 0 || W <= 0) return no(GNR_ERR_SHAPE, "H, W > 0");
     if (planes == 0) return GNR_OK;
     const float sh = (float)(H - 1) / (float)(2 * H - 1), sw = (float)(W - 1) / (float)(2 * W - 1);
     const unsigned long long total = (unsigned long long)planes * 2 * H * 2 * W;
     hipStream_t st = (hipStream_t)stream;
     if (W % 2 == 0 && aligned16(y)) {
         const unsigned long long blocks = (total / 4 + 255) / 256;
-        if (blocks > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_upsample2x_bilinear: too large for one launch");
+        if (blocks > 0x7fffffffULL) return no(GNR_ERR_SHAPE, "too large for one launch");
         return launch<k_upsample2x>(nullptr, st, dim3((unsigned)blocks), dim3(256), 0, x, y, H, W, sh, sw, (size_t)(total / 4));
     }
     const unsigned long long blocks = (total + 255) / 256;
-    if (blocks > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_upsample2x_bilinear: too large for one launch");
+    if (blocks > 0x7fffffffULL) return no(GNR_ERR_SHAPE, "too large for one launch");
     return launch<k_upsample2x_any>(nullptr, st, dim3((unsigned)blocks), dim3(256), 0, x, y, H, W, sh, sw, (size_t)total);
 }
 

@@ -106,10 +106,11 @@ size_t gnr_ingest_tables_bytes(int dst_h, int dst_w) {
 }
 
 int gnr_ingest_tables_host(int src_h, int src_w, int dst_h, int dst_w, void* tables_host) {
-    if (!tables_host) return fail(GNR_ERR_ARG, "gnr_ingest_tables_host: null pointer");
+    const Refuse no{"gnr_ingest_tables_host"};
+    if (!tables_host) return no(GNR_ERR_ARG, "null pointer");
     if (src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || src_h > GNR_INGEST_MAX_DIM || src_w > GNR_INGEST_MAX_DIM ||
         dst_h > GNR_INGEST_MAX_DIM || dst_w > GNR_INGEST_MAX_DIM)
-        return fail(GNR_ERR_SHAPE, "gnr_ingest_tables_host: every dimension must be in 1..16384");
+        return no(GNR_ERR_SHAPE, "every dimension must be in 1..16384");
     int* t = static_cast<int*>(tables_host);
     axis_table(dst_w, src_w, t, t + dst_w, t + 2 * dst_w, t + 3 * dst_w);
     int* ty = t + 4 * (size_t)dst_w;
@@ -121,17 +122,18 @@ int gnr_ingest_tables_host(int src_h, int src_w, int dst_h, int dst_w, void* tab
 
 int gnr_ingest_u8(const unsigned char* frames, int n, int src_h, int src_w, int channels, size_t row_pitch, size_t frame_pitch,
                   const void* tables_dev, float* out, int dst_h, int dst_w, void* stream) {
-    if (!frames || !tables_dev || !out) return fail(GNR_ERR_ARG, "gnr_ingest_u8: null pointer");
-    if (channels != 3 && channels != 4) return fail(GNR_ERR_ARG, "gnr_ingest_u8: channels must be 3 or 4");
+    const Refuse no{"gnr_ingest_u8"};
+    if (!frames || !tables_dev || !out) return no(GNR_ERR_ARG, "null pointer");
+    if (channels != 3 && channels != 4) return no(GNR_ERR_ARG, "channels must be 3 or 4");
     if (n < 1 || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || src_h > GNR_INGEST_MAX_DIM || src_w > GNR_INGEST_MAX_DIM ||
         dst_h > GNR_INGEST_MAX_DIM || dst_w > GNR_INGEST_MAX_DIM)
-        return fail(GNR_ERR_SHAPE, "gnr_ingest_u8: n >= 1 and every dimension in 1..16384");
-    if (row_pitch < (size_t)src_w * (size_t)channels) return fail(GNR_ERR_ARG, "gnr_ingest_u8: row_pitch < src_w * channels");
+        return no(GNR_ERR_SHAPE, "n >= 1 and every dimension in 1..16384");
+    if (row_pitch < (size_t)src_w * (size_t)channels) return no(GNR_ERR_ARG, "row_pitch < src_w * channels");
     if (n > 1 && frame_pitch < (size_t)(src_h - 1) * row_pitch + (size_t)src_w * (size_t)channels)
-        return fail(GNR_ERR_ARG, "gnr_ingest_u8: frame_pitch shorter than one frame");
+        return no(GNR_ERR_ARG, "frame_pitch shorter than one frame");
     const unsigned groups = (unsigned)(dst_w + 3) / 4;
     const unsigned long long total = (unsigned long long)n * (unsigned)dst_h * groups;
-    if (total > 0x7fffffffULL) return fail(GNR_ERR_SHAPE, "gnr_ingest_u8: too many output pixels for one launch");
+    if (total > 0x7fffffffULL) return no(GNR_ERR_SHAPE, "too many output pixels for one launch");
     const int* tab = static_cast<const int*>(tables_dev);
     Args a{frames, tab, reinterpret_cast<const float*>(tab + table_words(dst_h, dst_w)), out, row_pitch, frame_pitch,
            src_h, src_w, channels, dst_h, dst_w, groups, (unsigned)total};

@@ -186,32 +186,35 @@ static inline size_t chunks(size_t items) { return (items + 1023) / 1024; }
 using namespace gnr_mesh;
 
 // workspace: the cells' chunk counts [B, chunks((R-1)^3)], the edges' [B, chunks(R^3)], the cell -> vertex map [B, (R-1)^3], ints
-extern "C" size_t gnr_surface_mesh_workspace_bytes(int B, int R) {
-    if (B < 1 || B > 65535 || R < 2 || R > 256) return 0;
+struct MeshWork { int *chunk_v, *chunk_f, *map; size_t total; };
+
+static MeshWork carve(int B, int R, void* base) {
     const size_t nc = (size_t)(R - 1) * (R - 1) * (R - 1), n = (size_t)R * R * R;
-    return al256((size_t)B * chunks(nc) * sizeof(int)) + al256((size_t)B * chunks(n) * sizeof(int)) + al256((size_t)B * nc * sizeof(int));
+    Carve c(base);
+    return MeshWork{c.take<int>(B * chunks(nc)), c.take<int>(B * chunks(n)), c.take<int>(B * nc), c.total()};     // (in this order)
+}
+
+extern "C" size_t gnr_surface_mesh_workspace_bytes(int B, int R) {
+    return scenes_ok(B) && lattice_ok(R) ? carve(B, R, nullptr).total : 0;
 }
 
 extern "C" int gnr_surface_mesh_fwd(const float* vol, const float* grad, int B, int R, const GnrMeshParams* p, int* count, double* vertices,
                                     int* faces, float* gradient, int max_v, int max_f, void* ws, size_t ws_bytes, void* stream) {
-    if (!vol || !p || !count || !vertices || !faces || !ws) return fail(GNR_ERR_ARG, "gnr_surface_mesh_fwd: null pointer");
-    if ((grad == nullptr) != (gradient == nullptr))
-        return fail(GNR_ERR_ARG, "gnr_surface_mesh_fwd: grad and gradient must be both given or both NULL");
-    if (B < 1 || B > 65535) return fail(GNR_ERR_SHAPE, "gnr_surface_mesh_fwd: B must be in 1..65535");
-    if (R < 2 || R > 256) return fail(GNR_ERR_SHAPE, "gnr_surface_mesh_fwd: R must be in 2..256");
-    if (max_v < 1) return fail(GNR_ERR_SHAPE, "gnr_surface_mesh_fwd: max_v must be >= 1");
-    if (max_f < 1) return fail(GNR_ERR_SHAPE, "gnr_surface_mesh_fwd: max_f must be >= 1");
+    const Refuse no{"gnr_surface_mesh_fwd"};
+    if (!vol || !p || !count || !vertices || !faces || !ws) return no(GNR_ERR_ARG, "null pointer");
+    if ((grad == nullptr) != (gradient == nullptr)) return no(GNR_ERR_ARG, "grad and gradient must be both given or both NULL");
+    if (int rc = check_scenes(no, GNR_ERR_SHAPE, B)) return rc;
+    if (int rc = check_lattice(no, GNR_ERR_SHAPE, R)) return rc;
+    if (max_v < 1) return no(GNR_ERR_SHAPE, "max_v must be >= 1");
+    if (max_f < 1) return no(GNR_ERR_SHAPE, "max_f must be >= 1");
     if (!isfinite(p->iso) || !isfinite(p->scale) || !isfinite(p->origin[0]) || !isfinite(p->origin[1]) || !isfinite(p->origin[2]))
-        return fail(GNR_ERR_ARG, "gnr_surface_mesh_fwd: iso, scale and origin must be finite");
-    if (ws_bytes < gnr_surface_mesh_workspace_bytes(B, R))
-        return fail(GNR_ERR_WORKSPACE, "gnr_surface_mesh_fwd: workspace smaller than gnr_surface_mesh_workspace_bytes(B, R)");
+        return no(GNR_ERR_ARG, "iso, scale and origin must be finite");
+    const MeshWork k = carve(B, R, ws);
+    if (ws_bytes < k.total) return no(GNR_ERR_WORKSPACE, "workspace smaller than gnr_surface_mesh_workspace_bytes(B, R)");
     hipStream_t st = (hipStream_t)stream;
     const size_t nc = (size_t)(R - 1) * (R - 1) * (R - 1), n = (size_t)R * R * R;
     const int ch_v = (int)chunks(nc), ch_f = (int)chunks(n);
-    char* base = (char*)ws;
-    int* chunk_v = (int*)base;      base += al256((size_t)B * ch_v * sizeof(int));
-    int* chunk_f = (int*)base;      base += al256((size_t)B * ch_f * sizeof(int));
-    int* map = (int*)base;
+    int *chunk_v = k.chunk_v, *chunk_f = k.chunk_f, *map = k.map;
     const Frame fr{p->iso, p->scale, {p->origin[0], p->origin[1], p->origin[2]}};
     const dim3 grid_v(ch_v, B), grid_f(ch_f, B), block(1024);
     if (int rc = launch<k_mesh_count_cells>("k_mesh_count_cells@gnr_surface_mesh_fwd", st, grid_v, block, 0, vol, R, p->iso, chunk_v)) return rc;

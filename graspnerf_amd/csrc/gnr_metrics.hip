@@ -50,16 +50,14 @@ struct Work {
 
 static Work carve(const Dims& d, bool ssim, void* base) {
     Work k;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += al256(bytes); return q; };
+    Carve c(base);
     const size_t bp = (size_t)d.B * d.n_pred;
-    k.sse = (unsigned long long*)take(bp * sizeof(unsigned long long));
-    k.bad = (int*)take(bp * sizeof(int));
-    k.zero_bytes = off;
-    k.mae_part = (double*)take((size_t)d.B * d.nblk * sizeof(double));
-    k.ssim_part = ssim ? (double*)take(bp * 3 * (size_t)d.tx * d.ty * sizeof(double)) : nullptr;
-    k.total = off;
+    k.sse = c.take<unsigned long long>(bp);
+    k.bad = c.take<int>(bp);
+    k.zero_bytes = c.total();
+    k.mae_part = c.take<double>((size_t)d.B * d.nblk);
+    k.ssim_part = ssim ? c.take<double>(bp * 3 * (size_t)d.tx * d.ty) : nullptr;
+    k.total = c.total();
     return k;
 }
 
@@ -220,11 +218,9 @@ __global__ __launch_bounds__(256) void k_frame_finish(Dims d, Work k, int ssim, 
     }
 }
 
-static int check_dims(const char* who, int B, int h, int w, int n_pred, int hm, int wm, int ssim, Dims* out) {
-    char msg[160];                                          // (fail() copies the text)
-    auto say = [&](int code, const char* what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return fail(code, msg); };
+static int check_dims(const Refuse& say, int B, int h, int w, int n_pred, int hm, int wm, int ssim, Dims* out) {
     if (n_pred < 1 || n_pred > GNR_METRICS_MAX_PRED) return say(GNR_ERR_ARG, "n_pred must be in 1..4");
-    if (B < 1 || B > 65535 || h < 1 || w < 1 || (long long)h * w > (1ll << 31) - PIX_PER_BLOCK)
+    if (!scenes_ok(B) || h < 1 || w < 1 || (long long)h * w > (1ll << 31) - PIX_PER_BLOCK)
         return say(GNR_ERR_SHAPE, "B in 1..65535, h, w >= 1, h * w below 2^31");
     if (hm < 0 || wm < 0 || 2 * (long long)hm >= h || 2 * (long long)wm >= w) return say(GNR_ERR_SHAPE, "the crop margins leave no pixel");
     const Dims d = dims(B, h, w, n_pred, hm, wm);
@@ -242,22 +238,23 @@ extern "C" {
 
 size_t gnr_frame_metrics_workspace_bytes(int B, int h, int w, int n_pred, int h_margin, int w_margin, int ssim) {
     Dims d;
-    if (check_dims("gnr_frame_metrics_workspace_bytes", B, h, w, n_pred, h_margin, w_margin, ssim, &d) != GNR_OK) return 0;
+    if (check_dims(Refuse{"gnr_frame_metrics_workspace_bytes"}, B, h, w, n_pred, h_margin, w_margin, ssim, &d) != GNR_OK) return 0;
     return carve(d, ssim != 0, nullptr).total;
 }
 
 int gnr_frame_metrics(const float* gt, const float* const* preds, int n_pred, const float* depth_pr, const float* depth_gt, int B, int h,
                       int w, int h_margin, int w_margin, int ssim, double* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!gt || !preds || !depth_pr || !depth_gt || !out || !workspace) return fail(GNR_ERR_ARG, "gnr_frame_metrics: null pointer");
+    const Refuse no{"gnr_frame_metrics"};
+    if (!gt || !preds || !depth_pr || !depth_gt || !out || !workspace) return no(GNR_ERR_ARG, "null pointer");
     Dims d;
-    if (int rc = check_dims("gnr_frame_metrics", B, h, w, n_pred, h_margin, w_margin, ssim, &d)) return rc;
+    if (int rc = check_dims(no, B, h, w, n_pred, h_margin, w_margin, ssim, &d)) return rc;
     Preds pr{};
     for (int p = 0; p < n_pred; ++p) {
-        if (!preds[p]) return fail(GNR_ERR_ARG, "gnr_frame_metrics: null prediction pointer");
+        if (!preds[p]) return no(GNR_ERR_ARG, "null prediction pointer");
         pr.p[p] = preds[p];
     }
     const Work k = carve(d, ssim != 0, workspace);
-    if (workspace_bytes < k.total) return fail(GNR_ERR_WORKSPACE, "gnr_frame_metrics: workspace smaller than gnr_frame_metrics_workspace_bytes()");
+    if (workspace_bytes < k.total) return no(GNR_ERR_WORKSPACE, "workspace smaller than gnr_frame_metrics_workspace_bytes()");
     hipStream_t st = (hipStream_t)stream;
     if (const hipError_t e = hipMemsetAsync(workspace, 0, k.zero_bytes, st)) return fail(GNR_ERR_HIP, "gnr_frame_metrics: hipMemsetAsync", e);
     if (int rc = launch<k_frame_pixels>("k_frame_pixels@gnr_frame_metrics", st, dim3(d.nblk, B), dim3(256), 0, gt, pr, depth_pr, depth_gt, d, k)) return rc;

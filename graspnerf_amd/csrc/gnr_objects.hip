@@ -28,10 +28,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "gnr_compact.h"
 #include "gnr_host.h"
+#include "gnr_solid.h"
 
 namespace gnr_objects {
 
@@ -77,11 +77,6 @@ __device__ inline void unite(int* parent, int a, int b, int lim, int* status) {
         b = lo;
     }
     flag_bound(status);
-}
-
-__device__ inline bool solid_at(const Shape& sh, float v, int k) {
-    const double x = (double)v;
-    return sh.lower < x && x < sh.level && k >= sh.z_min;
 }
 
 // launch grid: (ceil(n / 256), B), 256 threads.  The rows of the statistics are spread over all threads of the grid.
@@ -221,22 +216,12 @@ __global__ __launch_bounds__(256) void k_label(const float* __restrict__ vol, co
     }
 }
 
-static int refuse(const char* fn, int code, const char* what) {
-    char text[200];
-    snprintf(text, sizeof text, "%s: %s", fn, what);
-    return fail(code, text);
-}
+struct Work { int *status, *parent, *size, *chunk; size_t total; };
 
-struct Layout { size_t parent, size, chunk, total; };
-
-static Layout layout_of(int B, int R) {
+static Work carve(int B, int R, void* base) {
     const size_t n = (size_t)R * R * R, nc = (n + 1023) / 1024;
-    Layout l;
-    l.parent = 256;                                                            // the status word has the first 256 bytes to itself
-    l.size = l.parent + al256((size_t)B * n * sizeof(int));
-    l.chunk = l.size + al256((size_t)B * n * sizeof(int));
-    l.total = l.chunk + al256((size_t)B * nc * sizeof(int));
-    return l;
+    Carve c(base);                                                             // the status word has the first 256 bytes to itself
+    return Work{c.take<int>(1), c.take<int>(B * n), c.take<int>(B * n), c.take<int>(B * nc), c.total()};          // (in this order)
 }
 
 }  // namespace gnr_objects
@@ -244,36 +229,28 @@ static Layout layout_of(int B, int R) {
 using namespace gnr_objects;
 
 extern "C" size_t gnr_volume_objects_workspace_bytes(int B, int R) {
-    if (B < 1 || B > 65535 || R < 2 || R > 256) return 0;
-    return layout_of(B, R).total;
+    return scenes_ok(B) && lattice_ok(R) ? carve(B, R, nullptr).total : 0;
 }
 
 extern "C" int gnr_volume_objects_fwd(const GnrObjectsParams* p, const float* vol, int B, int R, int* labels, int* count, int* voxels,
                                       int* bbox, unsigned long long* sums, float* cleaned, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    const char* fn = "gnr_volume_objects_fwd";
-    auto no = [&](int code, const char* what) { return refuse(fn, code, what); };
+    const Refuse no{"gnr_volume_objects_fwd"};
     if (!p || !vol || !labels || !count || !voxels || !bbox || !sums || !workspace) return no(GNR_ERR_ARG, "null pointer");
-    if (B < 1 || B > 65535) return no(GNR_ERR_SHAPE, "B must be in 1..65535");
-    if (R < 2 || R > 256) return no(GNR_ERR_SHAPE, "R must be in 2..256");
+    if (int rc = check_scenes(no, GNR_ERR_SHAPE, B)) return rc;
+    if (int rc = check_lattice(no, GNR_ERR_SHAPE, R)) return rc;
     if (p->connectivity != 6 && p->connectivity != 18 && p->connectivity != 26) return no(GNR_ERR_ARG, "connectivity must be 6, 18 or 26");
     if (p->max_objects < 1) return no(GNR_ERR_SHAPE, "max_objects must be >= 1");
-    if (p->z_min < 0 || p->z_min > R) return no(GNR_ERR_ARG, "z_min must be in 0..R");
-    if (!isfinite(p->level)) return no(GNR_ERR_ARG, "level must be finite");
-    if (isnan(p->lower)) return no(GNR_ERR_ARG, "lower must not be a NaN (-inf: none)");
+    if (int rc = check_solid(no, p->level, p->lower, p->z_min, R)) return rc;
     if (!isfinite(p->free_value)) return no(GNR_ERR_ARG, "free_value must be finite");
-    const Layout l = layout_of(B, R);
-    if (workspace_bytes < l.total) return no(GNR_ERR_WORKSPACE, "workspace too small");
+    const Work k = carve(B, R, workspace);
+    if (workspace_bytes < k.total) return no(GNR_ERR_WORKSPACE, "workspace too small");
     Shape sh{};
     sh.R = R; sh.n = R * R * R; sh.nc = (sh.n + 1023) / 1024;
     sh.z_min = p->z_min; sh.order = p->connectivity == 6 ? 1 : p->connectivity == 18 ? 2 : 3;
     sh.max_objects = p->max_objects; sh.min_voxels = p->min_voxels;
     sh.level = p->level; sh.lower = p->lower; sh.free_value = p->free_value;
-    char* ws = (char*)workspace;
-    int* status = (int*)ws;
-    int* parent = (int*)(ws + l.parent);
-    int* size = (int*)(ws + l.size);
-    int* chunk = (int*)(ws + l.chunk);
+    int *status = k.status, *parent = k.parent, *size = k.size, *chunk = k.chunk;
     hipStream_t st = (hipStream_t)stream;
     const dim3 g256((unsigned)((sh.n + 255) / 256), (unsigned)B), g1024((unsigned)sh.nc, (unsigned)B);
     if (int rc = launch<k_init>("k_init@gnr_volume_objects_fwd", st, g256, dim3(256), 0, vol, parent, size, status, voxels, bbox, sums, sh)) return rc;

@@ -40,27 +40,27 @@ int c16_image(float* p, hipStream_t st) {
 using namespace gnr;
 
 extern "C" int gnr_pack_weights_device(const float* canonical_dev, float* packed_dev, void* stream) {
-    if (!canonical_dev || !packed_dev) return fail(GNR_ERR_ARG, "gnr_pack_weights_device: null pointer");
+    if (!canonical_dev || !packed_dev) return Refuse{"gnr_pack_weights_device"}(GNR_ERR_ARG, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (int rc = pack<k_pack_forward>(st, canonical_dev, packed_dev)) return rc;
     return c16_image(packed_dev, st);
 }
 
 extern "C" int gnr_pack_vis_decoder_device(const float* vis_decoder_dev, float* packed_dev, void* stream) {
-    if (!vis_decoder_dev || !packed_dev) return fail(GNR_ERR_ARG, "gnr_pack_vis_decoder_device: null pointer");
+    if (!vis_decoder_dev || !packed_dev) return Refuse{"gnr_pack_vis_decoder_device"}(GNR_ERR_ARG, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (int rc = pack<k_pack_vis>(st, vis_decoder_dev, packed_dev)) return rc;
     return c16_image(packed_dev, st);
 }
 
 extern "C" int gnr_pack_weights_bwd_device(const float* canonical_dev, float* packed_bwd_dev, void* stream) {
-    if (!canonical_dev || !packed_bwd_dev) return fail(GNR_ERR_ARG, "gnr_pack_weights_bwd_device: null pointer");
+    if (!canonical_dev || !packed_bwd_dev) return Refuse{"gnr_pack_weights_bwd_device"}(GNR_ERR_ARG, "null pointer");
     if (int rc = pack<k_pack_backward>((hipStream_t)stream, canonical_dev, packed_bwd_dev)) return rc;
     return pack<k_pack_backward_pairs>((hipStream_t)stream, packed_bwd_dev);
 }
 
 extern "C" int gnr_pack_vis_decoder_bwd_device(const float* vis_decoder_dev, float* packed_bwd_dev, void* stream) {
-    if (!vis_decoder_dev || !packed_bwd_dev) return fail(GNR_ERR_ARG, "gnr_pack_vis_decoder_bwd_device: null pointer");
+    if (!vis_decoder_dev || !packed_bwd_dev) return Refuse{"gnr_pack_vis_decoder_bwd_device"}(GNR_ERR_ARG, "null pointer");
     if (int rc = pack<k_pack_vis_backward>((hipStream_t)stream, vis_decoder_dev, packed_bwd_dev)) return rc;
     return pack<k_pack_vis_backward_pairs>((hipStream_t)stream, packed_bwd_dev);
 }

@@ -271,45 +271,49 @@ using namespace gnr_post;
 
 extern "C" const char* gnr_post_last_error(void) { return gnr_last_error(); }       // alias: the library has one error text
 
-extern "C" size_t gnr_grasp_select_workspace_bytes(int B, int R) {
-    if (B < 1 || R < 1) return 0;
+// the select workspace: two float and three byte volumes, then, to rank by score, two key and two index volumes
+struct SelectWork { float *fa, *fb; unsigned char *xa, *xb, *mk; unsigned *ka, *kb; int *ia, *ib; size_t total; };
+
+static SelectWork carve_select(int B, int R, int order, void* base) {
     const size_t n = (size_t)B * R * R * R;
-    return 2 * al256(n * sizeof(float)) + 3 * al256(n);
+    Carve c(base);
+    SelectWork k{c.take<float>(n), c.take<float>(n), c.take<unsigned char>(n), c.take<unsigned char>(n), c.take<unsigned char>(n)};     // (in this order)
+    if (order == GNR_SELECT_ORDER_SCORE) { k.ka = c.take<unsigned>(n); k.kb = c.take<unsigned>(n); k.ia = c.take<int>(n); k.ib = c.take<int>(n); }
+    k.total = c.total();
+    return k;
+}
+
+extern "C" size_t gnr_grasp_select_workspace_bytes(int B, int R) {
+    return B < 1 || R < 1 ? 0 : carve_select(B, R, GNR_SELECT_ORDER_INDEX, nullptr).total;
 }
 
 extern "C" size_t gnr_grasp_select_v2_workspace_bytes(int B, int R, int order) {
-    if (B < 1 || R < 1) return 0;
-    const size_t n = (size_t)B * R * R * R;
-    return gnr_grasp_select_workspace_bytes(B, R) + (order == GNR_SELECT_ORDER_SCORE ? 4 * al256(n * 4) : 0);
+    return B < 1 || R < 1 ? 0 : carve_select(B, R, order, nullptr).total;
 }
 
 // Both select entry points: `who` = 0 the original call (its refusals keep their texts), 1 the v2 call.
 static int select_impl(int who, const float* tsdf, const float* qual, const float* rot, const float* width, int B, int R,
                        const GnrSelectParams* p, float outside, int order, int top_k, float* qual_out, int* count, int* index,
                        float* score, float* quat, float* width_out, int max_n, void* ws, size_t ws_bytes, void* stream) {
-    static const char* const text[2][3] = {
-        {"gnr_grasp_select_fwd: null pointer", "gnr_grasp_select_fwd: bad B / R / max_n", "gnr_grasp_select_fwd: bad filter parameters"},
-        {"gnr_grasp_select_v2_fwd: null pointer", "gnr_grasp_select_v2_fwd: bad B / R / max_n", "gnr_grasp_select_v2_fwd: bad filter parameters"}};
+    const Refuse no{who ? "gnr_grasp_select_v2_fwd" : "gnr_grasp_select_fwd"};
     if (!tsdf || !qual || !rot || !width || !p || !qual_out || !count || !index || !score || !quat || !width_out || !ws)
-        return fail(GNR_ERR_ARG, text[who][0]);
-    if (B < 1 || R < 2 || R > 256 || max_n < 1) return fail(GNR_ERR_SHAPE, text[who][1]);
+        return no(GNR_ERR_ARG, "null pointer");
+    if (B < 1 || !lattice_ok(R) || max_n < 1) return no(GNR_ERR_SHAPE, "bad B / R / max_n");
     if (p->gauss_radius < 0 || p->gauss_radius > GNR_GAUSS_MAX_RADIUS || p->dilate_iterations < 0 || p->max_filter_size < 1 ||
         p->max_filter_size > 16)
-        return fail(GNR_ERR_ARG, text[who][2]);
+        return no(GNR_ERR_ARG, "bad filter parameters");
+    // (the next three are the v2 call's alone: the original call passes GNR_SELECT_ORDER_INDEX and top_k 0)
     if (order != GNR_SELECT_ORDER_INDEX && order != GNR_SELECT_ORDER_SCORE)
-        return fail(GNR_ERR_ARG, "gnr_grasp_select_v2_fwd: order must be GNR_SELECT_ORDER_INDEX or GNR_SELECT_ORDER_SCORE");
-    if (top_k < 0) return fail(GNR_ERR_ARG, "gnr_grasp_select_v2_fwd: top_k must be >= 0 (0: as many as max_n)");
+        return no(GNR_ERR_ARG, "order must be GNR_SELECT_ORDER_INDEX or GNR_SELECT_ORDER_SCORE");
+    if (top_k < 0) return no(GNR_ERR_ARG, "top_k must be >= 0 (0: as many as max_n)");
     if (order == GNR_SELECT_ORDER_SCORE && R > GNR_SELECT_SCORE_MAX_R)
-        return fail(GNR_ERR_SHAPE, "gnr_grasp_select_v2_fwd: GNR_SELECT_ORDER_SCORE takes R <= 64 (2^18 voxels per scene to rank)");
-    if (ws_bytes < gnr_grasp_select_v2_workspace_bytes(B, R, order)) return fail(GNR_ERR_WORKSPACE, "workspace too small");
+        return no(GNR_ERR_SHAPE, "GNR_SELECT_ORDER_SCORE takes R <= 64 (2^18 voxels per scene to rank)");
+    const SelectWork k = carve_select(B, R, order, ws);
+    if (ws_bytes < k.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)B * R * R * R;
-    char* base = (char*)ws;
-    float* fa = (float*)base;                      base += al256(n * sizeof(float));
-    float* fb = (float*)base;                      base += al256(n * sizeof(float));
-    unsigned char* xa = (unsigned char*)base;      base += al256(n);
-    unsigned char* xb = (unsigned char*)base;      base += al256(n);
-    unsigned char* mk = (unsigned char*)base;      base += al256(n);
+    float *fa = k.fa, *fb = k.fb;
+    unsigned char *xa = k.xa, *xb = k.xb, *mk = k.mk;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     GaussW g;
     g.radius = p->gauss_radius;
@@ -330,11 +334,7 @@ static int select_impl(int who, const float* tsdf, const float* qual, const floa
     const int limit = top_k > 0 && top_k < max_n ? top_k : max_n;
     if (order == GNR_SELECT_ORDER_INDEX)
         return launch<k_compact>(nullptr, st, dim3(B), dim3(1024), 0, xout, fb, rot, width, R, max_n, limit, count, index, score, quat, width_out);
-    unsigned* ka = (unsigned*)base;                base += al256(n * 4);
-    unsigned* kb = (unsigned*)base;                base += al256(n * 4);
-    int* ia = (int*)base;                          base += al256(n * 4);
-    int* ib = (int*)base;
-    return launch<k_rank>(nullptr, st, dim3(B), dim3(1024), 0, xout, fb, rot, width, R, max_n, limit, ka, kb, ia, ib, count, index, score,
+    return launch<k_rank>(nullptr, st, dim3(B), dim3(1024), 0, xout, fb, rot, width, R, max_n, limit, k.ka, k.kb, k.ia, k.ib, count, index, score,
                           quat, width_out);
 }
 
@@ -352,23 +352,31 @@ extern "C" int gnr_grasp_select_v2_fwd(const float* tsdf, const float* qual, con
                        p ? p->top_k : 0, qual_out, count, index, score, quat, width_out, max_n, ws, ws_bytes, stream);
 }
 
+// the surface cloud's workspace: the chunk counts [B, chunks of 1024 voxels]
+struct SurfaceWork { int* chunk; size_t total; };
+
+static SurfaceWork carve_surface(int B, int R, void* base) {
+    Carve c(base);
+    return SurfaceWork{c.take<int>(B * (((size_t)R * R * R + 1023) / 1024)), c.total()};
+}
+
 extern "C" size_t gnr_surface_points_workspace_bytes(int B, int R) {
-    if (B < 1 || R < 1) return 0;
-    const size_t nc = ((size_t)R * R * R + 1023) / 1024;
-    return al256((size_t)B * nc * sizeof(int));
+    return B < 1 || R < 1 ? 0 : carve_surface(B, R, nullptr).total;
 }
 
 extern "C" int gnr_surface_points_fwd(const float* vol, int B, int R, const GnrSurfaceParams* p, int* count, int* index, double* points,
                                       float* colors, int max_n, void* ws, size_t ws_bytes, void* stream) {
-    if (!vol || !p || !count || !index || !points || !colors || !ws) return fail(GNR_ERR_ARG, "gnr_surface_points_fwd: null pointer");
-    if (B < 1 || B > 65535 || R < 1 || R > 256 || max_n < 1) return fail(GNR_ERR_SHAPE, "gnr_surface_points_fwd: bad B / R / max_n (R <= 256)");
+    const Refuse no{"gnr_surface_points_fwd"};
+    if (!vol || !p || !count || !index || !points || !colors || !ws) return no(GNR_ERR_ARG, "null pointer");
+    if (!scenes_ok(B) || R < 1 || R > MAX_LATTICE || max_n < 1) return no(GNR_ERR_SHAPE, "bad B / R / max_n (R <= 256)");
     if (p->color_mode != GNR_SURFACE_COLOR_FIXED && p->color_mode != GNR_SURFACE_COLOR_VALUE)
-        return fail(GNR_ERR_ARG, "gnr_surface_points_fwd: color_mode must be GNR_SURFACE_COLOR_FIXED or GNR_SURFACE_COLOR_VALUE");
-    if (ws_bytes < gnr_surface_points_workspace_bytes(B, R)) return fail(GNR_ERR_WORKSPACE, "workspace too small");
+        return no(GNR_ERR_ARG, "color_mode must be GNR_SURFACE_COLOR_FIXED or GNR_SURFACE_COLOR_VALUE");
+    const SurfaceWork k = carve_surface(B, R, ws);
+    if (ws_bytes < k.total) return fail(GNR_ERR_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)R * R * R;
     const int nc = (int)((n + 1023) / 1024);
-    int* chunk = (int*)ws;
+    int* chunk = k.chunk;
     SurfColor col;
     col.value_map = p->color_mode == GNR_SURFACE_COLOR_VALUE;
     for (int c = 0; c < 3; ++c) col.rgb[c] = p->color[c];
@@ -381,8 +389,9 @@ extern "C" int gnr_surface_points_fwd(const float* vol, int B, int R, const GnrS
 }
 
 extern "C" int gnr_surface_gradient_fwd(const float* grad, const int* index, const int* count, int B, int R, int max_points, float* out, void* stream) {
-    if (!grad || !index || !count || !out) return fail(GNR_ERR_ARG, "gnr_surface_gradient_fwd: null pointer");
-    if (B < 1 || B > 65535 || R < 1 || R > 256 || max_points < 0) return fail(GNR_ERR_SHAPE, "gnr_surface_gradient_fwd: bad B / R / max_points (1 <= R <= 256, max_points >= 0)");
+    const Refuse no{"gnr_surface_gradient_fwd"};
+    if (!grad || !index || !count || !out) return no(GNR_ERR_ARG, "null pointer");
+    if (!scenes_ok(B) || R < 1 || R > MAX_LATTICE || max_points < 0) return no(GNR_ERR_SHAPE, "bad B / R / max_points (1 <= R <= 256, max_points >= 0)");
     if (max_points == 0) return GNR_OK;
     return launch<k_surf_gradient>(nullptr, (hipStream_t)stream, dim3((max_points + 255) / 256, B), dim3(256), 0, grad, index, count, R, max_points, out);
 }

@@ -123,25 +123,25 @@ using namespace gnr_raycast;
 
 extern "C" int gnr_volume_raycast_fwd(const GnrRaycastParams* p, const float* vol, const float* grad, const float* poses, const float* Ks,
                                       float* depth, float* gradient, void* stream) {
-    if (!p || !vol || !poses || !Ks || !depth) return fail(GNR_ERR_ARG, "gnr_volume_raycast_fwd: null pointer");
-    if ((grad == nullptr) != (gradient == nullptr))
-        return fail(GNR_ERR_ARG, "gnr_volume_raycast_fwd: grad and gradient must be both given or both NULL");
-    if (p->B < 1 || p->B > 65535) return fail(GNR_ERR_SHAPE, "gnr_volume_raycast_fwd: B must be in 1..65535");
-    if (p->V < 1) return fail(GNR_ERR_SHAPE, "gnr_volume_raycast_fwd: V must be >= 1");
-    if (p->h < 1 || p->w < 1) return fail(GNR_ERR_SHAPE, "gnr_volume_raycast_fwd: h and w must be >= 1");
-    if (p->R < 2 || p->R > 256) return fail(GNR_ERR_SHAPE, "gnr_volume_raycast_fwd: R must be in 2..256");
-    if (p->bisections < 0 || p->bisections > 32) return fail(GNR_ERR_ARG, "gnr_volume_raycast_fwd: bisections must be in 0..32");
+    const Refuse no{"gnr_volume_raycast_fwd"};
+    if (!p || !vol || !poses || !Ks || !depth) return no(GNR_ERR_ARG, "null pointer");
+    if ((grad == nullptr) != (gradient == nullptr)) return no(GNR_ERR_ARG, "grad and gradient must be both given or both NULL");
+    if (int rc = check_scenes(no, GNR_ERR_SHAPE, p->B)) return rc;
+    if (p->V < 1) return no(GNR_ERR_SHAPE, "V must be >= 1");
+    if (p->h < 1 || p->w < 1) return no(GNR_ERR_SHAPE, "h and w must be >= 1");
+    if (int rc = check_lattice(no, GNR_ERR_SHAPE, p->R)) return rc;
+    if (p->bisections < 0 || p->bisections > 32) return no(GNR_ERR_ARG, "bisections must be in 0..32");
     if (!isfinite(p->scale) || !isfinite(p->step) || !(p->scale > 0.0) || !(p->step > 0.0))
-        return fail(GNR_ERR_ARG, "gnr_volume_raycast_fwd: scale and step must be finite and > 0");
+        return no(GNR_ERR_ARG, "scale and step must be finite and > 0");
     if (!isfinite(p->iso) || !isfinite(p->origin[0]) || !isfinite(p->origin[1]) || !isfinite(p->origin[2]))
-        return fail(GNR_ERR_ARG, "gnr_volume_raycast_fwd: iso and origin must be finite");
-    if (!(p->near_s >= 0.0) || !(p->far_s > p->near_s)) return fail(GNR_ERR_ARG, "gnr_volume_raycast_fwd: near_s must be >= 0 and far_s > near_s");
+        return no(GNR_ERR_ARG, "iso and origin must be finite");
+    if (!(p->near_s >= 0.0) || !(p->far_s > p->near_s)) return no(GNR_ERR_ARG, "near_s must be >= 0 and far_s > near_s");
     const double most = ceil(sqrt(3.0) * (double)(p->R - 1) / p->step) + 1.0;   // the march's loop bound
     if (!(most <= (double)GNR_RAYCAST_MAX_SAMPLES))
-        return fail(GNR_ERR_ARG, "gnr_volume_raycast_fwd: step too small, a ray would take more than GNR_RAYCAST_MAX_SAMPLES (65536) samples");
+        return no(GNR_ERR_ARG, "step too small, a ray would take more than GNR_RAYCAST_MAX_SAMPLES (65536) samples");
     const unsigned long long tiles_x = ((unsigned long long)p->w + 7) / 8, tiles_y = ((unsigned long long)p->h + 7) / 8;
     const unsigned long long blocks = (tiles_x * tiles_y + 3) / 4;
-    if (tiles_x * tiles_y > (1ull << 28)) return fail(GNR_ERR_SHAPE, "gnr_volume_raycast_fwd: h and w must give at most 2^28 tiles of 8 x 8 pixels");
+    if (tiles_x * tiles_y > (1ull << 28)) return no(GNR_ERR_SHAPE, "h and w must give at most 2^28 tiles of 8 x 8 pixels");
     Shape sh{p->V, p->h, p->w, p->R, p->bisections, (int)most, (unsigned)tiles_x, (unsigned)(tiles_x * tiles_y), (unsigned)blocks, (double)p->iso, p->scale, p->step,
              p->near_s, p->far_s, {p->origin[0], p->origin[1], p->origin[2]}};
     const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)p->B, (unsigned)(p->V < 64 ? p->V : 64));

@@ -185,12 +185,11 @@ __global__ __launch_bounds__(256) void k_surface_color(const float* __restrict__
     }
 }
 
-static int check(const char* fn, char (&text)[160], const GnrSurfaceColorParams* p, double& most) {
-    auto no = [&](int code, const char* what) { snprintf(text, sizeof text, "%s: %s", fn, what); return fail(code, text); };
-    if (p->B < 1 || p->B > 65535) return no(GNR_ERR_SHAPE, "B must be in 1..65535");
+static int check(const Refuse& no, const GnrSurfaceColorParams* p, double& most) {
+    if (int rc = check_scenes(no, GNR_ERR_SHAPE, p->B)) return rc;
     if (p->V < 1 || p->V > 32) return no(GNR_ERR_SHAPE, "V must be in 1..32 (one bit of the view mask each)");
     if (p->H < 2 || p->W < 2) return no(GNR_ERR_SHAPE, "H and W must be >= 2");
-    if (p->R < 2 || p->R > 256) return no(GNR_ERR_SHAPE, "R must be in 2..256");
+    if (int rc = check_lattice(no, GNR_ERR_SHAPE, p->R)) return rc;
     if (!isfinite(p->scale) || !isfinite(p->step) || !(p->scale > 0.0) || !(p->step > 0.0))
         return no(GNR_ERR_ARG, "scale and step must be finite and > 0");
     if (!isfinite(p->bias) || !(p->bias >= 0.0)) return no(GNR_ERR_ARG, "bias must be finite and >= 0");
@@ -218,14 +217,12 @@ using namespace gnr_surface_color;
 extern "C" int gnr_surface_color_points_fwd(const GnrSurfaceColorParams* p, const float* vol, const double* points, const int* count,
                                             int count_stride, int max_n, const float* images, const float* poses, const float* Ks,
                                             float* colors, float* weight, int* views, void* stream) {
-    const char* fn = "gnr_surface_color_points_fwd";
-    char text[160];
-    if (!p || !vol || !points || !count || !images || !poses || !Ks || !colors || !weight || !views)
-        return fail(GNR_ERR_ARG, "gnr_surface_color_points_fwd: null pointer");
+    const Refuse no{"gnr_surface_color_points_fwd"};
+    if (!p || !vol || !points || !count || !images || !poses || !Ks || !colors || !weight || !views) return no(GNR_ERR_ARG, "null pointer");
     double most = 0.0;
-    if (const int rc = check(fn, text, p, most)) return rc;
-    if (max_n < 1) return fail(GNR_ERR_SHAPE, "gnr_surface_color_points_fwd: max_n must be >= 1");
-    if (count_stride < 1) return fail(GNR_ERR_ARG, "gnr_surface_color_points_fwd: count_stride must be >= 1");
+    if (const int rc = check(no, p, most)) return rc;
+    if (max_n < 1) return no(GNR_ERR_SHAPE, "max_n must be >= 1");
+    if (count_stride < 1) return no(GNR_ERR_ARG, "count_stride must be >= 1");
     Shape sh = shape_of(p, most);
     sh.pixels = 0; sh.max_n = max_n; sh.count_stride = count_stride;
     sh.blocks = (unsigned)(((unsigned long long)max_n + 255) / 256);
@@ -237,17 +234,15 @@ extern "C" int gnr_surface_color_points_fwd(const GnrSurfaceColorParams* p, cons
 extern "C" int gnr_surface_color_pixels_fwd(const GnrSurfaceColorParams* p, const float* vol, const float* depth, const float* cam_poses,
                                             const float* cam_Ks, int Vc, int hc, int wc, const float* images, const float* poses,
                                             const float* Ks, float* colors, float* weight, int* views, void* stream) {
-    const char* fn = "gnr_surface_color_pixels_fwd";
-    char text[160];
+    const Refuse no{"gnr_surface_color_pixels_fwd"};
     if (!p || !vol || !depth || !cam_poses || !cam_Ks || !images || !poses || !Ks || !colors || !weight || !views)
-        return fail(GNR_ERR_ARG, "gnr_surface_color_pixels_fwd: null pointer");
+        return no(GNR_ERR_ARG, "null pointer");
     double most = 0.0;
-    if (const int rc = check(fn, text, p, most)) return rc;
-    if (Vc < 1) return fail(GNR_ERR_SHAPE, "gnr_surface_color_pixels_fwd: Vc must be >= 1");
-    if (hc < 1 || wc < 1) return fail(GNR_ERR_SHAPE, "gnr_surface_color_pixels_fwd: hc and wc must be >= 1");
+    if (const int rc = check(no, p, most)) return rc;
+    if (Vc < 1) return no(GNR_ERR_SHAPE, "Vc must be >= 1");
+    if (hc < 1 || wc < 1) return no(GNR_ERR_SHAPE, "hc and wc must be >= 1");
     const unsigned long long tiles_x = ((unsigned long long)wc + 7) / 8, tiles_y = ((unsigned long long)hc + 7) / 8;
-    if (tiles_x * tiles_y > (1ull << 28))
-        return fail(GNR_ERR_SHAPE, "gnr_surface_color_pixels_fwd: hc and wc must give at most 2^28 tiles of 8 x 8 pixels");
+    if (tiles_x * tiles_y > (1ull << 28)) return no(GNR_ERR_SHAPE, "hc and wc must give at most 2^28 tiles of 8 x 8 pixels");
     Shape sh = shape_of(p, most);
     sh.pixels = 1; sh.Vc = Vc; sh.hc = hc; sh.wc = wc;
     sh.tiles_x = (unsigned)tiles_x; sh.tiles = (unsigned)(tiles_x * tiles_y); sh.blocks = (unsigned)((tiles_x * tiles_y + 3) / 4);

@@ -96,9 +96,10 @@ __global__ __launch_bounds__(256) void k_tsdf_reset(float* __restrict__ tsdf, fl
 using namespace gnr_tsdf;
 
 extern "C" int gnr_tsdf_reset(int B, int R, float* tsdf, float* weight, void* stream) {
-    if (!tsdf || !weight) return fail(GNR_ERR_ARG, "gnr_tsdf_reset: null pointer");
-    if (B < 1 || B > 65535) return fail(GNR_ERR_SHAPE, "gnr_tsdf_reset: B must be in 1..65535");
-    if (R < 2 || R > 256) return fail(GNR_ERR_SHAPE, "gnr_tsdf_reset: R must be in 2..256");
+    const Refuse no{"gnr_tsdf_reset"};
+    if (!tsdf || !weight) return no(GNR_ERR_ARG, "null pointer");
+    if (int rc = check_scenes(no, GNR_ERR_SHAPE, B)) return rc;
+    if (int rc = check_lattice(no, GNR_ERR_SHAPE, R)) return rc;
     const size_t n = (size_t)R * R * R;
     return launch<k_tsdf_reset>("k_tsdf_reset@gnr_tsdf_reset", (hipStream_t)stream, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, tsdf,
                                 weight, n);
@@ -106,15 +107,16 @@ extern "C" int gnr_tsdf_reset(int B, int R, float* tsdf, float* weight, void* st
 
 extern "C" int gnr_tsdf_integrate(const GnrTsdfParams* p, const void* depth, const float* poses, const float* Ks, const float* origin,
                                   float* tsdf, float* weight, void* stream) {
-    if (!p || !depth || !poses || !Ks || !origin || !tsdf || !weight) return fail(GNR_ERR_ARG, "gnr_tsdf_integrate: null pointer");
-    if (p->B < 1 || p->B > 65535) return fail(GNR_ERR_SHAPE, "gnr_tsdf_integrate: B must be in 1..65535");
-    if (p->R < 2 || p->R > 256) return fail(GNR_ERR_SHAPE, "gnr_tsdf_integrate: R must be in 2..256");
-    if (p->V < 1) return fail(GNR_ERR_SHAPE, "gnr_tsdf_integrate: V must be >= 1");
-    if (p->h < 1 || p->w < 1) return fail(GNR_ERR_SHAPE, "gnr_tsdf_integrate: h and w must be >= 1");
+    const Refuse no{"gnr_tsdf_integrate"};
+    if (!p || !depth || !poses || !Ks || !origin || !tsdf || !weight) return no(GNR_ERR_ARG, "null pointer");
+    if (int rc = check_scenes(no, GNR_ERR_SHAPE, p->B)) return rc;
+    if (int rc = check_lattice(no, GNR_ERR_SHAPE, p->R)) return rc;
+    if (p->V < 1) return no(GNR_ERR_SHAPE, "V must be >= 1");
+    if (p->h < 1 || p->w < 1) return no(GNR_ERR_SHAPE, "h and w must be >= 1");
     if (p->depth_dtype != GNR_DEPTH_F32 && p->depth_dtype != GNR_DEPTH_U16)
-        return fail(GNR_ERR_ARG, "gnr_tsdf_integrate: depth_dtype must be GNR_DEPTH_F32 or GNR_DEPTH_U16");
+        return no(GNR_ERR_ARG, "depth_dtype must be GNR_DEPTH_F32 or GNR_DEPTH_U16");
     if (!(p->voxel_size > 0.0) || !(p->sdf_trunc > 0.0) || !(p->depth_scale > 0.0) || !(p->depth_trunc > 0.0))
-        return fail(GNR_ERR_ARG, "gnr_tsdf_integrate: voxel_size, sdf_trunc, depth_scale and depth_trunc must be > 0");
+        return no(GNR_ERR_ARG, "voxel_size, sdf_trunc, depth_scale and depth_trunc must be > 0");
     const Shape s{p->V, p->h, p->w, p->R, p->voxel_size, p->sdf_trunc, p->depth_scale, p->depth_trunc};
     const size_t n = (size_t)p->R * p->R * p->R;
     const dim3 grid((unsigned)((n + 255) / 256), (unsigned)p->B), block(256);
@@ -126,10 +128,11 @@ extern "C" int gnr_tsdf_integrate(const GnrTsdfParams* p, const void* depth, con
 }
 
 extern "C" int gnr_tsdf_grid(int B, int R, const float* tsdf, const float* weight, int mode, float* out, void* stream) {
-    if (!tsdf || !weight || !out) return fail(GNR_ERR_ARG, "gnr_tsdf_grid: null pointer");
-    if (B < 1 || B > 65535) return fail(GNR_ERR_SHAPE, "gnr_tsdf_grid: B must be in 1..65535");
-    if (R < 2 || R > 256) return fail(GNR_ERR_SHAPE, "gnr_tsdf_grid: R must be in 2..256");
-    if (mode != GNR_TSDF_GRID && mode != GNR_TSDF_SDF_LABEL) return fail(GNR_ERR_ARG, "gnr_tsdf_grid: mode must be GNR_TSDF_GRID or GNR_TSDF_SDF_LABEL");
+    const Refuse no{"gnr_tsdf_grid"};
+    if (!tsdf || !weight || !out) return no(GNR_ERR_ARG, "null pointer");
+    if (int rc = check_scenes(no, GNR_ERR_SHAPE, B)) return rc;
+    if (int rc = check_lattice(no, GNR_ERR_SHAPE, R)) return rc;
+    if (mode != GNR_TSDF_GRID && mode != GNR_TSDF_SDF_LABEL) return no(GNR_ERR_ARG, "mode must be GNR_TSDF_GRID or GNR_TSDF_SDF_LABEL");
     const size_t n = (size_t)R * R * R;
     return launch<k_tsdf_grid>("k_tsdf_grid@gnr_tsdf_grid", (hipStream_t)stream, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, tsdf,
                                weight, mode == GNR_TSDF_SDF_LABEL ? 1 : 0, out, n);

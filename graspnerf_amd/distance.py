@@ -17,11 +17,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import DeviceOp, checked_params, picked, volume_batch
-from .hand import HAND_DEFAULTS, HandClearance, checked_hand, hand_from_rows, hand_rows
-from .objects import PLAN_VOXEL_SIZE, labels_batch
+from .grasp_post import (SOLID_DEFAULTS, DeviceOp, _host, checked_params, checked_solid, labels_batch, picked, solid_fields, split_params,
+                         volume_batch)
+from .hand import HAND_DEFAULTS, HandClearance, checked_hand, hand_from_rows, hand_rows, plan_rows
+from .objects import PLAN_VOXEL_SIZE
 
-DISTANCE_DEFAULTS = dict(level=0.0, lower=None, z_min=0, surface_offset=0.5, signed=True)
+DISTANCE_DEFAULTS = dict(SOLID_DEFAULTS, surface_offset=0.5, signed=True)
 DISTANCE_ROW_TYPES = dict(d2_solid=torch.int32, nearest_solid=torch.int32, d2_free=torch.int32, nearest_free=torch.int32, esdf=torch.float32,
                           nearest_label=torch.int32)
 UNSIGNED_ROWS, SIGNED_ROWS = ('d2_solid', 'nearest_solid'), ('d2_free', 'nearest_free', 'esdf')
@@ -31,18 +32,12 @@ PLAN_DEFAULTS = dict(margin=0.0)                                               #
 def checked_distance(level=0.0, lower=None, z_min=0, surface_offset=0.5, signed=True):
     """The transform's parameters, checked before anything touches the device (the library refuses the same; z_min <= R is the
     library's, which knows R)."""
-    if not math.isfinite(level):
-        raise ValueError(f'distance level must be finite, got {level!r}')
-    if lower is not None and math.isnan(lower):
-        raise ValueError(f'distance lower must be None (no lower bound) or a number, got {lower!r}')
-    if isinstance(z_min, bool) or int(z_min) != z_min or z_min < 0:
-        raise ValueError(f'distance z_min must be an integer >= 0, got {z_min!r}')
+    solid = checked_solid('distance', level, lower, z_min)
     if not (math.isfinite(surface_offset) and surface_offset >= 0):
         raise ValueError(f'distance surface_offset must be finite and >= 0 voxels, got {surface_offset!r}')
     if not isinstance(signed, bool):
         raise ValueError(f'distance signed must be True or False, got {signed!r}')
-    return dict(level=float(level), lower=None if lower is None else float(lower), z_min=int(z_min), surface_offset=float(surface_offset),
-                signed=signed)
+    return dict(solid, surface_offset=float(surface_offset), signed=signed)
 
 
 def distance_params(distance, **more):
@@ -84,8 +79,7 @@ class VolumeDistance(DeviceOp):
         q = checked_distance(level, lower, z_min, surface_offset, signed)
         scale = checked_scale(scale)
         vol, B, R = volume_batch(vol, d)
-        if q['z_min'] > R:
-            raise ValueError(f'distance z_min must be in 0..R = {R}, got {z_min!r}')
+        solid = solid_fields('distance', q, R, z_min)
         if labels is not None:
             labels, Bl, Rl = labels_batch(labels, d)
             if (Bl, Rl) != (B, R):
@@ -95,8 +89,7 @@ class VolumeDistance(DeviceOp):
         for k in names:
             if k not in out:
                 out[k] = torch.zeros(B, R, R, R, dtype=DISTANCE_ROW_TYPES[k], device=d)
-        p = _lib.GnrDistanceParams(level=q['level'], lower=-math.inf if q['lower'] is None else q['lower'], scale=scale,
-                                   surface_offset=q['surface_offset'], z_min=q['z_min'])
+        p = _lib.GnrDistanceParams(**solid, scale=scale, surface_offset=q['surface_offset'])
         ws, ws_bytes = self._workspace(self.L.gnr_volume_distance_workspace_bytes(B, R))
         ptr = lambda k: out[k].data_ptr() if k in names else None
         rc = self.L.gnr_volume_distance_fwd(C.byref(p), vol.data_ptr(), None if labels is None else labels.data_ptr(), B, R,
@@ -155,38 +148,29 @@ def distance_of_plan(tsdf_vol, grasps, *, voxel_size=PLAN_VOXEL_SIZE, objects=No
     negative: how deep it is in), `approach_clearance_m` [n] float32 (the same over the approach), `collision_free_m` [n] bool =
     approach_clearance_m > margin, hand_from_rows' `hand_inside` and `hand_worst`, and with objects `nearest_object` [n] int32
     (nearest_label at the grasp's own voxel).  HandClearance clips at 1.0: a margin reads at most 1 m."""
-    every = {**DISTANCE_DEFAULTS, **HAND_DEFAULTS, **PLAN_DEFAULTS}
-    unknown = sorted(set(params) - set(every))
-    if unknown:
-        raise TypeError(f'unknown distance parameters {unknown}; it takes {sorted(every)}')
-    q = distance_params(picked({**every, **params}, DISTANCE_DEFAULTS))
+    params = split_params('distance', params, DISTANCE_DEFAULTS, HAND_DEFAULTS, PLAN_DEFAULTS)
+    q = distance_params(picked(params, DISTANCE_DEFAULTS))
     if not q['signed']:
         raise ValueError('distance_of_plan reads the hand\'s margin from esdf: signed must be True')
-    hand = picked({**every, **params}, HAND_DEFAULTS)
+    hand = picked(params, HAND_DEFAULTS)
     checked_hand(**hand)
-    margin = float({**every, **params}['margin'])
+    margin = float(params['margin'])
     if not math.isfinite(margin):
         raise ValueError(f'distance margin must be finite metres, got {margin!r}')
     scale = checked_scale(voxel_size)
-    index, quat, width = np.asarray(grasps['index']), np.asarray(grasps['quat']), np.asarray(grasps['width'])
-    n = len(index)
     d = torch.device(device)
     vol, B, R = volume_batch(tsdf_vol, d)
     if B != 1:
         raise ValueError(f'distance_of_plan takes the volume of one scene, got {B}')
     labels = None if objects is None else torch.as_tensor(np.asarray(_labels_of(objects)), dtype=torch.int32).reshape(1, R, R, R)
     res = VolumeDistance(d)(vol, scale=scale, labels=labels, **q)
-    rows = max(n, 1)                                                           # (the library takes no empty buffer: one row that the count leaves out)
-    pos, qt, wd = np.zeros((1, rows, 3), np.float64), np.zeros((1, rows, 4), np.float32), np.zeros((1, rows), np.float32)
-    pos[0, :n], qt[0, :n], wd[0, :n] = index.reshape(n, 3), quat.reshape(n, 4), (width.reshape(n) / np.float32(voxel_size)).astype(np.float32)
-    count = torch.tensor([n], dtype=torch.int32, device=d)
+    pos, qt, wd, count, n = plan_rows(grasps, voxel_size, d)
     hres = HandClearance(d)(res['esdf'], pos, qt, wd, count, scale=scale, **hand)
-    host = lambda r: {k: v.cpu().numpy() for k, v in r.items()}
-    field = distance_from_rows(host(distance_rows(res, 0)), scale)
-    cols = hand_from_rows(host(hand_rows(hres, 0, n)), margin)
+    field = distance_from_rows(_host(distance_rows(res, 0)), scale)
+    cols = hand_from_rows(_host(hand_rows(hres, 0, n)), margin)
     columns = {'clearance_m': cols['clearance'], 'approach_clearance_m': cols['approach_clearance'], 'collision_free_m': cols['collision_free'],
                'hand_inside': cols['hand_inside'], 'hand_worst': cols['hand_worst']}
     if labels is not None:
-        at = index.reshape(n, 3).astype(np.int64)
+        at = np.asarray(grasps['index']).reshape(n, 3).astype(np.int64)
         columns['nearest_object'] = field['nearest_label'][at[:, 0], at[:, 1], at[:, 2]].astype(np.int32)
     return field, columns

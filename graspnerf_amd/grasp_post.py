@@ -6,6 +6,7 @@ draw_utils.py is here too: `process` with its three thresholds (GRASP_UTILS_PROC
 triangle mesh of the volume's iso-surface (MeshExtractor, csrc/gnr_mesh.hip) has no counterpart in the reference."""
 import ctypes as C
 import inspect
+import math
 
 import numpy as np
 import torch
@@ -35,13 +36,22 @@ class DeviceOp:
         return self._ws.data_ptr(), self._ws.numel()
 
 
+def _lattice_batch(x, device, dtype, noun):
+    x = torch.as_tensor(x, dtype=dtype, device=device).contiguous()
+    R = x.shape[-1]
+    if x.dim() < 3 or tuple(x.shape[-3:]) != (R, R, R) or x.numel() % R ** 3:
+        raise ValueError(f'{noun} must be [B,R,R,R], got {tuple(x.shape)}')
+    return x, x.numel() // R ** 3, R
+
+
 def volume_batch(vol, device):
     """vol [B,R,R,R] (or [B,1,R,R,R], or one [R,R,R]) -> (contiguous float32 device tensor, B, R)."""
-    vol = torch.as_tensor(vol, dtype=torch.float32, device=device).contiguous()
-    R = vol.shape[-1]
-    if vol.dim() < 3 or tuple(vol.shape[-3:]) != (R, R, R) or vol.numel() % R ** 3:
-        raise ValueError(f'vol must be [B,R,R,R], got {tuple(vol.shape)}')
-    return vol, vol.numel() // R ** 3, R
+    return _lattice_batch(vol, device, torch.float32, 'vol')
+
+
+def labels_batch(labels, device):
+    """labels [B,R,R,R] (or one [R,R,R]) -> (contiguous int32 device tensor, B, R): objects.VolumeObjects' `labels`."""
+    return _lattice_batch(labels, device, torch.int32, 'labels')
 
 
 def gradient_batch(gradient, B, R, device):
@@ -89,6 +99,35 @@ def same_params(asked, have):
 def picked(params, defaults):
     """The entries of `params` under the keys of one defaults dict: the keywords of the one call those are the defaults of."""
     return {k: params[k] for k in defaults}
+
+
+def split_params(what, params, *defaults):
+    """The keywords of a call that serves several operators -> every key of the defaults dicts with its value (picked() then takes
+    each operator's share); a key none of them has is checked_params' TypeError."""
+    return checked_params(what, dict(params), {k: v for d in defaults for k, v in d.items()})
+
+
+SOLID_DEFAULTS = dict(level=0.0, lower=None, z_min=0)      # the solid rule of the volume operators: lower < v < level and k >= z_min
+
+
+def checked_solid(what, level, lower, z_min):
+    """The solid rule's parameters of operator `what`, checked before anything touches the device (the library refuses the same)
+    -> them as float, None or float, int."""
+    if not math.isfinite(level):
+        raise ValueError(f'{what} level must be finite, got {level!r}')
+    if lower is not None and math.isnan(lower):
+        raise ValueError(f'{what} lower must be None (no lower bound) or a number, got {lower!r}')
+    if isinstance(z_min, bool) or int(z_min) != z_min or z_min < 0:
+        raise ValueError(f'{what} z_min must be an integer >= 0, got {z_min!r}')
+    return dict(level=float(level), lower=None if lower is None else float(lower), z_min=int(z_min))
+
+
+def solid_fields(what, q, R, z_min):
+    """checked_solid's dict, now that R is known -> the level, lower and z_min fields of the library's parameter struct (z_min: as the
+    caller wrote it, for the text)."""
+    if q['z_min'] > R:
+        raise ValueError(f'{what} z_min must be in 0..R = {R}, got {z_min!r}')
+    return dict(level=q['level'], lower=-math.inf if q['lower'] is None else q['lower'], z_min=q['z_min'])
 
 
 def _call_defaults(cls, *skip):

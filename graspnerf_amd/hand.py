@@ -70,6 +70,19 @@ def selection_pos(sel):
     return sel['index'].double()
 
 
+def plan_rows(grasps, voxel_size, device):
+    """The grasps dict of a plan (one scene; grasps_from_selection's conventions: `index` the voxel of each grasp, `quat` (x, y, z, w),
+    `width` in metres) -> (pos [1,rows,3] float64, quat [1,rows,4] float32, width [1,rows] float32 in voxels, count [1] int32 on the
+    device, n): the rows the checks of grasps take.  The width goes back to voxels by / voxel_size in float32, the selection's own
+    format; rows = max(n, 1): the library takes no empty buffer, so no grasp is one row that the count leaves out."""
+    index, quat, width = np.asarray(grasps['index']), np.asarray(grasps['quat']), np.asarray(grasps['width'])
+    n = len(index)
+    rows = max(n, 1)
+    pos, qt, wd = np.zeros((1, rows, 3), np.float64), np.zeros((1, rows, 4), np.float32), np.zeros((1, rows), np.float32)
+    pos[0, :n], qt[0, :n], wd[0, :n] = index.reshape(n, 3), quat.reshape(n, 4), (width.reshape(n) / np.float32(voxel_size)).astype(np.float32)
+    return pos, qt, wd, torch.tensor([n], dtype=torch.int32, device=device), n
+
+
 def checked_rows(pos, quat, width, count, top_k, B, d):
     """The rows of grasps of B scenes on device d, as the kernels read them -> (pos [B,n,3] float64, quat [B,n,4] float32, width [B,n]
     float32, n); count and top_k are checked."""

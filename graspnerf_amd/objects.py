@@ -10,41 +10,38 @@ Two things a caller must know.  Objects that stand on the table are one componen
 one component, whatever the connectivity: the labelling knows solid voxels and nothing of shapes.
 No row of planner.PRODUCTS yet: objects_of_plan runs both operators on what plan_real / plan / plan_depth return."""
 import ctypes as C
-import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from .grasp_post import DeviceOp, checked_params, picked, volume_batch
-from .hand import HAND_DEFAULTS, _GraspRows, checked_hand
+from .grasp_post import (SOLID_DEFAULTS, DeviceOp, _host, checked_params, checked_solid, labels_batch, picked, solid_fields, split_params,
+                         volume_batch)
+from .hand import HAND_DEFAULTS, _GraspRows, checked_hand, plan_rows
 
-OBJECT_DEFAULTS = dict(level=0.0, lower=None, z_min=0, connectivity=6, max_objects=1024, min_voxels=1, cleaned=False)
+OBJECT_DEFAULTS = dict(SOLID_DEFAULTS, connectivity=6, max_objects=1024, min_voxels=1, cleaned=False)
 FREE_VALUE = 1.0                                                               # the volume's upper clip: what `cleaned` holds where a component went
 OBJECT_ROW_TYPES = dict(voxels=((), torch.int32), bbox=((6,), torch.int32), sums=((3,), torch.int64))      # per statistics row: shape, dtype
 GRASP_OBJECT_ROW_TYPES = dict(object=((), torch.int32), votes=((), torch.int32), distinct=((), torch.int32), inside=((), torch.int32))
 GRASP_OBJECT_ROWS = tuple(GRASP_OBJECT_ROW_TYPES)
-PLAN_VOXEL_SIZE = 0.3 / 40                                                     # planner.REAL_VOXEL_SIZE (grasp_utils.py:146)
+# planner.REAL_VOXEL_SIZE (grasp_utils.py:146), a second literal: planner imports planner_session, whose product table is to import
+# this module for the objects' rows (DESIGN.md 4.7), so importing planner here would close a cycle
+PLAN_VOXEL_SIZE = 0.3 / 40
 
 
 def checked_objects(level=0.0, lower=None, z_min=0, connectivity=6, max_objects=1024, min_voxels=1, cleaned=False):
     """The labelling's parameters, checked before anything touches the device (the library refuses the same; z_min <= R is the
     library's, which knows R)."""
-    if not math.isfinite(level):
-        raise ValueError(f'objects level must be finite, got {level!r}')
-    if lower is not None and math.isnan(lower):
-        raise ValueError(f'objects lower must be None (no lower bound) or a number, got {lower!r}')
-    for k, v, least in (('z_min', z_min, 0), ('max_objects', max_objects, 1)):
-        if isinstance(v, bool) or int(v) != v or v < least:
-            raise ValueError(f'objects {k} must be an integer >= {least}, got {v!r}')
+    solid = checked_solid('objects', level, lower, z_min)
+    if isinstance(max_objects, bool) or int(max_objects) != max_objects or max_objects < 1:
+        raise ValueError(f'objects max_objects must be an integer >= 1, got {max_objects!r}')
     if isinstance(min_voxels, bool) or int(min_voxels) != min_voxels:
         raise ValueError(f'objects min_voxels must be an integer, got {min_voxels!r}')
     if connectivity not in (6, 18, 26) or isinstance(connectivity, bool):
         raise ValueError(f'objects connectivity must be 6, 18 or 26, got {connectivity!r}')
     if not isinstance(cleaned, bool):
         raise ValueError(f'objects cleaned must be True or False, got {cleaned!r}')
-    return dict(level=float(level), lower=None if lower is None else float(lower), z_min=int(z_min), connectivity=int(connectivity),
-                max_objects=int(max_objects), min_voxels=int(min_voxels), cleaned=cleaned)
+    return dict(solid, connectivity=int(connectivity), max_objects=int(max_objects), min_voxels=int(min_voxels), cleaned=cleaned)
 
 
 def object_params(objects, **more):
@@ -78,8 +75,7 @@ class VolumeObjects(DeviceOp):
         d = self.device
         q = checked_objects(level, lower, z_min, connectivity, max_objects, min_voxels, cleaned)
         vol, B, R = volume_batch(vol, d)
-        if q['z_min'] > R:
-            raise ValueError(f'objects z_min must be in 0..R = {R}, got {z_min!r}')
+        solid = solid_fields('objects', q, R, z_min)
         M = q['max_objects']
         out = self._out.get((B, R, M))
         if out is None:
@@ -87,8 +83,7 @@ class VolumeObjects(DeviceOp):
                                           **{k: torch.zeros(B, M, *tail, dtype=dtype, device=d) for k, (tail, dtype) in OBJECT_ROW_TYPES.items()}}
         if q['cleaned'] and 'cleaned' not in out:
             out['cleaned'] = torch.zeros(B, R, R, R, dtype=torch.float32, device=d)
-        p = _lib.GnrObjectsParams(level=q['level'], lower=-math.inf if q['lower'] is None else q['lower'], z_min=q['z_min'],
-                                  connectivity=q['connectivity'], max_objects=M, min_voxels=q['min_voxels'], free_value=FREE_VALUE)
+        p = _lib.GnrObjectsParams(**solid, connectivity=q['connectivity'], max_objects=M, min_voxels=q['min_voxels'], free_value=FREE_VALUE)
         ws, ws_bytes = self._workspace(self.L.gnr_volume_objects_workspace_bytes(B, R))
         rc = self.L.gnr_volume_objects_fwd(C.byref(p), vol.data_ptr(), B, R, out['labels'].data_ptr(), out['count'].data_ptr(),
                                            out['voxels'].data_ptr(), out['bbox'].data_ptr(), out['sums'].data_ptr(),
@@ -97,15 +92,6 @@ class VolumeObjects(DeviceOp):
         res = {k: v for k, v in out.items() if k != 'cleaned' or q['cleaned']}
         res.update(status=self._ws[:4].view(torch.int32), max_objects=M, min_voxels=q['min_voxels'])
         return res
-
-
-def labels_batch(labels, device):
-    """labels [B,R,R,R] (or one [R,R,R]) -> (contiguous int32 device tensor, B, R): VolumeObjects' `labels`."""
-    labels = torch.as_tensor(labels, dtype=torch.int32, device=device).contiguous()
-    R = labels.shape[-1]
-    if labels.dim() < 3 or tuple(labels.shape[-3:]) != (R, R, R) or labels.numel() % R ** 3:
-        raise ValueError(f'labels must be [B,R,R,R], got {tuple(labels.shape)}')
-    return labels, labels.numel() // R ** 3, R
 
 
 class GraspObjects(_GraspRows):
@@ -186,28 +172,19 @@ def objects_of_plan(tsdf_vol, grasps, *, voxel_size=PLAN_VOXEL_SIZE, origin=(0.0
     origin: the metres of voxel (0,0,0)'s value in the frame the caller wants the centres in (the grasps' own: 0).
     -> (objects, columns): objects_from_rows' dict with `labels` [R,R,R] int32 (and `cleaned` [R,R,R] float32 when asked for), and
     grasp_objects_from_rows' columns, in the order of the grasps."""
-    both = {**OBJECT_DEFAULTS, **HAND_DEFAULTS}
-    unknown = sorted(set(params) - set(both))
-    if unknown:
-        raise TypeError(f'unknown objects parameters {unknown}; it takes {sorted(both)}')
-    q = object_params(picked({**both, **params}, OBJECT_DEFAULTS))
-    hand = picked({**both, **params}, HAND_DEFAULTS)
+    params = split_params('objects', params, OBJECT_DEFAULTS, HAND_DEFAULTS)
+    q = object_params(picked(params, OBJECT_DEFAULTS))
+    hand = picked(params, HAND_DEFAULTS)
     checked_hand(**hand)
-    index, quat, width = np.asarray(grasps['index']), np.asarray(grasps['quat']), np.asarray(grasps['width'])
-    n = len(index)
     d = torch.device(device)
     vol, B, R = volume_batch(tsdf_vol, d)
     if B != 1:
         raise ValueError(f'objects_of_plan takes the volume of one scene, got {B}')
     res = VolumeObjects(d)(vol, **q)
-    rows = max(n, 1)                                                           # (the library takes no empty buffer: one row that the count leaves out)
-    pos, qt, wd = np.zeros((1, rows, 3), np.float64), np.zeros((1, rows, 4), np.float32), np.zeros((1, rows), np.float32)
-    pos[0, :n], qt[0, :n], wd[0, :n] = index.reshape(n, 3), quat.reshape(n, 4), (width.reshape(n) / np.float32(voxel_size)).astype(np.float32)
-    count = torch.tensor([n], dtype=torch.int32, device=d)
+    pos, qt, wd, count, n = plan_rows(grasps, voxel_size, d)
     gres = GraspObjects(d)(res['labels'], pos, qt, wd, count, scale=float(voxel_size), **hand)
-    host = lambda r: {k: v.cpu().numpy() for k, v in r.items()}
-    objects = objects_from_rows(host(objects_rows(res, 0, int(res['count'][0].item()))), float(voxel_size), origin, q['min_voxels'])
+    objects = objects_from_rows(_host(objects_rows(res, 0, int(res['count'][0].item()))), float(voxel_size), origin, q['min_voxels'])
     objects['labels'] = res['labels'][0].cpu().numpy()
     if q['cleaned']:
         objects['cleaned'] = res['cleaned'][0].cpu().numpy()
-    return objects, grasp_objects_from_rows(host(grasp_objects_rows(gres, 0, n)))
+    return objects, grasp_objects_from_rows(_host(grasp_objects_rows(gres, 0, n)))

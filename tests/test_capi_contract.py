@@ -299,6 +299,263 @@ def test_the_error_text_belongs_to_the_calling_thread():
                     'gnr_ingest_u8: row_pitch < src_w * channels': {(ARG,) + (b'gnr_ingest_u8: row_pitch < src_w * channels',) * 3}}
 
 
+# ---- the operator entry points: every refusal with its code, its exact text and its place in the order of the checks -------------
+class Op(Entry):
+    """An Entry whose parameter struct `p` is written as a dict of fields, so that the faults of two rows merge field by field."""
+
+    def __init__(self, name, struct=None, fields=None, **defaults):
+        super().__init__(name, **defaults)
+        self.struct, self.fields = struct, fields or {}
+
+    def __call__(self, **kw):
+        if self.struct is not None and kw.get('p', {}) is not None:
+            kw = dict(kw, p=self.struct(**{**self.fields, **kw.get('p', {})}))
+        return super().__call__(**kw)
+
+
+def _merged(first, then):
+    """The overrides of two rows in one call, or None when both set the same argument (or the same field of `p`)."""
+    pa, pb = first.get('p', {}), then.get('p', {})
+    if (set(first) & set(then)) - {'p'} or pa is None or pb is None or set(pa) & set(pb):
+        return None
+    out = {**then, **first}
+    if 'p' in out:
+        out['p'] = {**pb, **pa}
+    return out
+
+
+NAN, INF = float('nan'), float('inf')
+HAND = dict(height=0.004, finger_width=0.004, tail_length=0.04, depth=0.05, opening=-1.0, spacing=0.5, approach=0.05, scale=0.0075)
+HUGE = 1 << 40                                       # planes / bytes no launch takes
+
+
+def _hand_rows(t):
+    """The refusals gnr_hand.hip's three entry points share, in their order."""
+    return [(ARG, t + 'null pointer', dict(pos=None)), (ARG, t + 'null pointer', dict(p=None)),
+            (SHAPE, t + 'B must be in 1..65535', dict(B=0)), (SHAPE, t + 'B must be in 1..65535', dict(B=65536)),
+            (SHAPE, t + 'R must be in 2..256', dict(R=1)), (SHAPE, t + 'R must be in 2..256', dict(R=257)),
+            (SHAPE, t + 'max_n must be >= 1', dict(max_n=0)), (ARG, t + 'count_stride must be >= 1', dict(count_stride=0)),
+            (ARG, t + 'top_k must be >= 0 (0: every row)', dict(top_k=-1)),
+            (ARG, t + 'height, finger_width, tail_length, depth, spacing and scale must be finite and > 0', dict(p=dict(depth=0.0))),
+            (ARG, t + 'height, finger_width, tail_length, depth, spacing and scale must be finite and > 0', dict(p=dict(scale=INF))),
+            (ARG, t + 'approach must be finite and >= 0', dict(p=dict(approach=-1.0))),
+            (ARG, t + "opening must be finite (negative: each grasp's own width)", dict(p=dict(opening=NAN)))]
+
+
+def _operator_refusals():
+    """[(Op, [(status, text, overrides)])]: per entry point of the operator files its refusals IN THE ORDER OF ITS CHECKS, as the library
+    built from the commit before they went through gnr::Refuse, the shared limits and gnr::Carve reports them."""
+    L = _lib.lib()
+    out = []
+
+    mesh = Op('gnr_surface_mesh_fwd', _lib.GnrMeshParams, dict(iso=0.0, scale=1.0), vol=P, grad=None, B=1, R=8, p={}, count=P, vertices=P,
+              faces=P, gradient=None, max_v=8, max_f=8, ws=P, ws_bytes=BIG, stream=None)
+    t = mesh.name + ': '
+    out.append((mesh, [
+        (ARG, t + 'null pointer', dict(vol=None)), (ARG, t + 'null pointer', dict(p=None)),
+        (ARG, t + 'grad and gradient must be both given or both NULL', dict(grad=P)),
+        (SHAPE, t + 'B must be in 1..65535', dict(B=0)), (SHAPE, t + 'B must be in 1..65535', dict(B=65536)),
+        (SHAPE, t + 'R must be in 2..256', dict(R=1)), (SHAPE, t + 'R must be in 2..256', dict(R=257)),
+        (SHAPE, t + 'max_v must be >= 1', dict(max_v=0)), (SHAPE, t + 'max_f must be >= 1', dict(max_f=0)),
+        (ARG, t + 'iso, scale and origin must be finite', dict(p=dict(iso=NAN))),
+        (ARG, t + 'iso, scale and origin must be finite', dict(p=dict(origin=(0.0, INF, 0.0)))),
+        (WORKSPACE, t + 'workspace smaller than gnr_surface_mesh_workspace_bytes(B, R)', dict(ws_bytes=L.gnr_surface_mesh_workspace_bytes(1, 8) - 1))]))
+
+    ray = Op('gnr_volume_raycast_fwd', _lib.GnrRaycastParams, dict(B=1, V=1, h=8, w=8, R=8, bisections=4, iso=0.0, scale=1.0, step=0.5, near_s=0.0,
+                                                                  far_s=4.0), p={}, vol=P, grad=None, poses=P, Ks=P, depth=P, gradient=None, stream=None)
+    t = ray.name + ': '
+    out.append((ray, [
+        (ARG, t + 'null pointer', dict(depth=None)), (ARG, t + 'null pointer', dict(p=None)),
+        (ARG, t + 'grad and gradient must be both given or both NULL', dict(gradient=P)),
+        (SHAPE, t + 'B must be in 1..65535', dict(p=dict(B=65536))), (SHAPE, t + 'V must be >= 1', dict(p=dict(V=0))),
+        (SHAPE, t + 'h and w must be >= 1', dict(p=dict(h=0))), (SHAPE, t + 'R must be in 2..256', dict(p=dict(R=1))),
+        (SHAPE, t + 'R must be in 2..256', dict(p=dict(R=257))), (ARG, t + 'bisections must be in 0..32', dict(p=dict(bisections=33))),
+        (ARG, t + 'scale and step must be finite and > 0', dict(p=dict(scale=0.0))),
+        (ARG, t + 'iso and origin must be finite', dict(p=dict(iso=INF))),
+        (ARG, t + 'near_s must be >= 0 and far_s > near_s', dict(p=dict(far_s=0.0))),
+        (ARG, t + 'step too small, a ray would take more than GNR_RAYCAST_MAX_SAMPLES (65536) samples', dict(p=dict(step=1e-6))),
+        (SHAPE, t + 'h and w must give at most 2^28 tiles of 8 x 8 pixels', dict(p=dict(w=200000, h=200000)))]))
+
+    reset = Op('gnr_tsdf_reset', B=1, R=8, tsdf=P, weight=P, stream=None)
+    grid = Op('gnr_tsdf_grid', B=1, R=8, tsdf=P, weight=P, mode=0, out=P, stream=None)
+    for op, last in ((reset, []), (grid, [(ARG, 'gnr_tsdf_grid: mode must be GNR_TSDF_GRID or GNR_TSDF_SDF_LABEL', dict(mode=2))])):
+        t = op.name + ': '
+        out.append((op, [(ARG, t + 'null pointer', dict(weight=None)), (SHAPE, t + 'B must be in 1..65535', dict(B=0)),
+                         (SHAPE, t + 'B must be in 1..65535', dict(B=65536)), (SHAPE, t + 'R must be in 2..256', dict(R=1)),
+                         (SHAPE, t + 'R must be in 2..256', dict(R=257))] + last))
+    fuse = Op('gnr_tsdf_integrate', _lib.GnrTsdfParams, dict(B=1, V=1, h=8, w=8, R=8, depth_dtype=0, voxel_size=0.01, sdf_trunc=0.04, depth_scale=1.0,
+                                                            depth_trunc=2.0), p={}, depth=P, poses=P, Ks=P, origin=P, tsdf=P, weight=P, stream=None)
+    t = fuse.name + ': '
+    out.append((fuse, [
+        (ARG, t + 'null pointer', dict(origin=None)), (ARG, t + 'null pointer', dict(p=None)),
+        (SHAPE, t + 'B must be in 1..65535', dict(p=dict(B=0))), (SHAPE, t + 'R must be in 2..256', dict(p=dict(R=257))),
+        (SHAPE, t + 'V must be >= 1', dict(p=dict(V=0))), (SHAPE, t + 'h and w must be >= 1', dict(p=dict(w=0))),
+        (ARG, t + 'depth_dtype must be GNR_DEPTH_F32 or GNR_DEPTH_U16', dict(p=dict(depth_dtype=2))),
+        (ARG, t + 'voxel_size, sdf_trunc, depth_scale and depth_trunc must be > 0', dict(p=dict(sdf_trunc=NAN)))]))
+
+    sel_fields = dict(gauss_radius=4, dilate_iterations=2, max_filter_size=4)
+    sel_args = dict(tsdf=P, qual=P, rot=P, width=P, B=1, R=8, p={}, qual_out=P, count=P, index=P, score=P, quat=P, width_out=P, max_n=8, ws=P, ws_bytes=BIG,
+                    stream=None)
+    sel = Op('gnr_grasp_select_fwd', _lib.GnrSelectParams, sel_fields, **sel_args)
+    sel2 = Op('gnr_grasp_select_v2_fwd', lambda order=0, top_k=0, **kw: _lib.GnrSelectParamsV2(select=_lib.GnrSelectParams(**kw), order=order, top_k=top_k),
+              sel_fields, **sel_args)
+    for op in (sel, sel2):
+        t = op.name + ': '
+        out.append((op, [
+            (ARG, t + 'null pointer', dict(width_out=None)), (ARG, t + 'null pointer', dict(p=None)),
+            (SHAPE, t + 'bad B / R / max_n', dict(B=0)), (SHAPE, t + 'bad B / R / max_n', dict(R=1)), (SHAPE, t + 'bad B / R / max_n', dict(R=257)),
+            (SHAPE, t + 'bad B / R / max_n', dict(max_n=0)), (ARG, t + 'bad filter parameters', dict(p=dict(gauss_radius=17))),
+            (ARG, t + 'bad filter parameters', dict(p=dict(max_filter_size=17)))] + ([] if op is sel else [
+                (ARG, t + 'order must be GNR_SELECT_ORDER_INDEX or GNR_SELECT_ORDER_SCORE', dict(p=dict(order=2))),
+                (ARG, t + 'top_k must be >= 0 (0: as many as max_n)', dict(p=dict(top_k=-1))),
+                (SHAPE, t + 'GNR_SELECT_ORDER_SCORE takes R <= 64 (2^18 voxels per scene to rank)', dict(p=dict(order=1), R=65)),
+                (WORKSPACE, 'workspace too small', dict(p=dict(order=1), ws_bytes=L.gnr_grasp_select_v2_workspace_bytes(1, 8, 1) - 1))]) + [
+            (WORKSPACE, 'workspace too small', dict(ws_bytes=L.gnr_grasp_select_workspace_bytes(1, 8) - 1))]))
+
+    cloud = Op('gnr_surface_points_fwd', _lib.GnrSurfaceParams, dict(lo=-0.1, hi=0.1, color_mode=0, scale=1.0), vol=P, B=1, R=8, p={}, count=P, index=P,
+               points=P, colors=P, max_n=8, ws=P, ws_bytes=BIG, stream=None)
+    t = cloud.name + ': '
+    out.append((cloud, [
+        (ARG, t + 'null pointer', dict(colors=None)), (ARG, t + 'null pointer', dict(p=None)),
+        (SHAPE, t + 'bad B / R / max_n (R <= 256)', dict(B=0)), (SHAPE, t + 'bad B / R / max_n (R <= 256)', dict(B=65536)),
+        (SHAPE, t + 'bad B / R / max_n (R <= 256)', dict(R=0)), (SHAPE, t + 'bad B / R / max_n (R <= 256)', dict(R=257)),
+        (SHAPE, t + 'bad B / R / max_n (R <= 256)', dict(max_n=0)),
+        (ARG, t + 'color_mode must be GNR_SURFACE_COLOR_FIXED or GNR_SURFACE_COLOR_VALUE', dict(p=dict(color_mode=2))),
+        (WORKSPACE, 'workspace too small', dict(ws_bytes=L.gnr_surface_points_workspace_bytes(1, 8) - 1))]))
+    normals = Op('gnr_surface_gradient_fwd', grad=P, index=P, count=P, B=1, R=8, max_points=8, out=P, stream=None)
+    t = normals.name + ': bad B / R / max_points (1 <= R <= 256, max_points >= 0)'
+    out.append((normals, [(ARG, normals.name + ': null pointer', dict(count=None))] +
+                [(SHAPE, t, kw) for kw in (dict(B=0), dict(B=65536), dict(R=0), dict(R=257), dict(max_points=-1))]))
+
+    t = 'gnr_ingest_u8: '
+    out.append((Op('gnr_ingest_u8', frames=P, n=1, sh=4, sw=5, ch=3, rp=15, fp=60, tab=P, out=P, dh=3, dw=4, stream=None), [
+        (ARG, t + 'null pointer', dict(tab=None)), (ARG, t + 'channels must be 3 or 4', dict(ch=2)),
+        (SHAPE, t + 'n >= 1 and every dimension in 1..16384', dict(n=0)), (SHAPE, t + 'n >= 1 and every dimension in 1..16384', dict(dw=16385)),
+        (ARG, t + 'row_pitch < src_w * channels', dict(rp=14)), (ARG, t + 'frame_pitch shorter than one frame', dict(n=2, fp=59)),
+        (SHAPE, t + 'too many output pixels for one launch', dict(n=64, fp=60, dh=16384, dw=16384))]))
+    t = 'gnr_ingest_tables_host: '
+    out.append((Op('gnr_ingest_tables_host', sh=4, sw=5, dh=3, dw=4, tables=P), [
+        (ARG, t + 'null pointer', dict(tables=None)), (SHAPE, t + 'every dimension must be in 1..16384', dict(sw=0)),
+        (SHAPE, t + 'every dimension must be in 1..16384', dict(dh=16385))]))
+
+    t = 'gnr_instnorm_act_bwd: '
+    out.append((Op('gnr_instnorm_act_bwd', dy=P, out=None, x=P, mean=P, rstd=P, weight=P, dx=P, dres=None, s1=P, s2=P, dweight=P, dbias=P, planes=4, C=2,
+                   HW=16, act=0, stream=None), [
+        (ARG, t + 'null pointer', dict(s2=None)), (ARG, t + 'null pointer', dict(act=1)),                   # (an activation needs `out`)
+        (SHAPE, t + 'planes must be a multiple of C > 0, HW > 0, act in {0,1,2}', dict(planes=5)),
+        (SHAPE, t + 'planes must be a multiple of C > 0, HW > 0, act in {0,1,2}', dict(HW=0)),
+        (SHAPE, t + 'planes must be a multiple of C > 0, HW > 0, act in {0,1,2}', dict(planes=HUGE))]))
+    for name in ('gnr_reflect_pad2d', 'gnr_reflect_pad2d_bwd'):
+        t = name + ': null pointer or pad outside [0, min(H, W))'
+        out.append((Op(name, a=P, b=P, planes=2, H=4, W=4, pad=1, stream=None), [
+            (ARG, t, dict(b=None)), (SHAPE, t, dict(planes=-1)), (SHAPE, t, dict(pad=4)), (SHAPE, name + ': too many pixels for one launch', dict(planes=HUGE))]))
+    t = 'gnr_upsample2x_bilinear: '
+    out.append((Op('gnr_upsample2x_bilinear', x=P, y=P, planes=2, H=4, W=4, stream=None), [
+        (ARG, t + 'null pointer', dict(y=None)), (SHAPE, t + 'H, W > 0', dict(H=0)), (SHAPE, t + 'H, W > 0', dict(planes=-1)),
+        (SHAPE, t + 'too large for one launch', dict(planes=HUGE)), (SHAPE, t + 'too large for one launch', dict(planes=HUGE, W=5))]))
+
+    out.append((Op('gnr_pack_grasp_head', c=None, p=None), [(ARG, 'gnr_pack_grasp_head: null pointer', {})]))
+    out.append((Op('gnr_conv3d_bwd_weight', x=P, dy=P, dw=P, B=1, Cin=16, Cout=16, D=4, H=4, W=4, K=3, stream=None),
+                [(ARG, 'gnr_conv3d_bwd_weight: null pointer, a size below 1 or an even K', kw) for kw in (dict(dw=None), dict(Cin=0), dict(K=4), dict(K=0))]))
+    out.append((Op('gnr_conv3d_tap_mask', pattern=P, mask=P, Cin=16, Cout=16, K=3, stream=None),
+                [(ARG, 'gnr_conv3d_tap_mask: null pointer, a size below 1 or K not 3 or 5', kw) for kw in (dict(mask=None), dict(Cout=0), dict(K=7))]))
+    for name in ('gnr_pack_weights_device', 'gnr_pack_weights_bwd_device', 'gnr_pack_vis_decoder_device', 'gnr_pack_vis_decoder_bwd_device'):
+        out.append((Op(name, src=P, dst=P, stream=None), [(ARG, name + ': null pointer', dict(src=None)), (ARG, name + ': null pointer', dict(dst=None))]))
+
+    color_fields = dict(B=1, V=2, H=8, W=8, R=8, iso=0.0, scale=1.0, step=0.5, bias=0.0, cos_min=0.0)
+    points = Op('gnr_surface_color_points_fwd', _lib.GnrSurfaceColorParams, color_fields, p={}, vol=P, points=P, count=P, count_stride=1, max_n=8,
+                images=P, poses=P, Ks=P, colors=P, weight=P, views=P, stream=None)
+    pixels = Op('gnr_surface_color_pixels_fwd', _lib.GnrSurfaceColorParams, color_fields, p={}, vol=P, depth=P, cam_poses=P, cam_Ks=P, Vc=1, hc=8, wc=8,
+                images=P, poses=P, Ks=P, colors=P, weight=P, views=P, stream=None)
+    for op in (points, pixels):
+        t = op.name + ': '
+        out.append((op, [
+            (ARG, t + 'null pointer', dict(views=None)), (ARG, t + 'null pointer', dict(p=None)),
+            (SHAPE, t + 'B must be in 1..65535', dict(p=dict(B=0))), (SHAPE, t + 'B must be in 1..65535', dict(p=dict(B=65536))),
+            (SHAPE, t + 'V must be in 1..32 (one bit of the view mask each)', dict(p=dict(V=33))), (SHAPE, t + 'H and W must be >= 2', dict(p=dict(W=1))),
+            (SHAPE, t + 'R must be in 2..256', dict(p=dict(R=1))), (SHAPE, t + 'R must be in 2..256', dict(p=dict(R=257))),
+            (ARG, t + 'scale and step must be finite and > 0', dict(p=dict(step=-1.0))), (ARG, t + 'bias must be finite and >= 0', dict(p=dict(bias=-1.0))),
+            (ARG, t + 'iso, origin, point_offset, cos_min and fill must be finite', dict(p=dict(fill=(0.0, NAN, 0.0)))),
+            (ARG, t + 'step too small, a march would take more than GNR_RAYCAST_MAX_SAMPLES (65536) samples', dict(p=dict(step=1e-6)))] + (
+                [(SHAPE, t + 'max_n must be >= 1', dict(max_n=0)), (ARG, t + 'count_stride must be >= 1', dict(count_stride=0))] if op is points else
+                [(SHAPE, t + 'Vc must be >= 1', dict(Vc=0)), (SHAPE, t + 'hc and wc must be >= 1', dict(hc=0)),
+                 (SHAPE, t + 'hc and wc must give at most 2^28 tiles of 8 x 8 pixels', dict(hc=200000, wc=200000))])))
+
+    ptrs = (C.c_void_p * 2)(P, P)
+    need = L.gnr_frame_metrics_workspace_bytes(2, 33, 64, 2, 0, 0, 1)
+    t = 'gnr_frame_metrics: '
+    out.append((Op('gnr_frame_metrics', gt=P, preds=ptrs, n_pred=2, depth_pr=P, depth_gt=P, B=2, h=33, w=64, hm=0, wm=0, ssim=1, out=P, ws=P, ws_bytes=need,
+                   stream=None), [
+        (ARG, t + 'null pointer', dict(depth_gt=None)), (ARG, t + 'n_pred must be in 1..4', dict(n_pred=0)),
+        (SHAPE, t + 'B in 1..65535, h, w >= 1, h * w below 2^31', dict(B=0)), (SHAPE, t + 'B in 1..65535, h, w >= 1, h * w below 2^31', dict(B=65536)),
+        (SHAPE, t + 'B in 1..65535, h, w >= 1, h * w below 2^31', dict(h=1 << 16, w=1 << 15)),
+        (SHAPE, t + 'the crop margins leave no pixel', dict(wm=32)),
+        (SHAPE, t + 'SSIM needs a cropped frame of at least 11 x 11 pixels (the 11 x 11 window)', dict(hm=12)),
+        (ARG, t + 'null prediction pointer', dict(preds=(C.c_void_p * 2)(P, None))),
+        (WORKSPACE, t + 'workspace smaller than gnr_frame_metrics_workspace_bytes()', dict(ws_bytes=need - 1))]))
+
+    rows = dict(vol=P, pos=P, quat=P, width=P, count=P, count_stride=1, B=1, R=8, max_n=4, top_k=0)
+    small = dict(p=dict(spacing=1e-6))
+    clear = Op('gnr_hand_clearance_fwd', _lib.GnrHandParams, HAND, p={}, **rows, clearance=P, worst=P, inside=P, stream=None)
+    close = Op('gnr_finger_closure_fwd', _lib.GnrHandParams, HAND, p={}, level=0.0, bisections=4, **rows, travel=P, cosine=P, contact=P, closed=P, stream=None)
+    which = Op('gnr_grasp_objects_fwd', _lib.GnrHandParams, HAND, p={}, **rows, object=P, votes=P, distinct=P, inside=P, stream=None)
+    t = clear.name + ': '
+    out.append((clear, _hand_rows(t) + [
+        (ARG, t + 'spacing too small or approach too long, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) samples', small)]))
+    t = close.name + ': '
+    out.append((close, _hand_rows(t) + [
+        (ARG, t + 'level must be finite', dict(level=NAN)), (ARG, t + 'bisections must be in 0..16', dict(bisections=17)),
+        (ARG, t + 'spacing too small, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) volume reads', small)]))
+    t = which.name + ': '
+    out.append((which, _hand_rows(t) + [
+        (ARG, t + 'spacing too small, a grasp would take more than GNR_HAND_MAX_SAMPLES (4194304) samples', small)]))
+
+    solid = lambda t: [(ARG, t + 'z_min must be in 0..R', dict(p=dict(z_min=-1))), (ARG, t + 'z_min must be in 0..R', dict(p=dict(z_min=9))),
+                       (ARG, t + 'level must be finite', dict(p=dict(level=INF))), (ARG, t + 'lower must not be a NaN (-inf: none)', dict(p=dict(lower=NAN)))]
+    objects = Op('gnr_volume_objects_fwd', _lib.GnrObjectsParams, dict(level=0.0, lower=-INF, z_min=0, connectivity=6, max_objects=8, min_voxels=1,
+                                                                      free_value=1.0), p={}, vol=P, B=1, R=8, labels=P, count=P, voxels=P, bbox=P,
+                 sums=P, cleaned=None, ws=P, ws_bytes=BIG, stream=None)
+    t = objects.name + ': '
+    out.append((objects, [
+        (ARG, t + 'null pointer', dict(sums=None)), (ARG, t + 'null pointer', dict(p=None)),
+        (SHAPE, t + 'B must be in 1..65535', dict(B=0)), (SHAPE, t + 'B must be in 1..65535', dict(B=65536)),
+        (SHAPE, t + 'R must be in 2..256', dict(R=1)), (SHAPE, t + 'R must be in 2..256', dict(R=257)),
+        (ARG, t + 'connectivity must be 6, 18 or 26', dict(p=dict(connectivity=8))), (SHAPE, t + 'max_objects must be >= 1', dict(p=dict(max_objects=0)))] +
+        solid(t) + [(ARG, t + 'free_value must be finite', dict(p=dict(free_value=NAN))),
+                    (WORKSPACE, t + 'workspace too small', dict(ws_bytes=L.gnr_volume_objects_workspace_bytes(1, 8) - 1))]))
+    distance = Op('gnr_volume_distance_fwd', _lib.GnrDistanceParams, dict(level=0.0, lower=-INF, scale=0.0075, surface_offset=0.5, z_min=0), p={}, vol=P,
+                  labels=None, B=1, R=8, d2_solid=P, nearest_solid=P, d2_free=None, nearest_free=None, esdf=None, nearest_label=None, ws=P, ws_bytes=BIG,
+                  stream=None)
+    t = distance.name + ': '
+    out.append((distance, [
+        (ARG, t + 'null pointer', dict(nearest_solid=None)), (ARG, t + 'null pointer', dict(p=None)),
+        (ARG, t + 'B must be in 1..65535', dict(B=0)), (ARG, t + 'B must be in 1..65535', dict(B=65536)),       # GNR_ERR_ARG, not the siblings' GNR_ERR_SHAPE
+        (ARG, t + 'R must be in 2..256', dict(R=1)), (ARG, t + 'R must be in 2..256', dict(R=257))] + solid(t) + [
+        (ARG, t + 'scale must be finite and > 0', dict(p=dict(scale=0.0))), (ARG, t + 'surface_offset must be finite and >= 0', dict(p=dict(surface_offset=-0.5))),
+        (ARG, t + 'nearest_label needs labels', dict(nearest_label=P)), (ARG, t + 'd2_free and nearest_free go together', dict(d2_free=P)),
+        (WORKSPACE, t + 'workspace too small', dict(ws_bytes=L.gnr_volume_distance_workspace_bytes(1, 8) - 1))]))
+    return out
+
+
+def test_operator_entry_points_refuse_in_order():
+    """Mesh, ray cast, TSDF, select, surface cloud and normals, ingest, img, the head's small entry points, pack_dev, surface colours,
+    frame metrics, the hand's three, objects and distance: every refusal alone gives its status and its exact text, and together with
+    the fault of the row behind it (where the two do not set the same argument) it still gives its own -- the order of the checks.
+    Every call is one that validation refuses (fake pointers); runs without a GPU."""
+    L = _lib.lib()
+    singles = pairs = 0
+    for op, rows in _operator_refusals():
+        for i, (code, text, kw) in enumerate(rows):
+            assert (op(**kw), L.gnr_last_error().decode()) == (code, text), (op.name, kw)
+            singles += 1
+            for _, _, later in rows[i + 1:]:
+                both = _merged(kw, later)
+                if both is not None:
+                    assert (op(**both), L.gnr_last_error().decode()) == (code, text), (op.name, both)
+                    pairs += 1
+    assert (singles, pairs) == (237, 969)                     # (no row and no pair dropped out on the way)
+
+
 # What the library built from the commit before the host layer's launches went through one helper reports for the run below.
 LABELS = [
     'k_view_setup@gnr_prepare', 'k_repack_feats@gnr_prepare',
