@@ -4,41 +4,33 @@
 // tests/objects_reference.py's.  Everything is integer beyond the one threshold compare, so any order of execution gives the same bits.
 // Union-find in global memory over int32 parents (a voxel's index inside its own scene; -1: not solid), as six launches:
 //   k_init     parent = own index where solid, -1 elsewhere; sizes 0; the status word 0; the statistics rows to their empty values.
-//   k_union    each solid voxel unites with its solid neighbours of smaller index (3 / 9 / 13 of them).  unite() finds both roots and
-//              hooks the larger under the smaller with an atomic min; a parent is always smaller than its child, so a tree's root is
-//              its smallest index.  When the min returns something else than the root it expected, the node had a parent already (and
-//              the min may have replaced that link): it goes on uniting that former parent with the smaller root.  Each find also
-//              lowers the parent of the node it started from to the root it found (an atomic min again: a link only ever moves to a
-//              smaller member of what ends as one tree, and every link a min replaces is re-united by the thread that replaced it).
+//   k_union    each solid voxel unites with its solid neighbours of smaller index (3 / 9 / 13 of them); find() and unite() are
+//              gnr_union.h's (shared with gnr_parts.hip): the larger root hooks under the smaller with an atomic min, so a tree's root
+//              is its smallest index.
 //   k_flatten  parent = root, for every solid voxel; the sizes, added at the root voxel (one add per wavefront and root); the roots of
 //              each chunk of 1024 voxels counted (gnr_compact.h).
 //   k_scan     the chunk counts scanned per scene; their sum is the scene's count.
 //   k_rank     every root takes label 1 + its rank among the roots of its scene, and, when that is a statistics row, stores its size.
 //   k_label    labels of the other voxels (the root's), the boxes and sums (one atomic per wavefront, label and column), `cleaned`.
-// Visibility.  Inside k_union and k_flatten other workgroups -- on other XCDs, whose L2s are not coherent with this one's -- change
-// parent[] while a thread follows it.  Every access to parent[] in those two launches is therefore an agent-scope atomic (relaxed
-// loads that bypass the CU's L1, min / store at the memory side), through a global-address-space pointer, never a plain load and never
-// a const __restrict__ one (that could take the scalar path).  Stale values would even be harmless to the result -- every value a
-// parent ever held is an ancestor in the final tree -- but a plain load may be kept in a register across a loop.  A kernel boundary
-// makes the next launch's plain loads safe: k_rank and k_label read parent[], size[] and the root labels plainly.
-// No thread ever waits for another: the algorithm is lock-free, there is no spin and no flag.  Every loop carries a bound from the
-// parameters: a find follows at most R^3 links (each link goes to a smaller index), a unite retries at most R^3 times; running into
-// the bound sets GNR_OBJECTS_STATUS_BOUND in the status word (the first int of the workspace) and ends the loop.
+// Visibility (gnr_union.h states the rules).  k_union and k_flatten change parent[] while other workgroups follow it: every access to
+// parent[] in those two launches is an agent-scope relaxed atomic through a global pointer.  A kernel boundary makes the next launch's
+// plain loads safe: k_rank and k_label read parent[], size[] and the root labels plainly.
+// No thread ever waits for another.  Every loop carries a bound from the parameters: a find follows at most R^3 links, a unite retries
+// at most R^3 times; running into the bound sets GNR_OBJECTS_STATUS_BOUND in the status word (the first int of the workspace) and ends
+// the loop.
 // Everything a call reads from its workspace it has written in the same call (k_init), so a captured call replays.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include "gnr_compact.h"
 #include "gnr_host.h"
 #include "gnr_solid.h"
+#include "gnr_union.h"
 
 namespace gnr_objects {
 
 using namespace gnr;
-
-typedef __attribute__((address_space(1))) int gint;
-#define GNR_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+static_assert(UNION_STATUS_BOUND == GNR_OBJECTS_STATUS_BOUND, "find() and unite() flag the status word's bound bit");
 
 struct Shape {
     int R, n, nc;                              // n = R^3 voxels of a scene, nc chunks of 1024 of them
@@ -46,38 +38,6 @@ struct Shape {
     double level, lower;
     float free_value;
 };
-
-__device__ inline int ld(int* p) { return __hip_atomic_load((gint*)p, GNR_RLX_AGENT); }
-__device__ inline void st(int* p, int v) { __hip_atomic_store((gint*)p, v, GNR_RLX_AGENT); }
-__device__ inline int lower_to(int* p, int v) { return __hip_atomic_fetch_min((gint*)p, v, GNR_RLX_AGENT); }
-__device__ inline void flag_bound(int* status) { __hip_atomic_fetch_or((gint*)status, GNR_OBJECTS_STATUS_BOUND, GNR_RLX_AGENT); }
-
-// the root of solid voxel x: at most `lim` links, each to a smaller index (anything else -- there is nothing else -- ends the walk)
-__device__ inline int find(int* parent, int x, int lim, int* status) {
-    for (int s = 0; s <= lim; ++s) {
-        const int p = ld(parent + x);
-        if ((unsigned)p >= (unsigned)x) return x;
-        x = p;
-    }
-    flag_bound(status);
-    return x;
-}
-
-// one tree of the trees of solid voxels a and b
-__device__ inline void unite(int* parent, int a, int b, int lim, int* status) {
-    for (int s = 0; s <= lim; ++s) {
-        const int ra = find(parent, a, lim, status), rb = find(parent, b, lim, status);
-        if (ra != a) lower_to(parent + a, ra);
-        if (rb != b) lower_to(parent + b, rb);
-        if (ra == rb) return;
-        const int hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
-        const int old = lower_to(parent + hi, lo);
-        if (old == hi) return;                 // hi was a root and hangs under lo now
-        a = old;                               // hi had the parent `old` (which the min may have replaced): old and lo remain to be united
-        b = lo;
-    }
-    flag_bound(status);
-}
 
 // launch grid: (ceil(n / 256), B), 256 threads.  The rows of the statistics are spread over all threads of the grid.
 __global__ __launch_bounds__(256) void k_init(const float* __restrict__ vol, int* __restrict__ parent, int* __restrict__ size,
@@ -145,13 +105,6 @@ __global__ __launch_bounds__(1024) void k_flatten(int* parent_all, int* size_all
     if (threadIdx.x == 0) chunk[(size_t)b * sh.nc + blockIdx.x] = tot;
 }
 
-// launch grid: B, 1024 threads
-__global__ __launch_bounds__(1024) void k_scan(int* __restrict__ chunk, int nc, int* __restrict__ count) {
-    __shared__ int wave_tot[16];
-    const int total = scan_chunks(chunk + (size_t)blockIdx.x * nc, nc, wave_tot);
-    if (threadIdx.x == 0) count[blockIdx.x] = total;
-}
-
 // launch grid: (nc, B), 1024 threads
 __global__ __launch_bounds__(1024) void k_rank(const int* __restrict__ parent, const int* __restrict__ size, const int* __restrict__ chunk,
                                                int* __restrict__ labels, int* __restrict__ voxels, Shape sh) {
@@ -171,7 +124,7 @@ __global__ __launch_bounds__(1024) void k_rank(const int* __restrict__ parent, c
 __global__ __launch_bounds__(256) void k_label(const float* __restrict__ vol, const int* __restrict__ parent, const int* __restrict__ size,
                                                int* labels, int* __restrict__ bbox, unsigned long long* __restrict__ sums,
                                                float* __restrict__ cleaned, Shape sh) {
-    const int t = (int)(blockIdx.x * 256u + threadIdx.x), b = blockIdx.y, R = sh.R, lane = threadIdx.x & 63;
+    const int t = (int)(blockIdx.x * 256u + threadIdx.x), b = blockIdx.y, R = sh.R;
     int L = 0;
     if (t < sh.n) {
         const size_t base = (size_t)b * sh.n, o = base + t;
@@ -180,40 +133,7 @@ __global__ __launch_bounds__(256) void k_label(const float* __restrict__ vol, co
         if (p != t) labels[o] = L;
         if (cleaned) cleaned[o] = p >= 0 && size[base + p] < sh.min_voxels ? sh.free_value : vol[o];
     }
-    const bool has = L >= 1 && L <= sh.max_objects;
-    const int c[3] = {t / (R * R), (t / R) % R, t % R};
-    unsigned long long todo = __ballot(has);
-    for (int s = 0; s < 64 && todo; ++s) {
-        const int lead = __ffsll((long long)todo) - 1;
-        const int Ll = __shfl(L, lead);
-        const bool mine = has && L == Ll;
-        const unsigned long long m = __ballot(mine);
-        int lo[3], hi[3], sum[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { lo[a] = mine ? c[a] : INT32_MAX; hi[a] = mine ? c[a] : -1; sum[a] = mine ? c[a] : 0; }
-        if (__popcll(m) > 1) {
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    const int ol = __shfl_xor(lo[a], d), oh = __shfl_xor(hi[a], d);
-                    lo[a] = ol < lo[a] ? ol : lo[a];
-                    hi[a] = oh > hi[a] ? oh : hi[a];
-                    sum[a] += __shfl_xor(sum[a], d);
-                }
-            }
-        }
-        if (lane == lead) {
-            const size_t row = (size_t)b * sh.max_objects + (Ll - 1);
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                atomicMin(bbox + row * 6 + a, lo[a]);
-                atomicMax(bbox + row * 6 + 3 + a, hi[a]);
-                atomicAdd(sums + row * 3 + a, (unsigned long long)sum[a]);
-            }
-        }
-        todo &= ~m;
-    }
+    add_to_rows(L, L >= 1 && L <= sh.max_objects, t, R, b, sh.max_objects, bbox, sums);
 }
 
 struct Work { int *status, *parent, *size, *chunk; size_t total; };

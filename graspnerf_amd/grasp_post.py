@@ -54,6 +54,12 @@ def labels_batch(labels, device):
     return _lattice_batch(labels, device, torch.int32, 'labels')
 
 
+def height_batch(height, device):
+    """height [B,R,R,R] (or one [R,R,R]) -> (contiguous int32 device tensor, B, R): parts.VolumeParts' input, distance.VolumeDistance's
+    `d2_free`."""
+    return _lattice_batch(height, device, torch.int32, 'height')
+
+
 def gradient_batch(gradient, B, R, device):
     """The gradient volume [B,R,R,R,3] of B volumes as a contiguous float32 device tensor; None stays None."""
     if gradient is None:

@@ -7,7 +7,8 @@ GraspObjects (gnr_grasp_objects_fwd, csrc/gnr_hand.hip's third kernel) says whic
 it pinches two at once.  include/gnr.h states both; the results are the bits of tests/objects_reference.py (scipy.ndimage.label).
 Two things a caller must know.  Objects that stand on the table are one component with the table and with each other through it:
 `z_min` must cut the table slab (voxels with k < z_min are not solid) for them to separate.  And objects that touch each other are
-one component, whatever the connectivity: the labelling knows solid voxels and nothing of shapes.
+one component, whatever the connectivity: the labelling knows solid voxels and nothing of shapes (parts.VolumeParts splits such a
+component at its necks, with this module's numbering and rows).
 No row of planner.PRODUCTS yet: objects_of_plan runs both operators on what plan_real / plan / plan_depth return."""
 import ctypes as C
 

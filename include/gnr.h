@@ -984,6 +984,63 @@ int gnr_volume_distance_fwd(const GnrDistanceParams* params, const float* vol /*
                             int* nearest_free /*[B,R,R,R] or NULL*/, float* esdf /*[B,R,R,R] or NULL*/,
                             int* nearest_label /*[B,R,R,R] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* gnr_volume_parts_fwd: the parts of B integer height fields [B,R,R,R] -- their solid voxels split at the necks: a watershed by
+ * steepest ascent, neighbouring basins joined where the pass between them is no neck.  gnr_volume_objects_fwd knows solid voxels and
+ * nothing of shapes: objects that touch are one component.  With gnr_volume_distance_fwd's d2_free as the height -- per solid voxel the
+ * squared radius of the largest ball around it that stays inside the solid -- two convex things that touch are two hills joined over
+ * a low pass, and this call cuts there.  Numbering, statistics rows and calling conventions are gnr_volume_objects_fwd's, so
+ * gnr_grasp_objects_fwd takes the labels as they are.  No reference counterpart; tests/parts_reference.py is the same statement in
+ * numpy and the call produces its bits.  Nothing is floating-point beyond the one multiply and compare of the neck test.
+ *   lattice    gnr_volume_objects_fwd's: voxel (i,j,k) of scene b sits at ((b*R + i)*R + j)*R + k; an index below is that of a voxel
+ *              inside its scene, i R R + j R + k.
+ *   solid      height > 0.  d2_free is > 0 exactly at the solid voxels of its call, whose solid rule (level, lower, z_min, NaNs) is
+ *              not restated here.  Any int32 field is accepted.
+ *   neighbours gnr_volume_objects_fwd's, under connectivity 6, 18 or 26, inside the same scene: rows, planes and scenes do not wrap.
+ *   ascent     up[v] is the voxel of the largest height among the solid voxel v and its solid neighbours, of several with that
+ *              height the one of the smallest index; v takes part in both comparisons.  A voxel with up[v] == v is a summit.
+ *              Following up from any solid voxel ends at a summit (every link strictly increases (height, -index)): the voxel's
+ *              basin, whose peak is the summit's height.  basins[b] is the number of summits of scene b.
+ *   merge      for every pair of neighbouring solid voxels u, w in different basins a, b, with pass = min(height[u], height[w]):
+ *              the two basins are joined when min(peak_a, peak_b) <= min_peak, or when
+ *                  (double)pass >= (neck * neck) * (double)min(peak_a, peak_b)
+ *              -- neck * neck one double multiply, then one double multiply and one compare, the same on host and device.  The
+ *              peaks are the basins' own, never those of an already merged set, so the set of joins does not depend on any order.
+ *              The parts are the transitive closure of the joins.  neck is a ratio of radii: with heights from d2_free it compares
+ *              the half-width of the pass with the inscribed radius of the smaller hill.  neck = 0 joins every pair of adjoining
+ *              basins: the labels are then gnr_volume_objects_fwd's of the same solid voxels and connectivity.  On a plateau (all
+ *              heights equal) every summit merges for every neck <= 1, which is why neck > 1 is refused.
+ *   labels     a voxel that is not solid gets 0.  A part's label is 1 + the number of parts of its scene whose smallest index is
+ *              smaller: ndimage.label's numbering.  count[b] is the number of parts, the true number even when it exceeds max_parts;
+ *              the labels are always complete and do not depend on max_parts.
+ *   statistics gnr_volume_objects_fwd's rows and empty values, and two columns more: every call first writes rows 0 .. max_parts-1:
+ *              voxels 0, bbox (R,R,R,-1,-1,-1), sums 0, peak 0, peak_voxel -1; then, for the labels 1 .. min(count, max_parts), at
+ *              row label-1: voxels, bbox and sums of the part's voxels, peak = the largest height in the part, peak_voxel = the smallest
+ *              index in the part that has that height.  Integer atomics only: any order gives the same bits.
+ *   workspace  at least gnr_volume_parts_workspace_bytes(B, R) (0 for a B or R outside the limits).  Its first int is the status word
+ *              of the call, valid once the stream has run it: 0, or GNR_PARTS_STATUS_BOUND when a loop ran into its bound (R^3 links
+ *              of a walk or a chain, R^3 retries of a union; it never spins on) -- the results are then not to be used.  Everything a
+ *              call reads from its workspace it has written in that call; nothing is kept between calls.
+ * 1 <= B <= 65535, 2 <= R <= 256 (GNR_ERR_SHAPE); connectivity 6, 18 or 26 (GNR_ERR_ARG); max_parts >= 1 (GNR_ERR_SHAPE);
+ * min_peak >= 0; neck finite and in [0, 1] (GNR_ERR_ARG); a null pointer (GNR_ERR_ARG); a workspace too small (GNR_ERR_WORKSPACE).
+ * Asynchronous on `stream`, no allocation, no synchronisation, no float atomics (it can be captured in a graph and replayed); a
+ * refused call has launched nothing.
+ * What it cannot separate: two boxes face to face without a gap are one box to any rule that sees the solid voxels alone; a part
+ * whose own waist is narrower than `neck` times its smaller bulge is cut in two.  neck = 0.8 separates the synthetic touching shapes
+ * of tests/test_volume_parts.py; it has not been run on a network's volume.                                                       */
+#define GNR_PARTS_STATUS_BOUND 1
+typedef struct GnrPartsParams {
+    double neck;         /* in [0, 1]: a pass is a neck when its height is below neck^2 times the smaller of the two peaks; 0: none    */
+    int    connectivity; /* 6, 18 or 26: scipy's generate_binary_structure(3, 1 | 2 | 3)                                       */
+    int    max_parts;    /* rows of the statistics                                                                             */
+    int    min_peak;     /* a basin whose peak is at most this joins every basin it adjoins (ripples of a rough surface); 0: none  */
+} GnrPartsParams;
+size_t gnr_volume_parts_workspace_bytes(int B, int R);
+int gnr_volume_parts_fwd(const GnrPartsParams* params, const int* height /*[B,R,R,R]*/, int B, int R, int* labels /*[B,R,R,R]*/,
+                         int* count /*[B]*/, int* basins /*[B]*/, int* voxels /*[B,max_parts]*/,
+                         int* bbox /*[B,max_parts,6]: lo i,j,k, hi i,j,k (inclusive)*/,
+                         unsigned long long* sums /*[B,max_parts,3]: sum of i, j, k*/, int* peak /*[B,max_parts]*/,
+                         int* peak_voxel /*[B,max_parts]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
