@@ -120,6 +120,14 @@ class GnrPartsParams(C.Structure):
     _fields_ = [('neck', C.c_double), ('connectivity', C.c_int), ('max_parts', C.c_int), ('min_peak', C.c_int)]
 
 
+GNR_RETREAT_MAX_STEPS = 1024
+
+
+class GnrRetreatParams(C.Structure):
+    _fields_ = [('retreat', C.c_double), ('step', C.c_double), ('side_cos', C.c_double), ('scale', C.c_double), ('tolerance', C.c_int),
+                ('max_parts', C.c_int)]
+
+
 class GnrError(RuntimeError):
     pass
 
@@ -330,6 +338,8 @@ def lib():
     L.gnr_volume_parts_fwd.argtypes = [C.POINTER(GnrPartsParams), C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + \
                                       [C.c_void_p, C.c_size_t, C.c_void_p]
     L.gnr_volume_parts_fwd.restype = C.c_int
+    L.gnr_grasp_retreat_fwd.argtypes = [C.POINTER(GnrRetreatParams)] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 7
+    L.gnr_grasp_retreat_fwd.restype = C.c_int
     L.gnr_tsdf_reset.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gnr_tsdf_reset.restype = C.c_int
     L.gnr_tsdf_integrate.argtypes = [C.POINTER(GnrTsdfParams)] + [C.c_void_p] * 7
@@ -396,7 +406,7 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_tsdf_reset', 'gnr_tsdf_integrate', 'gnr_tsdf_grid', 'gnr_surface_mesh_workspace_bytes', 'gnr_surface_mesh_fwd',
             'gnr_volume_raycast_fwd', 'gnr_surface_color_points_fwd', 'gnr_surface_color_pixels_fwd', 'gnr_hand_clearance_fwd', 'gnr_finger_closure_fwd',
             'gnr_volume_objects_workspace_bytes', 'gnr_volume_objects_fwd', 'gnr_grasp_objects_fwd',
-            'gnr_volume_distance_workspace_bytes', 'gnr_volume_distance_fwd', 'gnr_volume_parts_workspace_bytes', 'gnr_volume_parts_fwd',
+            'gnr_volume_distance_workspace_bytes', 'gnr_volume_distance_fwd', 'gnr_volume_parts_workspace_bytes', 'gnr_volume_parts_fwd', 'gnr_grasp_retreat_fwd',
             'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 

@@ -1041,6 +1041,57 @@ int gnr_volume_parts_fwd(const GnrPartsParams* params, const int* height /*[B,R,
                          unsigned long long* sums /*[B,max_parts,3]: sum of i, j, k*/, int* peak /*[B,max_parts]*/,
                          int* peak_voxel /*[B,max_parts]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* gnr_grasp_retreat_fwd: whether the part each ranked grasp holds comes out of the pile -- the fourth step of execute_grasp
+ * (gd/simulation.py:369-422): after the fingers closed, the hand moves `retreat` metres back along its own z, or, when the approach
+ * is more than 60 degrees off straight down, lifts that far along world +z (:378-386, 406), and only then asks check_success.  The
+ * voxels of the held part (gnr_volume_parts_fwd's or gnr_volume_objects_fwd's label, gnr_grasp_objects_fwd's `object`) are moved
+ * along that line by integer offsets, and every step counts those that land inside another part.  No reference counterpart;
+ * tests/retreat_reference.py is the same statement in numpy and the call produces its bits.  quat converts to float64 before the
+ * first operation; all arithmetic is float64, single correctly rounded operations in the order written, never contracted;
+ * everything else is integers.
+ *   lattice    gnr_volume_objects_fwd's: voxel (i,j,k) of scene b sits at ((b*R + i)*R + j)*R + k; axis 2 (k) is the world's z, the
+ *              axis the solid rule's z_min cuts.
+ *   steps      T = retreat / scale (voxels);  K = (int)fmax(1, ceil(T / step));  sl = T / (double)K.  K depends on the parameters
+ *              alone and must be at most GNR_RETREAT_MAX_STEPS.
+ *   pose       M is gnr_hand_clearance_fwd's matrix of (double)quat[b,r], word for word (the division by fmax(norm, 1e-12)
+ *              included);  u_a = -M[a][2] for a = 0, 1, 2.  If any u_a is not a number the row moves nothing: every integer output
+ *              of the row is 0 and travel = (float)(T * scale).
+ *   direction  side = (-M[2][2] < side_cos) ? 1 : 0;  with side set, u = (0, 0, 1).
+ *   moving     L = held[b,r].  L < 1 or L > max_parts: no voxel moves.  Otherwise lo_a = max(bbox[b,L-1,a], 0), hi_a =
+ *              min(bbox[b,L-1,3+a], R-1), and the moving voxels are the voxels v of that box (none when some lo_a > hi_a) with
+ *              labels[b,v] == L.  moved = their number.  A box wider than the part gives the part's own result.
+ *   step k     for k = 1 .. K:  o_a = rint(u_a * ((double)k * sl)) -- to nearest, ties to even; an integer, not an int32: a
+ *              |o_a| >= R moves every voxel out --;  t = v + o.  A t with a component outside [0, R-1] has left the workspace and
+ *              hits nothing: it never wraps into a neighbouring row, plane or scene.  Otherwise v hits when labels[b,t] is
+ *              neither 0 nor L (labels are any int32).  hits_k = the number of moving voxels that hit.
+ *   result     overlap = max_k hits_k;  blocked_step = the smallest k with hits_k > tolerance, 0 when there is none;  blocker =
+ *              labels[b, v* + o] at k = blocked_step, v* the moving voxel of the smallest index i R R + j R + k that hits there, 0
+ *              when not blocked;  travel = (float)(((double)(blocked_step - 1) * sl) * scale) when blocked, else
+ *              (float)(T * scale): metres moved before the first blocked step;  side as above.
+ *   rows       gnr_hand_clearance_fwd's: r < min(count[b * count_stride], top_k > 0 ? top_k : max_n, max_n); the other rows are
+ *              left untouched.
+ * 1 <= B <= 65535, 2 <= R <= 256, max_n >= 1 (GNR_ERR_SHAPE); count_stride >= 1, top_k >= 0; retreat, step and scale finite and
+ * > 0; side_cos finite; tolerance >= 0 (GNR_ERR_ARG); max_parts >= 1 (GNR_ERR_SHAPE); K within the cap, a null pointer
+ * (GNR_ERR_ARG).  Every loop is bounded by the parameters and R: no content of bbox, held, quat or count ends one later or moves
+ * an access out of the scene's lattice.  Asynchronous on `stream`, no global-memory atomics, no workspace, no allocation, no
+ * synchronisation (it can be captured in a graph); a refused call has launched nothing.
+ * What it does not answer: the closed hand's own sweep on the lift, any rotation of the part, parts that would be pushed aside
+ * rather than block, and what the rest of the pile does once the part is gone (remove_and_wait).                              */
+#define GNR_RETREAT_MAX_STEPS 1024
+typedef struct GnrRetreatParams {
+    double retreat;    /* metres the hand moves away: 0.1 (simulation.py:382,385)                                              */
+    double step;       /* voxels between tested positions at most: 0.5                                                         */
+    double side_cos;   /* a grasp whose approach has -a_z < side_cos lifts along world +z: 0.5 = cos(pi/3)                     */
+    double scale;      /* metres per voxel                                                                                     */
+    int    tolerance;  /* a step is blocked when MORE than this many moving voxels are inside other parts: 0                   */
+    int    max_parts;  /* rows of bbox                                                                                         */
+} GnrRetreatParams;
+int gnr_grasp_retreat_fwd(const GnrRetreatParams* params, const int* labels /*[B,R,R,R]*/, const int* bbox /*[B,max_parts,6]*/,
+                          const int* held /*[B,max_n]*/, const float* quat /*[B,max_n,4]*/, const int* count /*[B * count_stride]*/,
+                          int count_stride, int B, int R, int max_n, int top_k, int* blocked_step /*[B,max_n]*/, int* blocker /*[B,max_n]*/,
+                          int* overlap /*[B,max_n]*/, int* moved /*[B,max_n]*/, int* side /*[B,max_n]*/, float* travel /*[B,max_n]*/,
+                          void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
