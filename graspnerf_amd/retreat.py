@@ -9,8 +9,8 @@ retreat by integer offsets, at most `step` voxels between tested positions; a st
 inside another part.  include/gnr.h states the rule; the results are the bits of tests/retreat_reference.py.
 What a caller must know.  The part moves as a rigid set of voxels without rotation; a position outside the lattice is free (the
 workspace ends there); parts that would be pushed aside count as blocking; the closed hand's own sweep on a side grasp's lift is not
-tested (for a top grasp the way out is the way in, HandClearance's approach_clearance); nothing says what the rest of the pile does
-once the part is gone.  Labels of touching parts meet without a gap, and a split is never perfectly along the contact: a few voxels
+tested (for a top grasp the way out is the way in, HandClearance's approach_clearance); what rests on the held part and what loses
+its footing once it is gone is support.PartSupport's answer, how the pile then moves is nobody's.  Labels of touching parts meet without a gap, and a split is never perfectly along the contact: a few voxels
 of overlap on the first steps are the split's own noise, which is what `tolerance` is for.
 No row of planner_session.PRODUCTS yet: retreat_of_plan runs the operators on what plan_real / plan / plan_depth return."""
 import ctypes as C

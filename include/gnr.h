@@ -1076,7 +1076,8 @@ int gnr_volume_parts_fwd(const GnrPartsParams* params, const int* height /*[B,R,
  * an access out of the scene's lattice.  Asynchronous on `stream`, no global-memory atomics, no workspace, no allocation, no
  * synchronisation (it can be captured in a graph); a refused call has launched nothing.
  * What it does not answer: the closed hand's own sweep on the lift, any rotation of the part, parts that would be pushed aside
- * rather than block, and what the rest of the pile does once the part is gone (remove_and_wait).                              */
+ * rather than block.  Which parts rest on the held one, and which lose their footing once it is gone, is gnr_part_support_fwd's
+ * answer; what the pile then does -- anything that slides, tips or settles (remove_and_wait) -- is nobody's.                   */
 #define GNR_RETREAT_MAX_STEPS 1024
 typedef struct GnrRetreatParams {
     double retreat;    /* metres the hand moves away: 0.1 (simulation.py:382,385)                                              */
@@ -1091,6 +1092,70 @@ int gnr_grasp_retreat_fwd(const GnrRetreatParams* params, const int* labels /*[B
                           int count_stride, int B, int R, int max_n, int top_k, int* blocked_step /*[B,max_n]*/, int* blocker /*[B,max_n]*/,
                           int* overlap /*[B,max_n]*/, int* moved /*[B,max_n]*/, int* side /*[B,max_n]*/, float* travel /*[B,max_n]*/,
                           void* stream);
+
+/* gnr_part_contacts_fwd, gnr_part_support_fwd: the support of the parts -- where two labels of a label volume touch, which of the two
+ * lies on the other there, and the graph that follows: on whom a part rests, what it carries, which parts lose every footing when it
+ * is taken, in which order a pile comes apart without anything falling, what hangs in the air.  gnr_grasp_retreat_fwd tests one line
+ * for one part; this looks at pairs of labels.  The reference leaves the question to physics (remove_and_wait, gd/simulation.py;
+ * `while sim.num_objects > 0`, clutter_removal.py:92).  No reference counterpart; tests/support_reference.py is the same statement in
+ * numpy and the calls produce its bits.  Integers throughout, but for the one double multiply and compare of the lean test.
+ *   lattice    gnr_volume_objects_fwd's: voxel (i,j,k) of scene b sits at ((b*R + i)*R + j)*R + k; axis 2 (k) is the world's z.
+ *   labels     any int32 volume (gnr_volume_parts_fwd's or gnr_volume_objects_fwd's `labels`).  A label < 1 is no part.  P =
+ *              max_parts is the number of rows of every table: part a is row a-1.
+ *   neighbours gnr_volume_objects_fwd's, under connectivity 6, 18 or 26, inside the same scene: rows, planes and scenes do not wrap.
+ * gnr_part_contacts_fwd: labels -> tables.
+ *   pairs      for every ORDERED pair of neighbouring voxels (u, w) of scene s, with a = labels[u], b = labels[w], a >= 1, b >= 1
+ *              and a != b:  if a <= P and b <= P, touch[s,a-1,b-1] += 1, and, when k_w > k_u (b's voxel is the higher one: b lies on
+ *              a there), over[s,a-1,b-1] += 1;  otherwise dropped[s] += 1.  touch is symmetric by construction.  pairs[s,a-1,b-1,0] =
+ *              touch, pairs[s,a-1,b-1,1] = over.
+ *   floor      floor[s,a-1] = the number of voxels with label a in 1..P and k == z_min: with z_min cutting the table slab these
+ *              voxels stand on the table.  z_min == R gives none.
+ *   Every element of pairs, floor and dropped is written by every call (a fill kernel, then integer atomics: any order gives the
+ *   same bits).
+ * gnr_part_support_fwd: tables -> graph.  Per scene n = min(max(count[s], 0), P); the parts are the labels 1..n.
+ *   rests      with N = touch[a,c] and D = over[a,c] - over[c,a]:  rests(c, a), "c rests on a", holds when a != c, N >= min_contact,
+ *              D > 0 and (double)D >= lean * (double)N -- one double multiply and one compare.  Antisymmetric in D: never both ways.
+ *              on_floor(a) = floor[a] >= min_floor.
+ *   below[a]   the number of c with rests(a, c): a's footings.      above[a]  the number of c with rests(c, a).
+ *   carried[a] the number of parts other than a reachable from a along "rests on a", transitively.
+ *   orphans[a] F starts as {a}; a round adds every c that is not in F, is not on_floor, has below[c] >= 1 and has all its footings in
+ *              F; rounds repeat until nothing changes (at most n do).  orphans[a] = |F| - 1: the parts that lose every footing when
+ *              a is taken.
+ *   layer[a]   0 when above[a] == 0, otherwise 1 + the largest layer of the parts resting on a, assigned only once all of those are
+ *              assigned (at most n rounds); a part still unassigned then gets -1: the relation has a cycle above it.  Any int32
+ *              label volume can make one; the parts' labels should not.  Ascending (layer, label) is an order in which nothing
+ *              taken has anything resting on it.
+ *   grounded[a]  1 when on_floor(a) or some footing of a is grounded (a fixed point, at most n rounds), otherwise 0.
+ *   rests_on   (when not NULL) rests_on[s,c-1,a-1] = rests(c, a) as 0 / 1, for c, a in 1..n; 0 elsewhere.
+ *   Rows n .. P-1 of every output are written as the empty values: the counts 0, layer -1, grounded 0.
+ * Limits, in the order they are refused (a null `params` comes first: GNR_ERR_ARG "null pointer"): 1 <= B <= 65535 and, for the
+ * contacts, 2 <= R <= 256 (GNR_ERR_SHAPE); 1 <= max_parts <= GNR_SUPPORT_MAX_PARTS (GNR_ERR_SHAPE: the table is dense, 256 rows are
+ * 512 KB per scene; a heap of more parts is not what this answers, and `dropped` says when labels went beyond the rows); connectivity
+ * 6, 18 or 26; 0 <= z_min <= R; min_contact >= 1; min_floor >= 1; lean finite and in [0, 1]; a null required pointer (GNR_ERR_ARG).
+ * The support call has no R.  Both calls: asynchronous on `stream`, no workspace, no allocation, no synchronisation, no float
+ * atomics, every loop bounded by R, P or 64 (they can be captured in a graph and replayed); a refused call has launched nothing and
+ * written nothing.
+ * What it does not answer: any dynamics -- nothing slides, tips or settles --, contact points and normals in metres, whether a
+ * part's centre of mass lies over its footings.  lean = 0.25 lies between the 0.0 of every side contact and the 0.83 .. 1.0 of every
+ * resting contact of the synthetic piles of tests/test_part_support.py; it has not been run on a network's volume.                */
+#define GNR_SUPPORT_MAX_PARTS 256
+typedef struct GnrContactsParams {
+    int connectivity;  /* 6, 18 or 26: the parts' own                                                                          */
+    int max_parts;     /* P: rows of the tables, 1 .. GNR_SUPPORT_MAX_PARTS                                                    */
+    int z_min;         /* the plane whose voxels stand on the table: the solid rule's z_min; R: none                           */
+} GnrContactsParams;
+int gnr_part_contacts_fwd(const GnrContactsParams* params, const int* labels /*[B,R,R,R]*/, int B, int R, int* pairs /*[B,P,P,2]*/,
+                          int* floor /*[B,P]*/, int* dropped /*[B]*/, void* stream);
+typedef struct GnrSupportParams {
+    double lean;         /* in [0, 1]: c rests on a when over[a,c] - over[c,a] >= lean * touch[a,c]: 0.25                      */
+    int    max_parts;    /* P: rows of the tables and of every output                                                          */
+    int    min_contact;  /* fewer touching voxel pairs are no contact: 1                                                       */
+    int    min_floor;    /* a part with at least this many voxels in the floor plane stands on the table: 1                    */
+} GnrSupportParams;
+int gnr_part_support_fwd(const GnrSupportParams* params, const int* pairs /*[B,P,P,2]*/, const int* floor /*[B,P]*/,
+                         const int* count /*[B]*/, int B, int* below /*[B,P]*/, int* above /*[B,P]*/, int* carried /*[B,P]*/,
+                         int* orphans /*[B,P]*/, int* layer /*[B,P]*/, int* grounded /*[B,P]*/,
+                         unsigned char* rests_on /*[B,P,P] or NULL*/, void* stream);
 
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
