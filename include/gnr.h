@@ -1157,6 +1157,81 @@ int gnr_part_support_fwd(const GnrSupportParams* params, const int* pairs /*[B,P
                          int* orphans /*[B,P]*/, int* layer /*[B,P]*/, int* grounded /*[B,P]*/,
                          unsigned char* rests_on /*[B,P,P] or NULL*/, void* stream);
 
+/* gnr_part_overlap_fwd, gnr_part_track_fwd: parts across two plans -- which part of the label volume of plan t is which part of the
+ * label volume of plan t+1, and what became of every part: it stayed, it moved, it is gone, it was absorbed into another; a part of
+ * the second volume is the same as before, new, or a fragment.  gnr_volume_parts_fwd numbers each volume on its own, in voxel order,
+ * so taking one ball renumbers every part behind it; the labels of two plans say nothing about each other until their voxels are
+ * compared.  The reference reads the answer off its simulator (check_success, remove_body, remove_and_wait: clutter_removal.py:92-150,
+ * gd/simulation.py); on the real-robot route the next plan's volume is the only witness of a take.  No reference counterpart;
+ * tests/track_reference.py is the same statement in numpy and the calls produce its bits.  Integers throughout, but for two kinds of
+ * double multiply and compare (share, stay), never contracted.
+ *   before, after   any int32 label volumes [B,R,R,R] on the same lattice (gnr_volume_objects_fwd's), 2 <= R <= 256.  A label < 1 is
+ *              no part.  P = max_parts.  index(l) = l for 1 <= l <= P, 0 for l < 1, and *beyond* for l > P.
+ * gnr_part_overlap_fwd: volumes -> table.
+ *   table      [B,P+1,P+1] int32: table[s,i,j] counts the voxels of scene s with index(before) = i and index(after) = j, neither
+ *              beyond, (i,j) != (0,0).  table[s,0,0] is written as 0: voxels free in both are not counted.  Row 0 is "was free",
+ *              column 0 is "is free now".
+ *   beyond     [B] int32: the voxels where either label is > P.
+ *   Every element of both is written by every call (a fill kernel, then integer atomics: any order gives the same bits).
+ * gnr_part_track_fwd: table and counts -> fates.  Per scene nb = min(max(count_before[s], 0), P) and na likewise from count_after;
+ * the old parts are the labels 1..nb, the new parts 1..na; only rows 0..nb and columns 0..na of the table are read.
+ *   size_before[a] = sum over j = 0..na of table[a,j];  size_after[b] = sum over i = 0..nb of table[i,b]  (int32 sums: a table of
+ *              gnr_part_overlap_fwd holds at most R^3 <= 2^24 in all; on any other table the sums wrap as unsigned adds do).
+ *   heir[a]    the b in 1..na with the largest table[a,b], ties to the smallest b; kept only if that count t >= 1 and
+ *              (double)t >= share * (double)size_before[a]; otherwise 0.  Where most of a's voxels are now.
+ *   source[b]  the a in 1..nb with the largest table[a,b], ties to the smallest a; kept only if t >= 1 and
+ *              (double)t >= share * (double)size_after[b]; otherwise 0.  What b is mostly made of.
+ *   a and b are the same part when heir[a] == b and source[b] == a.
+ *   per old part, [B,P] int32, part a in row a-1:
+ *     heir       as above                                  shared     the largest table[a,1..na], even below share; 0 when na == 0
+ *     size_before                                          vacated    table[a,0]
+ *     pieces     the number of b with source[b] == a
+ *     fate       0 STAYED  the same part, and (double)t >= stay * (double)(size_before[a] + size_after[b] - t): t over the union
+ *                1 MOVED   the same part, below stay
+ *                2 GONE    heir == 0
+ *                3 MERGED  heir[a] = b != 0 but source[b] != a: it was absorbed into something else
+ *     Rows nb .. P-1 hold 0, and fate -1.
+ *   per new part, [B,P] int32, part b in row b-1:
+ *     source     as above                                  size_after
+ *     fresh      table[0,b]                                absorbed   the number of a with heir[a] == b
+ *     origin     0 SAME;  1 NEW: source == 0;  2 FRAGMENT: source[b] = a != 0 but heir[a] != b
+ *     Rows na .. P-1 hold 0, and origin -1.
+ *   summary    [B,8] int32: nb, na, stayed, moved, gone, merged, new, fragments.
+ * Limits, in the order they are refused (a null `params` comes first: GNR_ERR_ARG "null pointer"): 1 <= B <= 65535 and, for the
+ * overlap, 2 <= R <= 256 (GNR_ERR_SHAPE); 1 <= max_parts <= GNR_TRACK_MAX_PARTS (GNR_ERR_SHAPE: the table is dense, 257 x 257 words
+ * are 258 KB per scene, and `beyond` says when labels went beyond the rows); share, then stay, finite and in [0, 1]; a null pointer
+ * (GNR_ERR_ARG).  The track call has no R.  Both calls: asynchronous on `stream`, no workspace, no allocation, no synchronisation, no
+ * float atomics, every loop bounded by P + 1 or 64 (they can be captured in a graph and replayed); a refused call has launched nothing
+ * and written nothing.
+ * What it does not answer.  The match is by overlap alone: a part that moved by more than about its own radius shares too few voxels
+ * with itself and reads GONE next to a NEW part -- it is not followed; nothing is matched by shape, and nothing turns.  share = 0.5 and
+ * stay = 0.6 are policy, not measurement: on synthetic balls of radius 3, 5, 8 voxels a shift of one voxel reads STAYED (overlap over
+ * union 0.62, 0.73, 0.83), a shift up to about 0.6 of the radius MOVED, more GONE + NEW (tests/test_part_track.py has the table).
+ * Neither has been run on a network's volumes, whose surface noise between two plans nobody has measured; the integer columns shared,
+ * size, vacated and fresh let a caller apply thresholds of their own.                                                              */
+#define GNR_TRACK_MAX_PARTS 256
+#define GNR_TRACK_STAYED 0
+#define GNR_TRACK_MOVED 1
+#define GNR_TRACK_GONE 2
+#define GNR_TRACK_MERGED 3
+#define GNR_TRACK_SAME 0
+#define GNR_TRACK_NEW 1
+#define GNR_TRACK_FRAGMENT 2
+typedef struct GnrOverlapParams {
+    int max_parts;     /* P: the table has P + 1 rows and columns, 1 .. GNR_TRACK_MAX_PARTS                                    */
+} GnrOverlapParams;
+int gnr_part_overlap_fwd(const GnrOverlapParams* params, const int* before /*[B,R,R,R]*/, const int* after /*[B,R,R,R]*/, int B, int R,
+                         int* table /*[B,P+1,P+1]*/, int* beyond /*[B]*/, void* stream);
+typedef struct GnrTrackParams {
+    double share;      /* in [0, 1]: an heir / a source holds at least this share of the part's voxels: 0.5                    */
+    double stay;       /* in [0, 1]: the same part STAYED when the shared voxels are at least this share of the union: 0.6     */
+    int    max_parts;  /* P: the table's, and the rows of every output                                                         */
+} GnrTrackParams;
+int gnr_part_track_fwd(const GnrTrackParams* params, const int* table /*[B,P+1,P+1]*/, const int* count_before /*[B]*/,
+                       const int* count_after /*[B]*/, int B, int* heir /*[B,P]*/, int* shared /*[B,P]*/, int* size_before /*[B,P]*/,
+                       int* vacated /*[B,P]*/, int* pieces /*[B,P]*/, int* fate /*[B,P]*/, int* source /*[B,P]*/, int* size_after /*[B,P]*/,
+                       int* fresh /*[B,P]*/, int* absorbed /*[B,P]*/, int* origin /*[B,P]*/, int* summary /*[B,8]*/, void* stream);
+
 /* ---- depth route: TSDF fusion of posed depth images (src/gd/perception.py:66-128 over Open3D's UniformTSDFVolume, no colour) ----
  * State per scene: tsdf [R,R,R] and weight [R,R,R], float32, voxel (x,y,z) at x*R*R + y*R + z (the order of volume[0,0,x,y,z]), zero
  * after gnr_tsdf_reset.  gnr_tsdf_integrate fuses V views per scene into it, in the order given, for every voxel:
