@@ -139,6 +139,19 @@ class GnrSupportParams(C.Structure):
     _fields_ = [('lean', C.c_double), ('max_parts', C.c_int), ('min_contact', C.c_int), ('min_floor', C.c_int)]
 
 
+GNR_BALANCE_MAX_PARTS = 256
+GNR_BALANCE_SLOTS = 8
+GNR_BALANCE_DIRECTIONS = 16
+
+
+class GnrFeetParams(C.Structure):
+    _fields_ = [('connectivity', C.c_int), ('max_parts', C.c_int), ('z_min', C.c_int)]
+
+
+class GnrBalanceParams(C.Structure):
+    _fields_ = [('max_parts', C.c_int), ('min_floor', C.c_int)]
+
+
 GNR_TRACK_MAX_PARTS = 256
 
 
@@ -366,6 +379,10 @@ def lib():
     L.gnr_part_contacts_fwd.restype = C.c_int
     L.gnr_part_support_fwd.argtypes = [C.POINTER(GnrSupportParams)] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 8
     L.gnr_part_support_fwd.restype = C.c_int
+    L.gnr_part_feet_fwd.argtypes = [C.POINTER(GnrFeetParams)] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 6
+    L.gnr_part_feet_fwd.restype = C.c_int
+    L.gnr_part_balance_fwd.argtypes = [C.POINTER(GnrBalanceParams)] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 6
+    L.gnr_part_balance_fwd.restype = C.c_int
     L.gnr_part_overlap_fwd.argtypes = [C.POINTER(GnrOverlapParams), C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3
     L.gnr_part_overlap_fwd.restype = C.c_int
     L.gnr_part_track_fwd.argtypes = [C.POINTER(GnrTrackParams)] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 13
@@ -437,7 +454,7 @@ EXPORTED = ['gnr_canonical_weights_floats', 'gnr_packed_weights_floats', 'gnr_pa
             'gnr_volume_raycast_fwd', 'gnr_surface_color_points_fwd', 'gnr_surface_color_pixels_fwd', 'gnr_hand_clearance_fwd', 'gnr_finger_closure_fwd',
             'gnr_volume_objects_workspace_bytes', 'gnr_volume_objects_fwd', 'gnr_grasp_objects_fwd',
             'gnr_volume_distance_workspace_bytes', 'gnr_volume_distance_fwd', 'gnr_volume_parts_workspace_bytes', 'gnr_volume_parts_fwd', 'gnr_grasp_retreat_fwd',
-            'gnr_part_contacts_fwd', 'gnr_part_support_fwd', 'gnr_part_overlap_fwd', 'gnr_part_track_fwd',
+            'gnr_part_contacts_fwd', 'gnr_part_support_fwd', 'gnr_part_feet_fwd', 'gnr_part_balance_fwd', 'gnr_part_overlap_fwd', 'gnr_part_track_fwd',
             'gnr_scatter_workspace_layout', 'gnr_debug_feature_scatter_bytes', 'gnr_debug_feature_scatter']
 
 

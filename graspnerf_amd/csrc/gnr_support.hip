@@ -21,6 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "gnr_closure.h"
 #include "gnr_host.h"
 
 #pragma clang fp contract(off)
@@ -33,6 +34,7 @@ typedef __attribute__((address_space(1))) int gint;
 __device__ inline void add_to(int* p, int v) { __hip_atomic_fetch_add((gint*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 constexpr int MAXP = GNR_SUPPORT_MAX_PARTS, WORDS = MAXP / 32;
+static_assert(MAXP == CLOSURE_PARTS && WORDS == CLOSURE_WORDS, "close_over and bits_of (gnr_closure.h) work on sets of 256 parts");
 
 // launch grid: (ceil(2 P P / 256), B), block 256: thread x of scene b writes pairs element x, the first P also floor, the first dropped
 __global__ __launch_bounds__(256) void k_contacts_fill(int* __restrict__ pairs, int* __restrict__ floor, int* __restrict__ dropped, int P) {
@@ -119,44 +121,6 @@ struct Rule {
     double lean;
     int P, min_contact, min_floor;
 };
-
-// S |= everything reachable from the parts of `todo` along `rows` (S holds `todo` already).  A sweep takes the words of the work list
-// in turn and expands every part of a word, those that join it meanwhile too; a part is expanded once in all, so a word gives at most
-// 32 expansions per sweep, and a sweep that finds work expands at least one part: at most MAXP sweeps.  stop: (when not null) end as
-// soon as S meets it.  -> whether S meets `stop`.
-__device__ inline bool close_over(const unsigned (*rows)[WORDS], unsigned (&S)[WORDS], unsigned (&todo)[WORDS], const unsigned* stop) {
-    for (int sweep = 0; sweep <= MAXP; ++sweep) {
-        bool any = false, met = false;
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) {
-            any = any || todo[w] != 0u;
-            if (stop) met = met || (S[w] & stop[w]) != 0u;
-        }
-        if (met) return true;
-        if (!any) return false;
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) {
-            for (int q = 0; q < 32 && todo[w]; ++q) {
-                const int c = w * 32 + __ffs((int)todo[w]) - 1;
-                todo[w] &= todo[w] - 1u;
-#pragma unroll
-                for (int v = 0; v < WORDS; ++v) {
-                    const unsigned fresh = rows[c][v] & ~S[v];
-                    S[v] |= fresh;
-                    todo[v] |= fresh;
-                }
-            }
-        }
-    }
-    return false;
-}
-
-__device__ inline int bits_of(const unsigned (&S)[WORDS]) {
-    int c = 0;
-#pragma unroll
-    for (int w = 0; w < WORDS; ++w) c += __popc(S[w]);
-    return c;
-}
 
 // launch grid: B, block 256: thread a is part a + 1
 __global__ __launch_bounds__(256) void k_support(const int* __restrict__ pairs, const int* __restrict__ floor, const int* __restrict__ count,

@@ -229,17 +229,11 @@ def best_clear_per_part(columns):
     return best_free_per_part({**{k: columns[k] for k in ('part', 'object') if k in columns}, 'retreat_free': clear})
 
 
-def support_of_plan(tsdf_vol, grasps, *, voxel_size=PLAN_VOXEL_SIZE, origin=(0.0, 0.0, 0.0), device='cuda:0', **params):
-    """The support of a plan: tsdf_vol and the grasps dict as plan_real / plan / plan_depth return them (one scene;
-    retreat.retreat_of_plan's conventions and chain).  params: the solid rule's keys (SOLID_DEFAULTS -- z_min must cut the table slab:
-    it is the floor plane), PART_DEFAULTS', the hand's (HAND_DEFAULTS), RETREAT_DEFAULTS' and SUPPORT_DEFAULTS'.  VolumeDistance on the
-    volume, VolumeParts on its d2_free, GraspObjects on the parts' labels, GraspRetreat on the part each grasp closes on, PartContacts
-    on the labels under the parts' connectivity and the solid rule's z_min, PartSupport on its tables.
-    -> (parts, columns): retreat_of_plan's, with support_from_rows' fields added to the parts and grasp_support_columns' to the
-    columns; take_order(parts) is an order of removal, best_clear_per_part(columns) the best-ranked grasp of every part that comes out
-    and carries nothing."""
-    params = split_params('support', params, SOLID_DEFAULTS, PART_DEFAULTS, HAND_DEFAULTS, RETREAT_DEFAULTS, SUPPORT_DEFAULTS)
-    solid = checked_solid('support', **picked(params, SOLID_DEFAULTS))
+def _plan_support(what, tsdf_vol, grasps, voxel_size, origin, device, params, *more):
+    """support_of_plan's chain for operator `what` (the noun of its errors), which takes the keys of the defaults dicts `more` on top.
+    -> (parts, columns, the VolumeParts result, the PartSupport result, every parameter, the checked scale)."""
+    params = split_params(what, params, SOLID_DEFAULTS, PART_DEFAULTS, HAND_DEFAULTS, RETREAT_DEFAULTS, SUPPORT_DEFAULTS, *more)
+    solid = checked_solid(what, **picked(params, SOLID_DEFAULTS))
     q = part_params(picked(params, PART_DEFAULTS))
     hand = picked(params, HAND_DEFAULTS)
     checked_hand(**hand)
@@ -250,7 +244,7 @@ def support_of_plan(tsdf_vol, grasps, *, voxel_size=PLAN_VOXEL_SIZE, origin=(0.0
     d = torch.device(device)
     vol, B, R = volume_batch(tsdf_vol, d)
     if B != 1:
-        raise ValueError(f'support_of_plan takes the volume of one scene, got {B}')
+        raise ValueError(f'{what}_of_plan takes the volume of one scene, got {B}')
     field = VolumeDistance(d)(vol, scale=scale, **solid)
     res = VolumeParts(d)(field['d2_free'], **q)
     rows = plan_rows(grasps, voxel_size, d)
@@ -265,4 +259,16 @@ def support_of_plan(tsdf_vol, grasps, *, voxel_size=PLAN_VOXEL_SIZE, origin=(0.0
     columns = grasp_parts_from_rows(_host(grasp_objects_rows(gres, 0, n)))
     columns.update(retreat_from_rows(_host(retreat_rows(rres, 0, n))))
     columns.update(grasp_support_columns(columns['part'], parts))
-    return parts, columns
+    return parts, columns, res, sres, {**params, **solid, **q}, scale
+
+
+def support_of_plan(tsdf_vol, grasps, *, voxel_size=PLAN_VOXEL_SIZE, origin=(0.0, 0.0, 0.0), device='cuda:0', **params):
+    """The support of a plan: tsdf_vol and the grasps dict as plan_real / plan / plan_depth return them (one scene;
+    retreat.retreat_of_plan's conventions and chain).  params: the solid rule's keys (SOLID_DEFAULTS -- z_min must cut the table slab:
+    it is the floor plane), PART_DEFAULTS', the hand's (HAND_DEFAULTS), RETREAT_DEFAULTS' and SUPPORT_DEFAULTS'.  VolumeDistance on the
+    volume, VolumeParts on its d2_free, GraspObjects on the parts' labels, GraspRetreat on the part each grasp closes on, PartContacts
+    on the labels under the parts' connectivity and the solid rule's z_min, PartSupport on its tables.
+    -> (parts, columns): retreat_of_plan's, with support_from_rows' fields added to the parts and grasp_support_columns' to the
+    columns; take_order(parts) is an order of removal, best_clear_per_part(columns) the best-ranked grasp of every part that comes out
+    and carries nothing."""
+    return _plan_support('support', tsdf_vol, grasps, voxel_size, origin, device, params)[:2]

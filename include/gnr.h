@@ -1157,6 +1157,76 @@ int gnr_part_support_fwd(const GnrSupportParams* params, const int* pairs /*[B,P
                          int* orphans /*[B,P]*/, int* layer /*[B,P]*/, int* grounded /*[B,P]*/,
                          unsigned char* rests_on /*[B,P,P] or NULL*/, void* stream);
 
+/* gnr_part_feet_fwd, gnr_part_balance_fwd: the balance of the parts -- on which of its voxels a part stands, whether its centre of mass
+ * lies over them, by how much, and what tips over, and falls, when a part is taken.  gnr_part_support_fwd's orphans are the parts that
+ * lose EVERY footing; the commoner failure of a pile is a part that keeps one footing and tips over it (a plank across two pillars,
+ * one pillar taken).  The reference leaves the question to physics (remove_and_wait, gd/simulation.py).  No reference counterpart;
+ * tests/balance_reference.py is the same statement in numpy and the calls produce its bits.  Integers throughout, but for one double
+ * multiply and one double divide per direction of a margin, never contracted.
+ *   lattice, labels, neighbours   gnr_part_contacts_fwd's: k is up; P = max_parts rows, part c is row c-1; n = min(max(count[s], 0), P),
+ *              the parts are the labels 1..n.
+ *   rests_on   [B,P,P] bytes, gnr_part_support_fwd's or any: [c-1,a-1] != 0 reads "c rests on a".
+ * gnr_part_feet_fwd: labels and relation -> tables.
+ *   slots      Part c has GNR_BALANCE_SLOTS = 8 foot slots.  Slot 0 is the floor plane k == z_min.  The footings of c <= n are the a
+ *              with rests_on[c-1,a-1] != 0, a <= n, a != c; they take the slots 1, 2, .. in ascending label order, and from the
+ *              seventh on they share slot 7.  slots[s,c-1,a-1] (uint8) is the slot of footing a, 0 where a is no footing of c; the rows
+ *              of c > n hold 0.  crowded[s,c-1] = 1 when slot 7 holds two or more footings (eight footings or more), else 0.
+ *   feet       A voxel u with label c, 1 <= c <= P, is a foot in slot 0 when k_u == z_min, and a foot in slot t >= 1 when some
+ *              neighbour w with k_w < k_u carries a label a with 1 <= a <= P, a != c and slots[c-1,a-1] == t.  A voxel counts once per
+ *              slot and may be in several.  feet[s,c-1,t] (int32) is the number of foot voxels of slot t.  z_min == R: no slot 0.
+ *   reach      reach[s,c-1,t,q] (int32) = the largest dx_q * i + dy_q * j over the foot voxels of slot t, INT32_MIN where there are
+ *              none.  The GNR_BALANCE_DIRECTIONS = 16 directions (dx, dy) are (1,0) (2,1) (1,1) (1,2) (0,1) (-1,2) (-1,1) (-2,1), then
+ *              their negatives in the same order.
+ *   moments    moments[s,c-1,:] (int64) = n_c, sum i, sum j, sum k, sum i^2, sum j^2, sum k^2, sum i j, sum i k, sum j k over the voxels
+ *              with label c.  Labels outside 1..P are ignored (gnr_part_contacts_fwd's `dropped` reports them).
+ *   Every element of moments, slots, feet, reach and crowded is written by every call (a fill kernel, then integer atomics: any
+ *   order gives the same bits).
+ * gnr_part_balance_fwd: tables -> balance.
+ *   balance    of a mass (m, Si, Sj) over a set of slots of part c.  A slot is usable when feet[c-1,t] >= 1, slot 0 when feet[c-1,0]
+ *              >= min_floor.  r_q = the largest reach[c-1,t,q] over the usable slots of the set; H_q = 2 r_q + |dx_q| + |dy_q| -- the
+ *              support function, doubled, of the hull of the foot voxels' unit squares; num_q = m * H_q - 2 * (dx_q * Si + dy_q * Sj)
+ *              in int64.  Balanced: every num_q >= 0.  margin = the least (double)num_q / ((double)(2 m) * len_q), in voxels, with
+ *              len_q = 1, sqrt 2 or sqrt 5 as the nearest double: one multiply, then one divide.  With no usable slot in the set, or
+ *              with m < 1, the mass is not balanced and the margin is -inf.
+ *   balanced[c], margin[c]   for c <= n: the balance of c's own mass (moments[c-1,0..2]) over all its slots.
+ *   tips       tips[s,c-1,a-1] = 1 for c, a <= n, c != a, with rests_on[c-1,a-1] != 0, when c's own mass is not balanced over its
+ *              slots other than slots[c-1,a-1] (read & 7); 0 elsewhere.  When a shares the crowded slot 7 the whole slot goes: on
+ *              the careful side.
+ *   unsettles[a]  the number of c with tips[c-1,a-1].
+ *   falls[a]   the number of parts other than a among those c and everything they carry (gnr_part_support_fwd's closure of "rests
+ *              on", over this call's rests_on).  falls >= orphans, element by element, when rests_on, count, z_min and min_floor are
+ *              the support's own.
+ *   Rows n .. P-1 hold balanced 0, margin -inf, unsettles 0, falls 0.
+ * Limits, in the order they are refused (a null `params` comes first: GNR_ERR_ARG "null pointer"): 1 <= B <= 65535 and, for the
+ * feet, 2 <= R <= 256 (GNR_ERR_SHAPE); 1 <= max_parts <= GNR_BALANCE_MAX_PARTS (GNR_ERR_SHAPE); connectivity 6, 18 or 26; 0 <= z_min
+ * <= R; min_floor >= 1; a null required pointer (GNR_ERR_ARG; `tips` may be NULL).  The balance call has no R; its int64 products are
+ * exact on the tables of the feet call (m <= 2^24, coordinates <= 255) and wrap on others.  Both calls: asynchronous on `stream`, no
+ * workspace, no allocation, no synchronisation, no float atomics, every loop bounded by P, 64, 16 or 8 (they can be captured in a
+ * graph and replayed); a refused call has launched nothing and written nothing.
+ * What it does not answer.  It is the statics of each part's own mass: what a part carries does not shift its balance point, and
+ * nothing slides or rotates.  A part on a single floor voxel reads a margin of 0.5 (voxelised balls do).  Under connectivity 18 or 26
+ * a foot voxel may overhang its footing by one diagonal; connectivity 6 gives the strict footprint.  There is no threshold of its
+ * own: the rule is integer geometry plus the support's min_floor.  It has not been run on a network's volume.                      */
+#define GNR_BALANCE_MAX_PARTS 256
+#define GNR_BALANCE_SLOTS 8
+#define GNR_BALANCE_DIRECTIONS 16
+typedef struct GnrFeetParams {
+    int connectivity;  /* 6, 18 or 26: the parts' own                                                                          */
+    int max_parts;     /* P: rows of the tables, 1 .. GNR_BALANCE_MAX_PARTS                                                    */
+    int z_min;         /* the floor plane: the solid rule's z_min; R: none                                                     */
+} GnrFeetParams;
+int gnr_part_feet_fwd(const GnrFeetParams* params, const int* labels /*[B,R,R,R]*/, const unsigned char* rests_on /*[B,P,P]*/,
+                      const int* count /*[B]*/, int B, int R, long long* moments /*[B,P,10]*/, unsigned char* slots /*[B,P,P]*/,
+                      int* feet /*[B,P,8]*/, int* reach /*[B,P,8,16]*/, int* crowded /*[B,P]*/, void* stream);
+typedef struct GnrBalanceParams {
+    int max_parts;     /* P: rows of the tables and of every output                                                            */
+    int min_floor;     /* slot 0 is usable with at least this many voxels in the floor plane: the support's, 1                 */
+} GnrBalanceParams;
+int gnr_part_balance_fwd(const GnrBalanceParams* params, const long long* moments /*[B,P,10]*/, const int* feet /*[B,P,8]*/,
+                         const int* reach /*[B,P,8,16]*/, const unsigned char* slots /*[B,P,P]*/, const unsigned char* rests_on /*[B,P,P]*/,
+                         const int* count /*[B]*/, int B, int* balanced /*[B,P]*/, double* margin /*[B,P]*/, int* unsettles /*[B,P]*/,
+                         int* falls /*[B,P]*/, unsigned char* tips /*[B,P,P] or NULL*/, void* stream);
+
 /* gnr_part_overlap_fwd, gnr_part_track_fwd: parts across two plans -- which part of the label volume of plan t is which part of the
  * label volume of plan t+1, and what became of every part: it stayed, it moved, it is gone, it was absorbed into another; a part of
  * the second volume is the same as before, new, or a fragment.  gnr_volume_parts_fwd numbers each volume on its own, in voxel order,
